@@ -1,9 +1,19 @@
 #!/usr/bin/env python3
 """bench.py -- voxels/s of the per-voxel fitting hot path on N MI355X (one process per GPU).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload triexp|biexp|mono|nnls] [--no-secondary]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload triexp|biexp|mono|nnls] [--dump-outputs DIR]
+                    [--full [--no-secondary] [--no-host-mode] ...]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, warms up, times the K steps, writes the outputs of the last step when --dump-outputs is given, and
+prints the line.  Everything else the line can carry -- the NNLS leg beside triexp, the two-in-flight throughput, the
+PCIe-inclusive host-array legs, the CPU baselines, the standalone roofline probes, the noise sweep -- runs only with --full
+(each of them can still be left out there with its --no-* option).
+
+--dump-outputs DIR: after the timed steps, the arrays the timed path handed back in its last step, as DIR/<name>.npy in
+float64 -- for the curve fit popt / pcov / status / nfev / cost, for the NNLS coefficients / rnorm / status / iters -- over a
+fixed, seeded sample of the volume's voxels (DIR/voxel_index.npy, every voxel when the volume is small), at most 48 MB in all.
 
 A "step" is one pass of the hot path (one batched fit through the C ABI, device-pointer mode) over ONE seed-fixed
 synthetic volume that is already resident in HBM.  Default workload: BASELINE.json configs[2] (triexp bounded TRF,
@@ -61,6 +71,10 @@ def parse(argv=None):
     ap.add_argument("--workload", default="triexp", choices=["triexp", "biexp", "mono", "nnls"])
     ap.add_argument("--jac", default="fd", choices=["fd", "analytic"])
     ap.add_argument("--no-pcov", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the secondary NNLS leg, throughput, host-array legs, CPU baselines, roofline probes and noise sweep")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step (a seeded sample of the voxels) as DIR/<name>.npy")
     ap.add_argument("--no-secondary", action="store_true", help="skip the NNLS leg that is reported beside triexp")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-host-mode", action="store_true", help="skip the PCIe-inclusive host-pointer legs")
@@ -235,6 +249,13 @@ class CurvefitLeg:
         ok = (self.status > 0).double().mean().item()
         return {"converged_frac": ok, "mean_nfev": self.nfev.double().mean().item()}
 
+    def outputs(self):
+        """What a caller of the timed path receives: name -> (device tensor, voxel axis)."""
+        out = {"popt": (self.popt, 1), "status": (self.status, 0), "nfev": (self.nfev, 0), "cost": (self.cost, 0)}
+        if self.pcov is not None:
+            out["pcov"] = (self.pcov, 0)
+        return out
+
     def pipelined(self, steps, world, dist):
         """The same K passes with TWO in flight: launches alternate between two streams and two sets of result buffers, as a
         caller with a queue of independent batches would issue them.  A single pass ends in a straggler tail (a handful of
@@ -374,6 +395,10 @@ class NnlsLeg:
     def check(self):
         return {"converged_frac": (self.status == 1).double().mean().item(),
                 "mean_iters": self.iters.double().mean().item()}
+
+    def outputs(self):
+        """What a caller of the timed path receives: name -> (device tensor, voxel axis)."""
+        return {"coefficients": (self.coeff, 0), "rnorm": (self.rnorm, 0), "status": (self.status, 0), "iters": (self.iters, 0)}
 
     def host_mode(self, reps=3):
         """PNX_MEM_HOST solve: numpy signal in, numpy (n_vox, 250) float64 spectra out.  The whole volume when the host
@@ -547,6 +572,42 @@ def timed(leg, steps, warmup, world, dist, torch):
 
     dt = max_over_ranks(dt, dist if world > 1 else None, device="cuda" if dist is None or dist.get_backend() == "nccl" else "cpu")
     return dt, kernel_ms
+
+
+DUMP_BYTES = 48 << 20  # --dump-outputs budget: every file together, voxel_index.npy included
+
+
+def dump_sample(n_total, bytes_per_voxel):
+    """Global voxel indices that --dump-outputs writes: every voxel when the volume fits the budget, else a fixed, seeded
+    sample (the same for every run and every rank count), ascending."""
+    from pyneapple_amd import synth
+
+    k = min(n_total, DUMP_BYTES // bytes_per_voxel)
+    if k == n_total:
+        return np.arange(n_total, dtype=np.int64)
+    return np.sort(np.random.default_rng(synth.SEED).choice(n_total, size=k, replace=False))
+
+
+def dump_outputs(leg, out_dir, n_total, rank, world, dist):
+    """The arrays of the last timed step, restricted to dump_sample's voxels, as out_dir/<name>.npy (float64; status and counts
+    are exact in it).  Every rank contributes the sampled voxels of its row range; rank 0 writes them in volume order."""
+    import torch
+
+    outs = leg.outputs()
+    per_voxel = 8 * (1 + sum(t.numel() // max(1, t.shape[ax]) for t, ax in outs.values()))
+    idx = dump_sample(n_total, per_voxel)
+    a, b = leg.rows
+    sel = torch.from_numpy(idx[(idx >= a) & (idx < b)] - a).to(leg.device)
+    part = {k: t.index_select(ax, sel).to(torch.float64).cpu().numpy() for k, (t, ax) in outs.items()}
+    if world > 1:
+        parts = [None] * world
+        dist.all_gather_object(parts, part)
+        part = {k: np.concatenate([p[k] for p in parts], axis=outs[k][1]) for k in part}
+    if rank == 0:
+        os.makedirs(out_dir, exist_ok=True)
+        np.save(os.path.join(out_dir, "voxel_index.npy"), idx.astype(np.float64))
+        for k, v in part.items():
+            np.save(os.path.join(out_dir, k + ".npy"), np.ascontiguousarray(v))
 
 
 # ---------------------------------------------------------------------------------------------------------------
@@ -788,6 +849,8 @@ def main(argv=None):
     else:
         leg = CurvefitLeg(args.workload, device, args.jac, want_pcov, n_total, rows)
     dt, kernel_ms = timed(leg, args.steps, args.warmup, world, dist, torch)
+    if args.dump_outputs:
+        dump_outputs(leg, args.dump_outputs, n_total, rank, world, dist)
     value = n_total * args.steps / dt
     k_avg = float(np.mean(kernel_ms)) * 1e-3
     achieved = leg.bytes_per_voxel * leg.n_vox / k_avg / 1e9
@@ -829,7 +892,9 @@ def main(argv=None):
                                        "simd_valu_busy": min(1.0, fl.get("valu_issue_busy", 0.0) * 1),
                                        "fp64_share_of_valu_instructions": fl.get("fp64_share_of_valu_instructions"),
                                        "source": fl["source"], "source_id": fl["source_id"]}
-    if args.workload != "nnls" and not args.no_pipelined:
+    # everything below the headline figure runs with --full only
+    full = args.full
+    if full and args.workload != "nnls" and not args.no_pipelined:
         out["pipelined"] = leg.pipelined(max(args.steps, 4), world, dist)  # every rank takes part (barriers)
         # `value` is the strong-scaling figure north_star asks for: ONE volume, one pass at a time, so at N ranks it ends in the
         # straggler tail of an N-th of the volume.  `throughput` is what N ranks sustain on a queue of independent volumes
@@ -838,15 +903,15 @@ def main(argv=None):
         out["throughput"] = {"value": out["pipelined"]["value"], "unit": "voxels/s", "n_gpus": world,
                              "mode": "two passes in flight per rank on its shard; voxels of the whole volume x passes / max over ranks"}
     solo = rank == 0 and world == 1
-    if solo and not args.no_host_mode:
+    if full and solo and not args.no_host_mode:
         out["host_mode"] = leg.host_mode()
         if args.workload != "nnls":
             out["host_mode_f32"] = leg.host_mode_f32()
-    if world > 1 and not args.no_host_mode:  # every rank takes part (barriers)
+    if full and world > 1 and not args.no_host_mode:  # every rank takes part (barriers)
         out["host_mode"] = host_mode_ranks(leg, dist, world, torch, n_total)
-    if solo and not args.no_cpu_baseline:
+    if full and solo and not args.no_cpu_baseline:
         out["cpu_baseline"] = leg.cpu_baseline()
-    if args.workload == "triexp" and not args.no_secondary:
+    if full and args.workload == "triexp" and not args.no_secondary:
         del leg
         torch.cuda.empty_cache()
         n2, rows2 = volume_rows("nnls", args, rank, world)
@@ -882,7 +947,7 @@ def main(argv=None):
         out["secondary"] = sec
         del leg2
         torch.cuda.empty_cache()
-    if args.workload == "triexp" and not args.no_secondary and rank == 0:
+    if full and args.workload == "triexp" and not args.no_secondary and rank == 0:
         # The two sub-millisecond roofline probes.  Whatever runs right after gigabytes of device memory have been released is
         # slow for a few hundred milliseconds on this box (measured both ways round: the sweep's launch burst at 0.29 ms per
         # enqueue right after the NNLS leg was freed; the host-mode leg at 68-77 ms instead of 51 when it followed the probes'

@@ -6,6 +6,8 @@ import json
 import os
 import sys
 
+import numpy as np
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import bench  # noqa: E402
@@ -98,3 +100,46 @@ def test_pinning_two_ranks_without_numa_information_splits_the_affinity_mask():
     if len(outs[0]["before"]) >= 2:
         assert not (a & b)
     assert outs[0]["r"]["cpus"] == bench._fmt_cpus(a)
+
+
+def test_plain_run_is_lean_and_full_opts_in():
+    a = bench.parse(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert a.steps == 7 and a.warmup == 2 and not a.full and a.dump_outputs is None
+    b = bench.parse(["--full", "--dump-outputs", "out"])
+    assert b.full and b.dump_outputs == "out"
+
+
+def test_dump_sample_is_seed_fixed_and_within_budget():
+    n = 256 * 256 * 64
+    per_voxel = 8 * (1 + 5 + 25 + 3)  # voxel index, popt, pcov, status / nfev / cost
+    a, b = bench.dump_sample(n, per_voxel), bench.dump_sample(n, per_voxel)
+    assert (a == b).all() and len(a) * per_voxel <= bench.DUMP_BYTES and len(a) > 100000
+    assert (a[1:] > a[:-1]).all() and a[0] >= 0 and a[-1] < n
+    assert (bench.dump_sample(1024, per_voxel) == np.arange(1024)).all()  # a small volume is written whole
+
+
+def test_dump_outputs_writes_the_sampled_voxels_of_the_last_step(tmp_path):
+    """dump_outputs on a stand-in leg with host tensors: one float64 .npy per output, the voxel axis restricted to the sample."""
+    import torch
+
+    n_vox, n = 4096, 3
+    popt = torch.arange(n * n_vox, dtype=torch.float64).reshape(n, n_vox)
+    status = (torch.arange(n_vox) % 3).to(torch.int8)
+
+    class Leg:
+        rows, device = (0, n_vox), torch.device("cpu")
+
+        def outputs(self):
+            return {"popt": (popt, 1), "status": (status, 0)}
+
+    old = bench.DUMP_BYTES
+    bench.DUMP_BYTES = 8 * (1 + n + 1) * 1000  # forces a sample of 1000 voxels
+    try:
+        bench.dump_outputs(Leg(), str(tmp_path), n_vox, 0, 1, None)
+    finally:
+        bench.DUMP_BYTES = old
+    idx = np.load(tmp_path / "voxel_index.npy")
+    p, s = np.load(tmp_path / "popt.npy"), np.load(tmp_path / "status.npy")
+    assert idx.dtype == p.dtype == s.dtype == np.float64 and len(idx) == 1000
+    k = idx.astype(np.int64)
+    assert (p == popt.numpy()[:, k]).all() and (s == status.numpy()[k]).all()

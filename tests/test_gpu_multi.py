@@ -123,7 +123,7 @@ def test_bench_two_ranks_as_child_processes_on_one_card():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     env.update(PNX_BENCH_SHARE_GPU="1", PNX_BENCH_BACKEND="gloo")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--voxels", "262144", "--steps", "2",
-                        "--warmup", "1", "--no-cpu-baseline"], env=env,
+                        "--warmup", "1", "--full", "--no-cpu-baseline"], env=env,
                        capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]
@@ -158,7 +158,7 @@ def test_bench_four_ranks_on_one_card():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     env.update(PNX_BENCH_SHARE_GPU="1", PNX_BENCH_BACKEND="gloo")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "4", "--voxels", "524288", "--steps", "2",
-                        "--warmup", "1", "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=900)
+                        "--warmup", "1", "--full", "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]
     assert len(lines) == 1, r.stdout[-2000:]
@@ -192,7 +192,7 @@ def test_bench_two_ranks_under_torch_distributed_run_on_one_card():
     env.update(PNX_BENCH_SHARE_GPU="1", PNX_BENCH_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
                         "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--voxels", "262144", "--steps", "2",
-                        "--warmup", "1", "--no-cpu-baseline", "--no-host-mode"], env=env, capture_output=True, text=True, timeout=900)
+                        "--warmup", "1", "--full", "--no-cpu-baseline", "--no-host-mode"], env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.strip().startswith("{")]
     assert len(lines) == 1, r.stdout[-2000:]
