@@ -349,6 +349,107 @@ struct AsyncBuf {
     }
 };
 
+// ---- the staging steps of a call, each written once as a loop over its ArrayTable (pnx_host_pipeline.hpp) ------------
+// Device buffers of an ArrayTable: the fp64 working copy the kernels read or write (dev) and the buffer the caller's array is
+// copied to or from (xfer: a float buffer beside it for a widened array, the same memory otherwise).
+struct DevSet {
+    void *dev[ArrayTable::kMax] = {};
+    void *xfer[ArrayTable::kMax] = {};
+    double *d(int k) const { return (double *)dev[k]; }
+};
+// Staged: every buffer of a host-array call for `cap` voxels.  Results: the outputs only, fp64 (the deferred hand-over's batch).
+// CallerDevice: PNX_MEM_DEVICE calls -- the caller's arrays from voxel v0 on are the transfer buffers; only the fp64 copies of
+// widened arrays are carved.
+enum class Carve { Staged, Results, CallerDevice };
+static void carve(Carver &cv, const ArrayTable &A, size_t cap, DevSet &D, Carve mode = Carve::Staged, size_t v0 = 0) {
+    for (int k = 0; k < A.n; ++k) {
+        const HostArray &a = A.a[k];
+        D.dev[k] = D.xfer[k] = nullptr;
+        if (mode == Carve::CallerDevice) {
+            if (!a.host) continue;
+            D.xfer[k] = (char *)a.host + v0 * a.w * a.esize;
+            D.dev[k] = a.widen ? cv.take(cap * a.w * sizeof(double)) : D.xfer[k];
+        } else if ((a.host || a.always) && (a.out || mode == Carve::Staged)) {
+            D.dev[k] = cv.take(cap * a.w * (a.widen ? sizeof(double) : a.esize));
+            D.xfer[k] = a.widen && a.host && mode == Carve::Staged ? cv.take(cap * a.w * a.esize) : D.dev[k];
+        }
+    }
+}
+static int alloc_carved(DevBuf &slab, const ArrayTable &A, size_t cap, DevSet &D) {
+    for (int pass = 0; pass < 2; ++pass) {  // pass 0 sizes the slab, pass 1 carves it
+        Carver cv;
+        cv.base = (char *)slab.p;
+        carve(cv, A, cap, D);
+        if (pass == 0)
+            if (int rc = slab.alloc(cv.off)) return rc;
+    }
+    return PNX_OK;
+}
+
+// Voxels [v0, v0 + c) of a call of nv voxels, at voxel dv0 of the device buffers, whose parameter-major rows lie `stride` voxels
+// apart.  An array is `rows` pieces of `len` contiguous elements within the span.
+struct Span {
+    size_t nv, v0, c, dv0, stride;
+    size_t rows(const HostArray &a) const { return a.pmajor ? a.w : 1; }
+    size_t len(const HostArray &a) const { return a.pmajor ? c : c * a.w; }
+    size_t host_at(const HostArray &a, size_t r) const { return a.pmajor ? r * nv + v0 : v0 * a.w; }
+    size_t dev_at(const HostArray &a, size_t r) const { return a.pmajor ? r * stride + dv0 : dv0 * a.w; }
+    bool dense(const HostArray &a) const { return !a.pmajor || (stride == c && dv0 == 0); }  // one block on the device
+};
+static Span ring_span(const std::vector<size_t> &bounds, int k) {  // chunk k of the ring: device stride = the chunk's own count
+    const size_t v0 = bounds[(size_t)k], c = bounds[(size_t)k + 1] - v0;
+    return Span{bounds.back(), v0, c, 0, c};
+}
+
+// fp32 <-> fp64 of the widened arrays of one direction (out: fp64 -> float) within the span
+static int convert(const ArrayTable &A, const DevSet &D, const Span &s, bool out, hipStream_t st) {
+    for (int k = 0; k < A.n; ++k) {
+        const HostArray &a = A.a[k];
+        if (!a.widen || !a.host || a.out != out) continue;
+        const bool one = s.dense(a);
+        for (size_t r = 0; r < (one ? 1 : s.rows(a)); ++r) {
+            const size_t at = one ? s.dv0 * a.w : s.dev_at(a, r), n = one ? s.c * a.w : s.len(a);
+            const int rc = out ? cvt(D.d(k) + at, (float *)D.xfer[k] + at, n, st) : cvt((const float *)D.xfer[k] + at, D.d(k) + at, n, st);
+            if (rc) return rc;
+        }
+    }
+    return PNX_OK;
+}
+static int widen(const ArrayTable &A, const DevSet &D, const Span &s, hipStream_t st) { return convert(A, D, s, false, st); }
+static int narrow(const ArrayTable &A, const DevSet &D, const Span &s, hipStream_t st) { return convert(A, D, s, true, st); }
+
+// H2D of the requested inputs within the span, in table order; widen_each: each piece's conversion right behind its copy
+static int h2d(const ArrayTable &A, const DevSet &D, const Span &s, hipStream_t st, bool widen_each = false) {
+    for (int k = 0; k < A.n; ++k) {
+        const HostArray &a = A.a[k];
+        if (a.out || !a.host) continue;
+        for (size_t r = 0; r < s.rows(a); ++r) {
+            const size_t h = s.host_at(a, r), d = s.dev_at(a, r), n = s.len(a);
+            PNX_HIP(hipMemcpyAsync((char *)D.xfer[k] + d * a.esize, (const char *)a.host + h * a.esize, n * a.esize, hipMemcpyHostToDevice, st));
+            if (widen_each && a.widen)
+                if (int rc = cvt((const float *)D.xfer[k] + d, D.d(k) + d, n, st)) return rc;
+        }
+    }
+    return PNX_OK;
+}
+static int d2h(const ArrayTable &A, const DevSet &D, const Span &s, hipStream_t st) {
+    for (int k = 0; k < A.n; ++k) {
+        const HostArray &a = A.a[k];
+        if (!a.out || !a.host) continue;
+        for (size_t r = 0; r < s.rows(a); ++r)
+            PNX_HIP(hipMemcpyAsync((char *)a.host + s.host_at(a, r) * a.esize, (const char *)D.xfer[k] + s.dev_at(a, r) * a.esize,
+                                   s.len(a) * a.esize, hipMemcpyDeviceToHost, st));
+    }
+    return PNX_OK;
+}
+static void touch(const ArrayTable &A, const Span &s) {  // the result pages of the span (touch_pages)
+    for (int k = 0; k < A.n; ++k) {
+        const HostArray &a = A.a[k];
+        if (!a.out || !a.host) continue;
+        for (size_t r = 0; r < s.rows(a); ++r) touch_pages((char *)a.host + s.host_at(a, r) * a.esize, s.len(a) * a.esize);
+    }
+}
+
 // ---- host-pointer calls, streamed --------------------------------------------------------------------------------
 // The chunk ring above launches one persistent kernel per chunk, and every one of them ends in a drain tail (lanes whose
 // queue ran dry idle until the slowest voxel of their wave has converged): seven tails cost C3 about 10 ms of its 50.
@@ -400,12 +501,9 @@ struct StreamRes {
         // comes (measured: with torch's streams in the process the uploads sat behind the kernel until its poll limit).
         // Queues are pooled per priority, so the kernel's stream gets the lowest priority and a queue of its own; copies and
         // epilogues stay at the default priority (and win the dispatch arbitration against the fit, which is what one wants).
-        int prio_least = 0, prio_greatest = 0;
-        PNX_HIP(hipDeviceGetStreamPriorityRange(&prio_least, &prio_greatest));
-        const int prio_other = prio_least > 0 ? 0 : prio_greatest;  // numerically lower = higher priority
         while ((int)s.size() < n) {
             hipStream_t q = nullptr;
-            PNX_HIP(hipStreamCreateWithPriority(&q, hipStreamNonBlocking, s.size() == 1 ? prio_least : prio_other));
+            if (!HipBackend::stream_create(&q, s.size() == 1)) return set_error(PNX_ERR_HIP, "streamed curve fit: stream setup failed");
             s.push_back(q);
         }
         return PNX_OK;
@@ -463,60 +561,56 @@ struct StreamLease {
     }
 };
 
-template <typename T>
-static int curvefit_streamed(const pnx_curvefit_opts *o, size_t nv, const double *bd, const T *y, const double *p0d,
-                             const double *lod, const double *hid, const T *p0_pv, const T *lo_pv, const T *hi_pv,
-                             const double *fxd, const T *fixed_pv, T *popt, T *pcov, int8_t *status, int32_t *nfev, T *cost,
-                             int gshift, DeviceInfo *dev, int device, hipStream_t user_stream, const HostCallGuard &hg) {
-    constexpr bool F32 = sizeof(T) == 4;
-    const int n = o->n_free, n_b = o->n_b;
-    const int n_fpv = fixed_pv ? o->n_fixed : 0;  // per-voxel fixed maps (n_fixed, n_vox): uploaded piece by piece like the signal
-    const bool pv = p0_pv != nullptr;             // per-voxel p0 / bounds (n_free, n_vox) each: likewise
+// the arrays of a curve fit, in the order of their copies (ArrayTable)
+enum { CF_Y, CF_P0, CF_LO, CF_HI, CF_FX, CF_POPT, CF_PCOV, CF_STAT, CF_NFEV, CF_COST };
+struct CurvefitShared {  // the b-values and the start values, bounds and fixed values that are not per voxel, as fp64
+    double b[PNX_MAX_BVALUES], p0[PNX_MAX_PARAMS], lo[PNX_MAX_PARAMS], hi[PNX_MAX_PARAMS], fx[PNX_MAX_PARAMS];
+};
+static const double *per_voxel_or(const ArrayTable &A, const DevSet &D, int k, const double *shared) { return A.a[k].host ? D.d(k) : shared; }
+// the fit of c voxels on the fp64 buffers of D
+static int curvefit_on(const pnx_curvefit_opts *o, const ArrayTable &A, const CurvefitShared &sh, const DevSet &D, size_t c, DeviceInfo *dev,
+                       hipStream_t st, const StreamLaunch *sl = nullptr, const int32_t *order = nullptr) {
+    return curvefit_device(o, (int64_t)c, sh.b, D.d(CF_Y), per_voxel_or(A, D, CF_P0, sh.p0), per_voxel_or(A, D, CF_LO, sh.lo),
+                           per_voxel_or(A, D, CF_HI, sh.hi), per_voxel_or(A, D, CF_FX, sh.fx), D.d(CF_POPT), D.d(CF_PCOV),
+                           (int8_t *)D.dev[CF_STAT], (int32_t *)D.dev[CF_NFEV], D.d(CF_COST), dev, st, sl, order);
+}
+
+static int curvefit_streamed(const pnx_curvefit_opts *o, const ArrayTable &A, const CurvefitShared &sh, size_t nv, int gshift,
+                             DeviceInfo *dev, int device, hipStream_t user_stream, const HostCallGuard &hg) {
+    const int n = o->n_free;
+    const bool pv = A.a[CF_P0].host != nullptr;  // per-voxel p0 / bounds (n_free, n_vox) each: uploaded piece by piece like the signal
     const size_t G = (size_t)1 << gshift;
     const int n_gran = (int)((nv + G - 1) >> gshift);
     // voxels per upload / watermark step.  Per-voxel p0 / bounds ride along as 3 n row slices per piece: at 128 Ki voxels those
     // are 1 MB copies and the upload (1.57 GB for C3) runs at 36 GB/s and holds the kernel back (53-58 ms, the ring's 55); at
     // 512 Ki 47-50 ms (profiles/stream_pv_probe.py)
-    const size_t in_piece = (size_t)dev_env_int("PNX_STREAM_IN_CHUNK", p0_pv ? 1 << 19 : 1 << 17, 1024, 1 << 26);
+    const size_t in_piece = (size_t)dev_env_int("PNX_STREAM_IN_CHUNK", pv ? 1 << 19 : 1 << 17, 1024, 1 << 26);
     const int n_in = (int)((nv + in_piece - 1) / in_piece);
-    const bool need_stat = status || pcov, need_cost = cost || pcov;
     const bool trace = dev_getenv("PNX_HOST_TRACE") != nullptr;
     const auto t_call = std::chrono::steady_clock::now();
     auto now = [&]() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_call).count(); };
     if (user_stream) PNX_HIP(hipStreamSynchronize(user_stream));
 
-    // device: the whole volume's fp64 working set (+ the T-typed transfer buffers of the float32 entry point) + control block
+    // device: the whole volume's fp64 working set (+ the float transfer buffers of the float32 entry point) + control block
     StreamLease lease(device);
     StreamRes &res = *lease.r;
-    double *dy = nullptr, *dpopt = nullptr, *dpcov = nullptr, *dcost = nullptr, *dfx = nullptr, *dp0 = nullptr, *dlo = nullptr, *dhi = nullptr;
-    T *ty = nullptr, *tpopt = nullptr, *tpcov = nullptr, *tcost = nullptr, *tfx = nullptr, *tp0 = nullptr, *tlo = nullptr, *thi = nullptr;
-    int8_t *dstat = nullptr;
-    int32_t *dnfev = nullptr;
+    DevSet D;
     StreamCtl *ctl = nullptr;
     const size_t ctl_bytes = sizeof(StreamCtl) + sizeof(unsigned int) * (size_t)n_gran;
     int rc;
     for (int pass = 0; pass < 2; ++pass) {
         Carver c;
         c.base = (char *)res.slab;
-        auto both = [&](double *&d64, T *&t, size_t count) {
-            d64 = (double *)c.take(count * sizeof(double));
-            t = F32 ? (T *)c.take(count * sizeof(T)) : (T *)d64;
-        };
-        both(dy, ty, nv * n_b);
-        if (n_fpv) both(dfx, tfx, nv * n_fpv);
-        if (pv) {
-            both(dp0, tp0, nv * n);
-            both(dlo, tlo, nv * n);
-            both(dhi, thi, nv * n);
-        }
-        both(dpopt, tpopt, nv * n);
-        if (pcov) both(dpcov, tpcov, nv * n * n);
-        if (need_stat) dstat = (int8_t *)c.take(nv);
-        if (nfev) dnfev = (int32_t *)c.take(nv * sizeof(int32_t));
-        if (need_cost) both(dcost, tcost, nv);
+        carve(c, A, nv, D);
         ctl = (StreamCtl *)c.take(ctl_bytes);
         if (pass == 0 && res.ensure_slab(c.off)) return kStreamRetry;  // no room for the whole volume: the ring needs three chunks
     }
+    // a span of the volume: the device buffers hold the whole volume, parameter-major rows nv voxels apart
+    auto span = [&](size_t v0, size_t c) { return Span{nv, v0, c, v0, nv}; };
+    auto granule = [&](int g) {
+        const size_t v0 = (size_t)g << gshift;
+        return span(v0, std::min(G, nv - v0));
+    };
     // pinned host: watermark values (source of the 8-byte copies), granule flags (written by the kernel) and, behind them, the
     // abort word the kernel polls while it waits for the watermark (a plain host store raises it: no stream is involved)
     const size_t pin_bytes = sizeof(unsigned long long) * (size_t)(n_in + 1) + sizeof(unsigned int) * (size_t)(n_gran + 1);
@@ -543,8 +637,7 @@ static int curvefit_streamed(const pnx_curvefit_opts *o, size_t nv, const double
     sl.spins = (unsigned int)dev_env_int("PNX_STREAM_SPINS", 400000, 1000, 1 << 20);  // ~6 us per poll: 2.4 s, at most ~6 s (the host's own
                                                                                    // watchdog below gives up after PNX_STREAM_STALL_MS)
     sl.phase = 1;
-    rc = curvefit_device(o, (int64_t)nv, bd, dy, pv ? dp0 : p0d, pv ? dlo : lod, pv ? dhi : hid, n_fpv ? dfx : fxd, dpopt, dpcov, dstat,
-                         dnfev, dcost, dev, s_main, &sl);
+    rc = curvefit_on(o, A, sh, D, nv, dev, s_main, &sl);
     if (rc == PNX_ERR_UNSUPPORTED) return kStreamRetry;  // no streamed instantiation for this combination: the ring has one
     if (rc) return rc;
     const double t_launched = now();
@@ -553,43 +646,11 @@ static int curvefit_streamed(const pnx_curvefit_opts *o, size_t nv, const double
     hipEvent_t ev_first = nullptr;
     PNX_HIP(hipEventCreateWithFlags(&ev_first, hipEventDisableTiming));
     std::atomic<int> first_recorded(0);
-    auto touch = [&](int g) {
-        const size_t v0 = (size_t)g << gshift, c = std::min(G, nv - v0);
-        for (int j = 0; j < n; ++j) touch_pages(popt + j * nv + v0, c * sizeof(T));
-        if (pcov) touch_pages(pcov + v0 * n * n, c * n * n * sizeof(T));
-        if (status) touch_pages(status + v0, c);
-        if (nfev) touch_pages(nfev + v0, c * sizeof(int32_t));
-        if (cost) touch_pages(cost + v0, c * sizeof(T));
-    };
     StreamedOps ops;
     ops.bind_device = [&]() { return hipSetDevice(device) == hipSuccess; };
     ops.upload_piece = [&](int i) -> int {
         const size_t v0 = (size_t)i * in_piece, c = std::min(in_piece, nv - v0);
-        PNX_HIP(hipMemcpyAsync(ty + v0 * n_b, y + v0 * n_b, c * n_b * sizeof(T), hipMemcpyHostToDevice, s_in));
-        if constexpr (F32) {
-            int r = cvt(ty + v0 * n_b, dy + v0 * n_b, c * n_b, s_in);
-            if (r) return r;
-        }
-        if (pv) {  // parameter-major (n_free, n_vox) start values and bounds: one row slice per parameter and array
-            const T *src[3] = {p0_pv, lo_pv, hi_pv};
-            T *tdst[3] = {tp0, tlo, thi};
-            double *ddst[3] = {dp0, dlo, dhi};
-            for (int a3 = 0; a3 < 3; ++a3)
-                for (int j = 0; j < n; ++j) {
-                    PNX_HIP(hipMemcpyAsync(tdst[a3] + j * nv + v0, src[a3] + j * nv + v0, c * sizeof(T), hipMemcpyHostToDevice, s_in));
-                    if constexpr (F32) {
-                        int r = cvt(tdst[a3] + j * nv + v0, ddst[a3] + j * nv + v0, c, s_in);
-                        if (r) return r;
-                    }
-                }
-        }
-        for (int j = 0; j < n_fpv; ++j) {  // parameter-major (n_fixed, n_vox): one row slice per fixed parameter
-            PNX_HIP(hipMemcpyAsync(tfx + j * nv + v0, fixed_pv + j * nv + v0, c * sizeof(T), hipMemcpyHostToDevice, s_in));
-            if constexpr (F32) {
-                int r = cvt(tfx + j * nv + v0, dfx + j * nv + v0, c, s_in);
-                if (r) return r;
-            }
-        }
+        if (int r = h2d(A, D, span(v0, c), s_in, true)) return r;
         wm[i] = v0 + c;
         PNX_HIP(hipMemcpyAsync(&ctl->ready, &wm[i], sizeof(unsigned long long), hipMemcpyHostToDevice, s_in));
         if (i == 0) {
@@ -606,31 +667,21 @@ static int curvefit_streamed(const pnx_curvefit_opts *o, size_t nv, const double
     ops.granule_ready = [&](int g) { return __atomic_load_n(&flags[g], __ATOMIC_ACQUIRE) != 0; };
     ops.download = [&](int g, int ot) -> int {
         hipStream_t s_out = res.s[2 + ot];
-        StreamLaunch s2;
-        s2.phase = 2;
-        const size_t v0 = (size_t)g << gshift, c = std::min(G, nv - v0);
-        if (pcov) {
-            int r = curvefit_device(o, (int64_t)c, bd, nullptr, pv ? dp0 : p0d, pv ? dlo : lod, pv ? dhi : hid, n_fpv ? dfx : fxd, nullptr, dpcov + v0 * n * n,
-                                    dstat + v0, nullptr, dcost + v0, dev, s_out, &s2);
+        const Span s = granule(g);
+        if (A.a[CF_PCOV].host) {  // the covariance epilogue of the granule
+            StreamLaunch s2;
+            s2.phase = 2;
+            int r = curvefit_device(o, (int64_t)s.c, sh.b, nullptr, per_voxel_or(A, D, CF_P0, sh.p0), per_voxel_or(A, D, CF_LO, sh.lo),
+                                    per_voxel_or(A, D, CF_HI, sh.hi), per_voxel_or(A, D, CF_FX, sh.fx), nullptr,
+                                    D.d(CF_PCOV) + s.v0 * n * n, (int8_t *)D.dev[CF_STAT] + s.v0, nullptr, D.d(CF_COST) + s.v0, dev, s_out, &s2);
             if (r) return r;
         }
-        if constexpr (F32) {
-            int r = PNX_OK;
-            for (int j = 0; j < n && !r; ++j) r = cvt(dpopt + j * nv + v0, tpopt + j * nv + v0, c, s_out);
-            if (!r && pcov) r = cvt(dpcov + v0 * n * n, tpcov + v0 * n * n, c * n * n, s_out);
-            if (!r && cost) r = cvt(dcost + v0, tcost + v0, c, s_out);
-            if (r) return r;
-        }
-        for (int j = 0; j < n; ++j)
-            PNX_HIP(hipMemcpyAsync(popt + j * nv + v0, tpopt + j * nv + v0, c * sizeof(T), hipMemcpyDeviceToHost, s_out));
-        if (pcov) PNX_HIP(hipMemcpyAsync(pcov + v0 * n * n, tpcov + v0 * n * n, c * n * n * sizeof(T), hipMemcpyDeviceToHost, s_out));
-        if (status) PNX_HIP(hipMemcpyAsync(status + v0, dstat + v0, c, hipMemcpyDeviceToHost, s_out));
-        if (nfev) PNX_HIP(hipMemcpyAsync(nfev + v0, dnfev + v0, c * sizeof(int32_t), hipMemcpyDeviceToHost, s_out));
-        if (cost) PNX_HIP(hipMemcpyAsync(cost + v0, tcost + v0, c * sizeof(T), hipMemcpyDeviceToHost, s_out));
+        if (int r = narrow(A, D, s, s_out)) return r;
+        if (int r = d2h(A, D, s, s_out)) return r;
         PNX_HIP(hipStreamSynchronize(s_out));
         return PNX_OK;
     };
-    ops.touch = touch;
+    ops.touch = [&](int g) { touch(A, granule(g)); };
     ops.abort_kernel = [&]() { __atomic_store_n(abort_word, 1u, __ATOMIC_RELEASE); };
     ops.kernel_state = [&]() -> int {
         const hipError_t e = hipStreamQuery(s_main);
@@ -690,51 +741,44 @@ static int curvefit_batch(const pnx_curvefit_opts *o, int64_t n_vox, const T *b,
     const int n = o->n_free;
     const size_t nv = (size_t)n_vox;
     const bool pv = o->per_voxel_p0_bounds != 0, fpv = o->n_fixed && o->fixed_per_voxel;
-    // the small shared host arrays (b-values, shared p0 / bounds / fixed values) as fp64
-    double bd[PNX_MAX_BVALUES], p0d[PNX_MAX_PARAMS], lod[PNX_MAX_PARAMS], hid[PNX_MAX_PARAMS], fxd[PNX_MAX_PARAMS];
-    for (int i = 0; i < o->n_b; ++i) bd[i] = (double)b[i];
+    CurvefitShared sh;  // the small shared host arrays as fp64
+    for (int i = 0; i < o->n_b; ++i) sh.b[i] = (double)b[i];
     if (!pv)
         for (int k = 0; k < n; ++k) {
-            p0d[k] = (double)p0[k];
-            lod[k] = (double)lo[k];
-            hid[k] = (double)hi[k];
+            sh.p0[k] = (double)p0[k];
+            sh.lo[k] = (double)lo[k];
+            sh.hi[k] = (double)hi[k];
         }
     if (o->n_fixed && !fpv)
-        for (int k = 0; k < o->n_fixed; ++k) fxd[k] = (double)fixed[k];
-    auto as_d = [](const T *p) { return reinterpret_cast<const double *>(p); };  // only used when T is double
+        for (int k = 0; k < o->n_fixed; ++k) sh.fx[k] = (double)fixed[k];
+    ArrayTable A;  // CF_* order; per-voxel p0 / bounds / fixed maps and popt are parameter-major
+    A.add(y, sizeof(T), o->n_b, false, F32);
+    A.add(pv ? p0 : nullptr, sizeof(T), n, false, F32).pmajor = true;
+    A.add(pv ? lo : nullptr, sizeof(T), n, false, F32).pmajor = true;
+    A.add(pv ? hi : nullptr, sizeof(T), n, false, F32).pmajor = true;
+    A.add(fpv ? fixed : nullptr, sizeof(T), o->n_fixed, false, F32).pmajor = true;
+    A.add(popt, sizeof(T), n, true, F32).pmajor = true;
+    A.add(pcov, sizeof(T), (size_t)n * n, true, F32);
+    A.add(status, 1, 1, true).always = pcov != nullptr;  // the covariance epilogue reads status and cost
+    A.add(nfev, sizeof(int32_t), 1, true);
+    A.add(cost, sizeof(T), 1, true, F32).always = pcov != nullptr;
 
     if (mem == PNX_MEM_DEVICE) {
         if (pcov && (!status || !cost))
             return set_error(PNX_ERR_INVALID, "device mode: pcov needs the status and cost outputs too (the covariance "
                                               "epilogue kernel reads them)");
         hipStream_t st = (hipStream_t)stream;
-        if constexpr (!F32) {
-            return curvefit_device(o, n_vox, bd, as_d(y), pv ? as_d(p0) : p0d, pv ? as_d(lo) : lod, pv ? as_d(hi) : hid,
-                                   fpv ? as_d(fixed) : fxd, (double *)popt, (double *)pcov, status, nfev, (double *)cost, dev, st, nullptr,
-                                   o->queue_order);
-        } else {
-            AsyncBuf y64, p64, l64, h64, f64, o64, c64, k64;
-            if ((rc = y64.alloc(nv * o->n_b * 8, st)) || (rc = cvt(y, (double *)y64.p, nv * o->n_b, st))) return rc;
-            if (pv) {
-                if ((rc = p64.alloc(nv * n * 8, st)) || (rc = l64.alloc(nv * n * 8, st)) || (rc = h64.alloc(nv * n * 8, st))) return rc;
-                if ((rc = cvt(p0, (double *)p64.p, nv * n, st)) || (rc = cvt(lo, (double *)l64.p, nv * n, st)) ||
-                    (rc = cvt(hi, (double *)h64.p, nv * n, st)))
-                    return rc;
-            }
-            if (fpv && ((rc = f64.alloc(nv * o->n_fixed * 8, st)) || (rc = cvt(fixed, (double *)f64.p, nv * o->n_fixed, st)))) return rc;
-            if ((rc = o64.alloc(nv * n * 8, st))) return rc;
-            if (pcov && (rc = c64.alloc(nv * n * n * 8, st))) return rc;
-            if ((cost || pcov) && (rc = k64.alloc(nv * 8, st))) return rc;
-            rc = curvefit_device(o, n_vox, bd, (const double *)y64.p, pv ? (const double *)p64.p : p0d,
-                                 pv ? (const double *)l64.p : lod, pv ? (const double *)h64.p : hid,
-                                 fpv ? (const double *)f64.p : fxd, (double *)o64.p, pcov ? (double *)c64.p : nullptr, status,
-                                 nfev, (double *)k64.p, dev, st, nullptr, o->queue_order);
-            if (rc) return rc;
-            if ((rc = cvt((const double *)o64.p, popt, nv * n, st))) return rc;
-            if (pcov && (rc = cvt((const double *)c64.p, pcov, nv * n * n, st))) return rc;
-            if (cost && (rc = cvt((const double *)k64.p, cost, nv, st))) return rc;
-            return PNX_OK;  // AsyncBuf destructors enqueue the frees behind the conversions
+        AsyncBuf scratch;  // float32: fp64 copies of the widened arrays, stream-ordered
+        DevSet D;
+        const Span all{nv, 0, nv, 0, nv};
+        for (int pass = 0; pass < 2; ++pass) {
+            Carver cv;
+            cv.base = (char *)scratch.p;
+            carve(cv, A, nv, D, Carve::CallerDevice);
+            if (pass == 0 && cv.off && (rc = scratch.alloc(cv.off, st))) return rc;
         }
+        if ((rc = widen(A, D, all, st)) || (rc = curvefit_on(o, A, sh, D, nv, dev, st, nullptr, o->queue_order))) return rc;
+        return narrow(A, D, all, st);  // the AsyncBuf destructor enqueues the free behind the conversions
     }
 
     HostCallGuard hg;  // this call is in flight from here on (helper-thread budget)
@@ -767,14 +811,14 @@ static int curvefit_batch(const pnx_curvefit_opts *o, int64_t n_vox, const T *b,
         }
         if (!cooling && dev_env_int("PNX_HOST_STREAM", 1, 0, 1) && !(pv && o->n_fixed) && !tight && nv > ((size_t)1 << gshift) &&
             nv < ((size_t)1 << 31) && nv * per_vox <= max_bytes) {
-            rc = curvefit_streamed<T>(o, nv, bd, y, p0d, lod, hid, pv ? p0 : nullptr, pv ? lo : nullptr, pv ? hi : nullptr, fxd,
-                                      fpv ? fixed : nullptr, popt, pcov, status, nfev, cost, gshift, dev, device, (hipStream_t)stream, hg);
+            rc = curvefit_streamed(o, A, sh, nv, gshift, dev, device, (hipStream_t)stream, hg);
             if (rc != kStreamRetry) return rc;
             static std::atomic<bool> warned(false);
             if (dev_getenv("PNX_HOST_TRACE") || !warned.exchange(true))
                 fprintf(stderr, "[pnx stream] the streamed launch could not be used (no room for the staging slab, or its upload did not "
                                 "start within PNX_STREAM_STALL_MS); running the call through the chunk ring, and after a stall the next "
-                                "PNX_STREAM_COOLDOWN calls of this device too. PNX_HOST_STREAM=0 skips the attempt.\n");
+                                "PNX_STREAM_COOLDOWN calls of this device too. With PNX_ENABLE_TEST_HOOKS=1, PNX_HOST_STREAM=0 skips "
+                                "the attempt.\n");
         }
     }
 
@@ -782,121 +826,27 @@ static int curvefit_batch(const pnx_curvefit_opts *o, int64_t n_vox, const T *b,
     // float32 transfers are half as long per voxel: a larger chunk (fewer drain tails of the persistent kernel) at the same
     // exposed transfer latency -- C3 float32: 86.3 M voxels/s at 768 Ki, 89.8 M at 1 Mi, 82.5 M at 2 Mi (profiles/host_chunk_sweep_f32.py)
     const size_t chunk = (size_t)dev_env_int("PNX_HOST_CHUNK", F32 ? 1 << 20 : 3 << 18, 1024, 1 << 26);
-    // chunk boundaries: with three or more full chunks the first and the last piece are a quarter chunk -- the first kernel
-    // starts after a quarter of an upload, and the serial tail (last kernel, last download) is a quarter as long
-    std::vector<size_t> bounds;
-    {
-        const size_t ramp = dev_env_int("PNX_HOST_RAMP", 1, 0, 1) && nv >= 3 * chunk ? chunk / 4 : 0;
-        size_t v = 0;
-        bounds.push_back(0);
-        if (ramp) bounds.push_back(v = ramp);
-        const size_t body_end = nv - ramp;
-        while (v < body_end) bounds.push_back(v = (body_end - v) < chunk ? body_end : v + chunk);
-        if (ramp) bounds.push_back(nv);
-    }
+    const std::vector<size_t> bounds = chunk_bounds(nv, chunk, true);
     const int n_chunks = (int)bounds.size() - 1;
     const int n_slots = n_chunks < 3 ? n_chunks : dev_env_int("PNX_HOST_SLOTS", 3, 2, 8);
-    const size_t cap = nv < chunk ? nv : chunk;
-    const bool need_stat = status || pcov, need_cost = cost || pcov;
     struct Slot {
         DevBuf slab;
-        // fp64 working set of the kernels ...
-        double *y = nullptr, *p0 = nullptr, *lo = nullptr, *hi = nullptr, *fx = nullptr, *popt = nullptr, *pcov = nullptr,
-               *cost = nullptr;
-        // ... and the T-typed transfer buffers (the same memory when T is double)
-        T *ty = nullptr, *tp0 = nullptr, *tlo = nullptr, *thi = nullptr, *tfx = nullptr, *tpopt = nullptr, *tpcov = nullptr,
-          *tcost = nullptr;
-        int8_t *stat = nullptr;
-        int32_t *nfev = nullptr;
+        DevSet D;
     };
     std::vector<Slot> slots(n_slots);
-    for (int w = 0; w < n_slots; ++w) {
-        Slot &S = slots[w];
-        for (int pass = 0; pass < 2; ++pass) {  // pass 0 sizes the slab, pass 1 carves it
-            Carver c;
-            c.base = (char *)S.slab.p;
-            auto both = [&](double *&d64, T *&t, size_t count) {
-                d64 = (double *)c.take(count * sizeof(double));
-                t = F32 ? (T *)c.take(count * sizeof(T)) : (T *)d64;
-            };
-            both(S.y, S.ty, cap * o->n_b);
-            if (pv) {
-                both(S.p0, S.tp0, cap * n);
-                both(S.lo, S.tlo, cap * n);
-                both(S.hi, S.thi, cap * n);
-            }
-            if (fpv) both(S.fx, S.tfx, cap * o->n_fixed);
-            both(S.popt, S.tpopt, cap * n);
-            if (pcov) both(S.pcov, S.tpcov, cap * n * n);
-            if (need_stat) S.stat = (int8_t *)c.take(cap);
-            if (nfev) S.nfev = (int32_t *)c.take(cap * sizeof(int32_t));
-            if (need_cost) both(S.cost, S.tcost, cap);
-            if (pass == 0 && (rc = S.slab.alloc(c.off))) return rc;
-        }
-    }
-    auto span = [&](int k, size_t &v0, size_t &c) {
-        v0 = bounds[k];
-        c = bounds[k + 1] - v0;
-    };
+    for (auto &S : slots)
+        if ((rc = alloc_carved(S.slab, A, nv < chunk ? nv : chunk, S.D))) return rc;
     PipeOps ops;
-    ops.h2d = [&](int k, int slot, hipStream_t st) -> int {
-        Slot &S = slots[slot];
-        size_t v0, c;
-        span(k, v0, c);
-        PNX_HIP(hipMemcpyAsync(S.ty, y + v0 * o->n_b, c * o->n_b * sizeof(T), hipMemcpyHostToDevice, st));
-        // parameter-major (k, n_vox) arrays: one row slice per parameter, device stride = c
-        if (pv)
-            for (int j = 0; j < n; ++j) {
-                PNX_HIP(hipMemcpyAsync(S.tp0 + j * c, p0 + j * nv + v0, c * sizeof(T), hipMemcpyHostToDevice, st));
-                PNX_HIP(hipMemcpyAsync(S.tlo + j * c, lo + j * nv + v0, c * sizeof(T), hipMemcpyHostToDevice, st));
-                PNX_HIP(hipMemcpyAsync(S.thi + j * c, hi + j * nv + v0, c * sizeof(T), hipMemcpyHostToDevice, st));
-            }
-        if (fpv)
-            for (int j = 0; j < o->n_fixed; ++j)
-                PNX_HIP(hipMemcpyAsync(S.tfx + j * c, fixed + j * nv + v0, c * sizeof(T), hipMemcpyHostToDevice, st));
-        return PNX_OK;
-    };
+    ops.h2d = [&](int k, int slot, hipStream_t st) { return h2d(A, slots[slot].D, ring_span(bounds, k), st); };
     ops.launch = [&](int k, int slot, hipStream_t st) -> int {
-        Slot &S = slots[slot];
-        size_t v0, c;
-        span(k, v0, c);
-        int r = PNX_OK;
-        if constexpr (F32) {
-            if ((r = cvt(S.ty, S.y, c * o->n_b, st))) return r;
-            if (pv && ((r = cvt(S.tp0, S.p0, c * n, st)) || (r = cvt(S.tlo, S.lo, c * n, st)) || (r = cvt(S.thi, S.hi, c * n, st)))) return r;
-            if (fpv && (r = cvt(S.tfx, S.fx, c * o->n_fixed, st))) return r;
-        }
-        r = curvefit_device(o, (int64_t)c, bd, S.y, pv ? S.p0 : p0d, pv ? S.lo : lod, pv ? S.hi : hid, fpv ? S.fx : fxd, S.popt,
-                            pcov ? S.pcov : nullptr, S.stat, S.nfev, S.cost, dev, st);
-        if (r) return r;
-        if constexpr (F32) {
-            if ((r = cvt(S.popt, S.tpopt, c * n, st))) return r;
-            if (pcov && (r = cvt(S.pcov, S.tpcov, c * n * n, st))) return r;
-            if (cost && (r = cvt(S.cost, S.tcost, c, st))) return r;
-        }
-        return PNX_OK;
+        const DevSet &D = slots[slot].D;
+        const Span s = ring_span(bounds, k);
+        int r;
+        if ((r = widen(A, D, s, st)) || (r = curvefit_on(o, A, sh, D, s.c, dev, st))) return r;
+        return narrow(A, D, s, st);
     };
-    ops.touch = [&](int k) {
-        size_t v0, c;
-        span(k, v0, c);
-        for (int j = 0; j < n; ++j) touch_pages(popt + j * nv + v0, c * sizeof(T));
-        if (pcov) touch_pages(pcov + v0 * n * n, c * n * n * sizeof(T));
-        if (status) touch_pages(status + v0, c);
-        if (nfev) touch_pages(nfev + v0, c * sizeof(int32_t));
-        if (cost) touch_pages(cost + v0, c * sizeof(T));
-    };
-    ops.d2h = [&](int k, int slot, hipStream_t st) -> int {
-        Slot &S = slots[slot];
-        size_t v0, c;
-        span(k, v0, c);
-        for (int j = 0; j < n; ++j)
-            PNX_HIP(hipMemcpyAsync(popt + j * nv + v0, S.tpopt + j * c, c * sizeof(T), hipMemcpyDeviceToHost, st));
-        if (pcov) PNX_HIP(hipMemcpyAsync(pcov + v0 * n * n, S.tpcov, c * n * n * sizeof(T), hipMemcpyDeviceToHost, st));
-        if (status) PNX_HIP(hipMemcpyAsync(status + v0, S.stat, c, hipMemcpyDeviceToHost, st));
-        if (nfev) PNX_HIP(hipMemcpyAsync(nfev + v0, S.nfev, c * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-        if (cost) PNX_HIP(hipMemcpyAsync(cost + v0, S.tcost, c * sizeof(T), hipMemcpyDeviceToHost, st));
-        return PNX_OK;
-    };
+    ops.touch = [&](int k) { touch(A, ring_span(bounds, k)); };
+    ops.d2h = [&](int k, int slot, hipStream_t st) { return d2h(A, slots[slot].D, ring_span(bounds, k), st); };
     return run_pipeline(n_chunks, n_slots, dev_env_int("PNX_HOST_KSTREAMS", 2, 1, 4), hg.touchers(), device, (hipStream_t)stream, ops);
 }
 
@@ -967,6 +917,149 @@ int pnx_nnls_plan_destroy(pnx_nnls_plan *plan) {
 
 }  // extern "C"
 
+// the arrays of an NNLS call, in table order: the signal, the spectra, the solver's per-voxel outputs, the peak tables
+enum { NN_Y, NN_SPEC, NN_RNORM, NN_STAT, NN_ITERS, NN_NPEAKS, NN_D, NN_F, NN_DC, NN_FC };
+struct NnlsHostCall {
+    ArrayTable A;          // NN_* order; the spectra are downloaded (solve) or only analysed on the device (solve_peaks)
+    size_t chunk = 0;      // voxels per chunk of the ring
+    bool ramp = false;     // quarter-chunk ramp at both ends (chunk_bounds)
+    bool overlap = false;  // the first deferred pass runs behind the last chunk's solve, beside its download (else after the ring)
+    std::function<int(size_t n, const DevSet &D, hipStream_t s)> post;  // behind every solve, on its stream (may be empty)
+};
+
+// NNLS from host arrays: the chunk ring of the curve fit with ONE kernel stream -- the plan's device scratch (ATY chunk, M
+// overflow, queue) serves one solve at a time, and in-order launches on one stream guarantee that.  The (n_vox, n_bins)
+// coefficient array is 8.4 GB for the C4 volume: its D2H and first-touch faults hide behind the solves of the following chunks.
+// The caller holds the plan's mutex.
+static int nnls_host(NnlsPlanData &P, size_t nv, int max_iter, const NnlsHostCall &C, hipStream_t st) {
+    const ArrayTable &A = C.A;
+    const std::vector<size_t> bounds = chunk_bounds(nv, C.chunk, C.ramp);
+    const int n_chunks = (int)bounds.size() - 1;
+    const int n_slots = n_chunks < 3 ? n_chunks : 3;
+    int rc;
+    struct Slot {
+        DevBuf slab;
+        DevSet D;
+    };
+    std::vector<Slot> slots((size_t)n_slots);
+    for (auto &S : slots)
+        if ((rc = alloc_carved(S.slab, A, nv < C.chunk ? nv : C.chunk, S.D))) return rc;
+    // Block-kernel plans hand a few voxels per chunk to the general kernel, and that pass costs ~8 ms per chunk whatever their
+    // number (they are the longest solves there are): with several chunks the hand-over is deferred -- the chunks only
+    // collect the voxels' indices and signal rows, ONE pass at the end of the call solves them, and their rows are patched
+    // into the caller's arrays (C4 from numpy arrays: seven passes -> one).
+    const int defer_cap = dev_env_int("PNX_NNLS_DEFER_CAP", 16384, 0, 1 << 22);
+    const bool defer = P.blk && n_chunks >= 2 && defer_cap > 0 && nv < ((size_t)1 << 31);
+    const size_t dcap = (size_t)defer_cap;
+    DevBuf dslab;
+    NnlsDefer dctx{};
+    DevSet side;  // results of the deferred pass, sized for the side buffer's capacity
+    int32_t *d_iota = nullptr;
+    struct SideStream {  // where the deferred pass runs
+        hipStream_t s = nullptr;
+        hipEvent_t e = nullptr;
+        ~SideStream() {
+            if (s) (void)hipStreamDestroy(s);
+            if (e) (void)hipEventDestroy(e);
+        }
+    } ss;
+    if (defer) {
+        for (int pass = 0; pass < 2; ++pass) {
+            Carver c;
+            c.base = (char *)dslab.p;
+            dctx.counters = (int32_t *)c.take(2 * sizeof(int32_t));
+            dctx.bail = (int32_t *)c.take(nv * sizeof(int32_t));
+            dctx.y_side = (double *)c.take(dcap * P.n_meas * sizeof(double));
+            carve(c, A, dcap, side, Carve::Results);
+            d_iota = (int32_t *)c.take(dcap * sizeof(int32_t));
+            if (pass == 0 && (rc = dslab.alloc(c.off))) return rc;
+        }
+        dctx.cap = defer_cap;
+        std::vector<int32_t> idx(dcap);
+        for (size_t i = 0; i < dcap; ++i) idx[i] = (int32_t)i;
+        PNX_HIP(hipMemcpy(d_iota, idx.data(), idx.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+        // a kernel stream (lowest priority): a copy must never sit in a hardware queue behind a kernel (the download of the
+        // last chunk would wait for this pass)
+        if (!HipBackend::stream_create(&ss.s, true) || !HipBackend::event_create(&ss.e))
+            return set_error(PNX_ERR_HIP, "deferred hand-over: stream/event setup failed");
+        PNX_HIP(hipMemset(dctx.counters, 0, 2 * sizeof(int32_t)));
+    }
+    // the four-slot block kernel on the first n handed-over voxels (the list is 0 .. n - 1 and the count on the device is >= n:
+    // the kernel stops at the n it is given), rows in the side buffer, results in `side`
+    auto redo = [&](size_t n) {
+        return nnls_blk_redo_device(&P, (int64_t)n, dctx.y_side, max_iter, side.d(NN_SPEC), side.d(NN_RNORM), (int8_t *)side.dev[NN_STAT],
+                                    (int32_t *)side.dev[NN_ITERS], d_iota, dctx.counters, ss.s);
+    };
+    PipeOps ops;
+    ops.h2d = [&](int k, int slot, hipStream_t s) { return h2d(A, slots[(size_t)slot].D, ring_span(bounds, k), s); };
+    ops.launch = [&](int k, int slot, hipStream_t s) -> int {
+        const DevSet &D = slots[(size_t)slot].D;
+        const Span sp = ring_span(bounds, k);
+        int r = widen(A, D, sp, s);
+        if (r) return r;
+        int8_t *stat = (int8_t *)D.dev[NN_STAT];
+        int32_t *iters = (int32_t *)D.dev[NN_ITERS];
+        if (defer) {
+            NnlsDefer d = dctx;
+            d.base = (int64_t)sp.v0;
+            r = nnls_blk_solve_device(&P, (int64_t)sp.c, D.d(NN_Y), max_iter, D.d(NN_SPEC), D.d(NN_RNORM), stat, iters, s, &d);
+            if (!r && C.overlap && k == n_chunks - 1) {
+                // every chunk has appended its handed-over voxels: ONE pass over the side buffer, on a stream of its own behind
+                // this chunk's solve, while the chunk's spectra go home (8 ms of download, 9 ms of pass) -- launched before the
+                // host knows how many voxels it holds, so on the buffer's whole capacity
+                PNX_HIP(hipEventRecord(ss.e, s));
+                PNX_HIP(hipStreamWaitEvent(ss.s, ss.e, 0));
+                r = redo(dcap);
+            }
+        } else {
+            r = nnls_solve_device(&P, (int64_t)sp.c, D.d(NN_Y), max_iter, D.d(NN_SPEC), D.d(NN_RNORM), stat, iters, s);
+        }
+        if (!r && C.post) r = C.post(sp.c, D, s);
+        return r ? r : narrow(A, D, sp, s);
+    };
+    ops.touch = [&](int k) { touch(A, ring_span(bounds, k)); };
+    ops.d2h = [&](int k, int slot, hipStream_t s) { return d2h(A, slots[(size_t)slot].D, ring_span(bounds, k), s); };
+    HostCallGuard hg;
+    rc = run_pipeline(n_chunks, n_slots, 1, hg.touchers(), P.device, st, ops);
+    if (rc || !defer) return rc;
+
+    PNX_HIP(hipStreamSynchronize(ss.s));  // the pass behind the last chunk's solve
+    int32_t cnt[2] = {0, 0};
+    PNX_HIP(hipMemcpy(cnt, dctx.counters, sizeof(cnt), hipMemcpyDeviceToHost));
+    if (cnt[0] == 0) return PNX_OK;
+    if (cnt[0] < 0 || (size_t)cnt[0] > nv) return set_error(PNX_ERR_HIP, "deferred hand-over: %d voxels counted in a call of %zu", cnt[0], nv);
+    const size_t n = (size_t)cnt[0], batch = n < dcap ? n : dcap;
+    std::vector<int32_t> where(n);
+    PNX_HIP(hipMemcpy(where.data(), dctx.bail, n * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if ((rc = check_rows(where.data(), n, nv))) return rc;
+    // More handed-over voxels than the side buffer holds (stronger regularisers than the reference's: a few per cent of the
+    // voxels): the first pass has solved the first defer_cap of them (the side buffer holds their signal rows, gathered chunk
+    // by chunk on the device); the others follow in batches of defer_cap, their signal rows gathered from the caller's array.
+    std::vector<std::vector<char>> res((size_t)A.n);
+    const void *rows[ArrayTable::kMax] = {};
+    for (int k = 0; k < A.n; ++k)
+        if (A.a[k].out && A.a[k].host) {
+            res[(size_t)k].resize(batch * A.a[k].w * (A.a[k].widen ? sizeof(double) : A.a[k].esize));
+            rows[k] = res[(size_t)k].data();
+        }
+    std::vector<double> y_rows;
+    for (size_t b0 = 0; b0 < n; b0 += batch) {
+        const size_t nb = (n - b0) < batch ? (n - b0) : batch;
+        if (b0 > 0) {
+            y_rows.resize(nb * (size_t)P.n_meas);
+            gather_rows(A.a[NN_Y], where.data() + b0, nb, y_rows.data());
+            PNX_HIP(hipMemcpy(dctx.y_side, y_rows.data(), y_rows.size() * sizeof(double), hipMemcpyHostToDevice));
+        }
+        if ((b0 > 0 || !C.overlap) && (rc = redo(nb))) return rc;
+        if (C.post && (rc = C.post(nb, side, ss.s))) return rc;
+        PNX_HIP(hipStreamSynchronize(ss.s));
+        for (int k = 0; k < A.n; ++k)
+            if (rows[k]) PNX_HIP(hipMemcpy((void *)rows[k], side.dev[k], nb * A.a[k].w * (A.a[k].widen ? sizeof(double) : A.a[k].esize), hipMemcpyDeviceToHost));
+        if ((rc = patch_rows(A, rows, where.data() + b0, nb, nv))) return rc;
+    }
+    return PNX_OK;
+}
+
 // T = double: fp64 entry point.  T = float: fp32 storage of the signal, the coefficients and rnorm; fp64 arithmetic.
 template <typename T>
 static int nnls_solve(pnx_nnls_plan *plan, int64_t n_vox, const T *y, int max_iter, T *coeff, T *rnorm, int8_t *status,
@@ -981,239 +1074,44 @@ static int nnls_solve(pnx_nnls_plan *plan, int64_t n_vox, const T *y, int max_it
     hipStream_t st = (hipStream_t)stream;
     if (max_iter <= 0) max_iter = 3 * P.n_bins;  // scipy/optimize/_nnls.py:93-94
     const size_t nv = (size_t)n_vox;
-    int rc;
+    NnlsHostCall C;
+    C.A.add(y, sizeof(T), P.n_meas, false, F32);
+    C.A.add(coeff, sizeof(T), P.n_bins, true, F32);
+    C.A.add(rnorm, sizeof(T), 1, true, F32);
+    C.A.add(status, 1, 1, true).always = true;
+    C.A.add(iters, sizeof(int32_t), 1, true).always = true;
     if (mem == PNX_MEM_DEVICE) {
-        if constexpr (!F32) {
-            return nnls_solve_device(&P, n_vox, (const double *)y, max_iter, (double *)coeff, (double *)rnorm, status, iters, st);
-        } else {
-            // converted in pieces of the kernel's own chunk so that the fp64 scratch stays at 2.4 GB
-            const size_t piece = (size_t)kAtyChunk < nv ? (size_t)kAtyChunk : nv;
-            AsyncBuf y64, c64, r64;
-            if ((rc = y64.alloc(piece * P.n_meas * 8, st)) || (rc = c64.alloc(piece * P.n_bins * 8, st)) || (rc = r64.alloc(piece * 8, st)))
+        // float32: converted in pieces of the kernel's own chunk so that the fp64 scratch stays at 2.4 GB
+        const size_t piece = F32 && (size_t)kAtyChunk < nv ? (size_t)kAtyChunk : nv;
+        AsyncBuf scratch;
+        DevSet D;
+        Carver sizing;
+        carve(sizing, C.A, piece, D, Carve::CallerDevice);
+        int rc;
+        if (sizing.off && (rc = scratch.alloc(sizing.off, st))) return rc;
+        for (size_t off = 0; off < nv; off += piece) {
+            const size_t c = (nv - off) < piece ? (nv - off) : piece;
+            Carver cv;
+            cv.base = (char *)scratch.p;
+            carve(cv, C.A, piece, D, Carve::CallerDevice, off);
+            const Span s{nv, off, c, 0, c};
+            if ((rc = widen(C.A, D, s, st)) ||
+                (rc = nnls_solve_device(&P, (int64_t)c, D.d(NN_Y), max_iter, D.d(NN_SPEC), D.d(NN_RNORM), (int8_t *)D.dev[NN_STAT],
+                                        (int32_t *)D.dev[NN_ITERS], st)) ||
+                (rc = narrow(C.A, D, s, st)))
                 return rc;
-            for (size_t off = 0; off < nv; off += piece) {
-                const size_t c = (nv - off) < piece ? (nv - off) : piece;
-                if ((rc = cvt(y + off * P.n_meas, (double *)y64.p, c * P.n_meas, st))) return rc;
-                rc = nnls_solve_device(&P, (int64_t)c, (const double *)y64.p, max_iter, (double *)c64.p, (double *)r64.p,
-                                       status ? status + off : nullptr, iters ? iters + off : nullptr, st);
-                if (rc) return rc;
-                if ((rc = cvt((const double *)c64.p, coeff + off * P.n_bins, c * P.n_bins, st)) ||
-                    (rc = cvt((const double *)r64.p, rnorm + off, c, st)))
-                    return rc;
-            }
-            return PNX_OK;
         }
+        return PNX_OK;
     }
-    // host staging: the same chunk ring as the curve fit, with ONE kernel stream -- the plan's device scratch (ATY
-    // chunk, M overflow, queue) serves one solve at a time, and in-order launches on one stream guarantee that.
-    // The (n_vox, n_bins) coefficient array is 8.4 GB for the C4 volume: its D2H and first-touch faults hide behind
-    // the solves of the following chunks.
     std::lock_guard<std::mutex> plan_lock(plan->mu);
     // every chunk is one launch of the solver plus (block kernel) one hand-over pass of ~8 ms: C4 from numpy arrays takes
     // 759 / 712 / 682 / 698 ms with chunks of 256 Ki / 512 Ki / 768 Ki / 1 Mi voxels (profiles/nnls_host_chunk.py) -- beyond
-    // 768 Ki the last chunk's download (2 KB per voxel) is what grows
-    const size_t chunk = (size_t)dev_env_int("PNX_NNLS_HOST_CHUNK", 3 << 18, 1024, 1 << 22);
-    // chunk boundaries.  Block-kernel plans with three or more chunks (their hand-over pass is deferred, see below, so a
-    // chunk more costs ~1.5 ms, not 8): the first and the last piece are a quarter chunk -- the first launch starts after a
-    // quarter of an upload, and the download left exposed at the end is 0.4 GB instead of 1.6 (2 KB per voxel).
-    std::vector<size_t> bounds;
-    {
-        const size_t ramp = (P.blk && dev_env_int("PNX_HOST_RAMP", 1, 0, 1) && nv >= 3 * chunk) ? chunk / 4 : 0;
-        size_t v = 0;
-        bounds.push_back(0);
-        if (ramp) bounds.push_back(v = ramp);
-        const size_t body_end = nv - ramp;
-        while (v < body_end) bounds.push_back(v = (body_end - v) < chunk ? body_end : v + chunk);
-        if (ramp) bounds.push_back(nv);
-    }
-    const int n_chunks = (int)bounds.size() - 1;
-    const int n_slots = n_chunks < 3 ? n_chunks : 3;
-    const size_t cap = nv < chunk ? nv : chunk;
-    struct Slot {
-        DevBuf slab;
-        double *y = nullptr, *c = nullptr, *r = nullptr;  // fp64 working set
-        T *ty = nullptr, *tc = nullptr, *tr = nullptr;    // transfer buffers (same memory when T is double)
-        int8_t *s = nullptr;
-        int32_t *i = nullptr;
-    };
-    std::vector<Slot> slots(n_slots);
-    for (int w = 0; w < n_slots; ++w) {
-        Slot &S = slots[w];
-        for (int pass = 0; pass < 2; ++pass) {
-            Carver c;
-            c.base = (char *)S.slab.p;
-            auto both = [&](double *&d64, T *&t, size_t count) {
-                d64 = (double *)c.take(count * sizeof(double));
-                t = F32 ? (T *)c.take(count * sizeof(T)) : (T *)d64;
-            };
-            both(S.y, S.ty, cap * P.n_meas);
-            both(S.c, S.tc, cap * P.n_bins);
-            both(S.r, S.tr, cap);
-            S.s = (int8_t *)c.take(cap);
-            S.i = (int32_t *)c.take(cap * sizeof(int32_t));
-            if (pass == 0 && (rc = S.slab.alloc(c.off))) return rc;
-        }
-    }
-    // Block-kernel plans hand a few voxels per chunk to the general kernel, and that pass costs ~8 ms per chunk whatever their
-    // number (they are the longest solves there are): with several chunks the hand-over is deferred -- the chunks only
-    // collect the voxels' indices and signal rows, ONE pass at the end of the call solves them, and their rows are patched
-    // into the caller's arrays (C4 from numpy arrays: seven passes -> one).
-    const int defer_cap = dev_env_int("PNX_NNLS_DEFER_CAP", 16384, 0, 1 << 22);
-    const bool can_defer = P.blk && n_chunks >= 2 && defer_cap > 0 && nv < ((size_t)1 << 31);
-    DevBuf dslab;
-    NnlsDefer dctx{};
-    double *d_sc = nullptr, *d_sr = nullptr;
-    int8_t *d_ss = nullptr;
-    int32_t *d_si = nullptr, *d_iota = nullptr;
-    struct SideStream {  // the deferred pass runs beside the last chunk's download
-        hipStream_t s = nullptr;
-        hipEvent_t e = nullptr;
-        ~SideStream() {
-            if (s) (void)hipStreamDestroy(s);
-            if (e) (void)hipEventDestroy(e);
-        }
-    } side;
-    if (can_defer) {
-        for (int pass = 0; pass < 2; ++pass) {
-            Carver c;
-            c.base = (char *)dslab.p;
-            dctx.counters = (int32_t *)c.take(2 * sizeof(int32_t));
-            dctx.bail = (int32_t *)c.take(nv * sizeof(int32_t));
-            dctx.y_side = (double *)c.take((size_t)defer_cap * P.n_meas * sizeof(double));
-            // results of the deferred pass, sized for the side buffer's capacity: the pass is launched behind the last chunk's
-            // solve -- before the host knows how many voxels it holds -- so that it overlaps that chunk's download
-            d_sc = (double *)c.take((size_t)defer_cap * P.n_bins * sizeof(double));
-            d_sr = (double *)c.take((size_t)defer_cap * sizeof(double));
-            d_ss = (int8_t *)c.take((size_t)defer_cap);
-            d_si = (int32_t *)c.take((size_t)defer_cap * sizeof(int32_t));
-            d_iota = (int32_t *)c.take((size_t)defer_cap * sizeof(int32_t));
-            if (pass == 0 && (rc = dslab.alloc(c.off))) return rc;
-        }
-        dctx.cap = defer_cap;
-        std::vector<int32_t> idx((size_t)defer_cap);
-        for (int i = 0; i < defer_cap; ++i) idx[(size_t)i] = i;
-        PNX_HIP(hipMemcpy(d_iota, idx.data(), idx.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-        {   // lowest priority, like every kernel stream of the host paths: hardware queues are pooled per priority, and a copy
-            // must never sit in a queue behind a kernel (the download of the last chunk would wait for this pass)
-            int prio_least = 0, prio_greatest = 0;
-            PNX_HIP(hipDeviceGetStreamPriorityRange(&prio_least, &prio_greatest));
-            PNX_HIP(hipStreamCreateWithPriority(&side.s, hipStreamNonBlocking, prio_least));
-        }
-        PNX_HIP(hipEventCreateWithFlags(&side.e, hipEventDisableTiming));
-    }
-    const bool overlap_pass = dev_env_int("PNX_NNLS_DEFER_OVERLAP", 1, 0, 1) != 0;
-    auto run = [&](const bool defer) -> int {
-        if (defer) PNX_HIP(hipMemset(dctx.counters, 0, 2 * sizeof(int32_t)));
-        auto span = [&](int k, size_t &off, size_t &c) {
-            off = bounds[(size_t)k];
-            c = bounds[(size_t)k + 1] - off;
-        };
-        PipeOps ops;
-        ops.h2d = [&](int k, int slot, hipStream_t s) -> int {
-            size_t off, c;
-            span(k, off, c);
-            PNX_HIP(hipMemcpyAsync(slots[slot].ty, y + off * P.n_meas, c * P.n_meas * sizeof(T), hipMemcpyHostToDevice, s));
-            return PNX_OK;
-        };
-        ops.launch = [&](int k, int slot, hipStream_t s) -> int {
-            Slot &S = slots[slot];
-            size_t off, c;
-            span(k, off, c);
-            int r = PNX_OK;
-            if constexpr (F32)
-                if ((r = cvt(S.ty, S.y, c * P.n_meas, s))) return r;
-            if (defer) {
-                NnlsDefer d = dctx;
-                d.base = (int64_t)off;
-                r = nnls_blk_solve_device(&P, (int64_t)c, S.y, max_iter, S.c, S.r, S.s, S.i, s, &d);
-                if (!r && k == n_chunks - 1 && overlap_pass) {
-                    // every chunk has appended its handed-over voxels: ONE pass of the general kernel over the side buffer, on a
-                    // stream of its own behind this chunk's solve, while the chunk's spectra go home (8 ms of download, 9 ms of pass)
-                    PNX_HIP(hipEventRecord(side.e, s));
-                    PNX_HIP(hipStreamWaitEvent(side.s, side.e, 0));
-                    r = nnls_blk_redo_device(&P, defer_cap, dctx.y_side, max_iter, d_sc, d_sr, d_ss, d_si, d_iota, dctx.counters, side.s);
-                }
-            } else {
-                r = nnls_solve_device(&P, (int64_t)c, S.y, max_iter, S.c, S.r, S.s, S.i, s);
-            }
-            if (r) return r;
-            if constexpr (F32)
-                if ((r = cvt(S.c, S.tc, c * P.n_bins, s)) || (r = cvt(S.r, S.tr, c, s))) return r;
-            return PNX_OK;
-        };
-        ops.touch = [&](int k) {
-            size_t off, c;
-            span(k, off, c);
-            touch_pages(coeff + off * P.n_bins, c * P.n_bins * sizeof(T));
-            touch_pages(rnorm + off, c * sizeof(T));
-            if (status) touch_pages(status + off, c);
-            if (iters) touch_pages(iters + off, c * sizeof(int32_t));
-        };
-        ops.d2h = [&](int k, int slot, hipStream_t s) -> int {
-            Slot &S = slots[slot];
-            size_t off, c;
-            span(k, off, c);
-            PNX_HIP(hipMemcpyAsync(coeff + off * P.n_bins, S.tc, c * P.n_bins * sizeof(T), hipMemcpyDeviceToHost, s));
-            PNX_HIP(hipMemcpyAsync(rnorm + off, S.tr, c * sizeof(T), hipMemcpyDeviceToHost, s));
-            if (status) PNX_HIP(hipMemcpyAsync(status + off, S.s, c, hipMemcpyDeviceToHost, s));
-            if (iters) PNX_HIP(hipMemcpyAsync(iters + off, S.i, c * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-            return PNX_OK;
-        };
-        HostCallGuard hg;
-        int r = run_pipeline(n_chunks, n_slots, 1, hg.touchers(), P.device, st, ops);
-        if (r || !defer) return r;
-        if (!overlap_pass) {  // PNX_NNLS_DEFER_OVERLAP=0: the pass after the ring has drained (round 3's order)
-            int rr = nnls_blk_redo_device(&P, defer_cap, dctx.y_side, max_iter, d_sc, d_sr, d_ss, d_si, d_iota, dctx.counters, side.s);
-            if (rr) return rr;
-        }
-        PNX_HIP(hipStreamSynchronize(side.s));  // the deferred pass (launched behind the last chunk's solve)
-        int32_t cnt[2] = {0, 0};
-        PNX_HIP(hipMemcpy(cnt, dctx.counters, sizeof(cnt), hipMemcpyDeviceToHost));
-        const int n = cnt[0];
-        if (n == 0) return PNX_OK;
-        if (n < 0 || (size_t)n > nv) return set_error(PNX_ERR_HIP, "deferred hand-over: %d voxels counted in a call of %zu", n, nv);
-        // More handed-over voxels than the side buffer holds (stronger regularisers than the reference's: a few per cent of the
-        // voxels): the pass behind the last chunk has solved the first defer_cap of them; the others follow in batches of
-        // defer_cap, their signal rows gathered from the caller's array.  (Up to round 4 the whole call ran again.)
-        std::vector<int32_t> where((size_t)n);
-        PNX_HIP(hipMemcpy(where.data(), dctx.bail, where.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
-        for (int i = 0; i < n; ++i)
-            if (where[(size_t)i] < 0 || (size_t)where[(size_t)i] >= nv)
-                return set_error(PNX_ERR_HIP, "deferred hand-over: voxel index %d outside the call's %zu voxels", where[(size_t)i], nv);
-        const int batch = n < defer_cap ? n : defer_cap;
-        std::vector<int32_t> hi((size_t)batch);
-        std::vector<double> hc((size_t)batch * P.n_bins), hr((size_t)batch), rows;
-        std::vector<int8_t> hs((size_t)batch);
-        for (int b0 = 0; b0 < n; b0 += defer_cap) {
-            const int nb = (n - b0) < defer_cap ? (n - b0) : defer_cap;
-            if (b0 > 0) {
-                rows.resize((size_t)nb * P.n_meas);
-                for (int i = 0; i < nb; ++i) {
-                    const T *src = y + (size_t)where[(size_t)(b0 + i)] * P.n_meas;
-                    for (int j = 0; j < P.n_meas; ++j) rows[(size_t)i * P.n_meas + j] = (double)src[j];
-                }
-                PNX_HIP(hipMemcpy(dctx.y_side, rows.data(), rows.size() * sizeof(double), hipMemcpyHostToDevice));
-                // the list is 0 .. nb - 1 (d_iota) and the count on the device is n >= nb: the kernel stops at the nb it is given
-                int rr = nnls_blk_redo_device(&P, nb, dctx.y_side, max_iter, d_sc, d_sr, d_ss, d_si, d_iota, dctx.counters, side.s);
-                if (rr) return rr;
-                PNX_HIP(hipStreamSynchronize(side.s));
-            }
-            PNX_HIP(hipMemcpy(hc.data(), d_sc, (size_t)nb * P.n_bins * sizeof(double), hipMemcpyDeviceToHost));
-            PNX_HIP(hipMemcpy(hr.data(), d_sr, (size_t)nb * sizeof(double), hipMemcpyDeviceToHost));
-            PNX_HIP(hipMemcpy(hs.data(), d_ss, (size_t)nb, hipMemcpyDeviceToHost));
-            PNX_HIP(hipMemcpy(hi.data(), d_si, (size_t)nb * sizeof(int32_t), hipMemcpyDeviceToHost));
-            for (int i = 0; i < nb; ++i) {  // (T) of a double rounds to nearest, as the device's narrowing copy does
-                const size_t v = (size_t)where[(size_t)(b0 + i)];
-                for (int j = 0; j < P.n_bins; ++j) coeff[v * P.n_bins + j] = (T)hc[(size_t)i * P.n_bins + j];
-                rnorm[v] = (T)hr[(size_t)i];
-                if (status) status[v] = hs[(size_t)i];
-                if (iters) iters[v] = hi[(size_t)i];
-            }
-        }
-        return PNX_OK;
-    };
-    rc = run(can_defer);
-    return rc;
+    // 768 Ki the last chunk's download (2 KB per voxel) is what grows.  The ramp only for block-kernel plans, whose hand-over
+    // pass is deferred (a chunk more costs ~1.5 ms, not 8): the download left exposed at the end is 0.4 GB instead of 1.6.
+    C.chunk = (size_t)dev_env_int("PNX_NNLS_HOST_CHUNK", 3 << 18, 1024, 1 << 22);
+    C.ramp = P.blk;
+    C.overlap = true;
+    return nnls_host(P, nv, max_iter, C, st);
 }
 
 extern "C" {
@@ -1225,206 +1123,6 @@ int pnx_nnls_solve_f64(pnx_nnls_plan *plan, int64_t n_vox, const double *y, int 
 int pnx_nnls_solve_f32(pnx_nnls_plan *plan, int64_t n_vox, const float *y, int max_iter, float *coeff, float *rnorm,
                        int8_t *status, int32_t *iters, int mem, void *stream) {
     return nnls_solve<float>(plan, n_vox, y, max_iter, coeff, rnorm, status, iters, mem, stream);
-}
-
-// Host arrays in, peak tables out: the chunk ring of nnls_solve with the peak analysis behind every chunk's solve (the chunk's
-// spectra never leave the device) and the same deferred hand-over -- the handed-over voxels' spectra are solved in one pass at
-// the end, analysed, and their rows of the peak tables patched on the host.
-static int nnls_solve_peaks_host(pnx_nnls_plan *plan, int64_t n_vox, const double *y, int max_iter, const double *bins_host,
-                                 double height, int regularized, double rel_height, int max_peaks, int32_t *n_peaks,
-                                 double *d_values, double *f_values, int n_cut, const double *cutoffs_host, double *d_cut,
-                                 double *f_cut, double *rnorm, int8_t *status, int32_t *iters, hipStream_t st) {
-    NnlsPlanData &P = plan->d;
-    if (max_peaks > 0 && (!d_values || !f_values)) return set_error(PNX_ERR_INVALID, "d_values / f_values are NULL");
-    if (n_cut > 0 && (!cutoffs_host || !d_cut || !f_cut)) return set_error(PNX_ERR_INVALID, "cutoffs / d_cut / f_cut are NULL");
-    const size_t nv = (size_t)n_vox;
-    const size_t chunk = (size_t)dev_env_int("PNX_NNLS_PEAKS_CHUNK", 3 << 18, 1024, 1 << 22);
-    const int n_chunks = (int)((nv + chunk - 1) / chunk);
-    const int n_slots = n_chunks < 3 ? n_chunks : 3;
-    const size_t cap = nv < chunk ? nv : chunk;
-    const size_t mp = (size_t)(max_peaks > 0 ? max_peaks : 1), nc = (size_t)(n_cut > 0 ? n_cut : 1);
-    int rc;
-    struct Out {  // device buffers of one batch of voxels: solver outputs + peak tables
-        double *spec = nullptr, *r = nullptr, *d = nullptr, *f = nullptr, *dc = nullptr, *fc = nullptr;
-        int8_t *s = nullptr;
-        int32_t *i = nullptr, *np = nullptr;
-        void carve(Carver &c, size_t n, int n_bins, size_t mp, size_t nc) {
-            spec = (double *)c.take(n * n_bins * 8);
-            r = (double *)c.take(n * 8);
-            d = (double *)c.take(n * mp * 8);
-            f = (double *)c.take(n * mp * 8);
-            dc = (double *)c.take(n * nc * 8);
-            fc = (double *)c.take(n * nc * 8);
-            i = (int32_t *)c.take(n * 4);
-            np = (int32_t *)c.take(n * 4);
-            s = (int8_t *)c.take(n);
-        }
-    };
-    struct Slot {
-        DevBuf slab;
-        double *y = nullptr;
-        Out o;
-    };
-    std::vector<Slot> slots((size_t)n_slots);
-    for (auto &S : slots)
-        for (int pass = 0; pass < 2; ++pass) {
-            Carver c;
-            c.base = (char *)S.slab.p;
-            S.y = (double *)c.take(cap * P.n_meas * 8);
-            S.o.carve(c, cap, P.n_bins, mp, nc);
-            if (pass == 0 && (rc = S.slab.alloc(c.off))) return rc;
-        }
-    auto analyse = [&](size_t n, const Out &o, hipStream_t s) -> int {
-        return pnx_nnls_spectrum_peaks_f64((int64_t)n, P.n_bins, o.spec, bins_host, height, regularized, rel_height, max_peaks, o.np, o.d,
-                                           o.f, n_cut, cutoffs_host, o.dc, o.fc, PNX_MEM_DEVICE, P.device, s);
-    };
-    const int defer_cap = dev_env_int("PNX_NNLS_DEFER_CAP", 16384, 0, 1 << 22);
-    const bool can_defer = P.blk && n_chunks >= 2 && defer_cap > 0 && nv < ((size_t)1 << 31);
-    DevBuf dslab;
-    NnlsDefer dctx{};
-    if (can_defer) {
-        for (int pass = 0; pass < 2; ++pass) {
-            Carver c;
-            c.base = (char *)dslab.p;
-            dctx.counters = (int32_t *)c.take(2 * sizeof(int32_t));
-            dctx.bail = (int32_t *)c.take(nv * sizeof(int32_t));
-            dctx.y_side = (double *)c.take((size_t)defer_cap * P.n_meas * sizeof(double));
-            if (pass == 0 && (rc = dslab.alloc(c.off))) return rc;
-        }
-        dctx.cap = defer_cap;
-    }
-    auto run = [&](const bool defer) -> int {
-        if (defer) PNX_HIP(hipMemset(dctx.counters, 0, 2 * sizeof(int32_t)));
-        auto span = [&](int k, size_t &off, size_t &c) {
-            off = (size_t)k * chunk;
-            c = (nv - off) < chunk ? (nv - off) : chunk;
-        };
-        PipeOps ops;
-        ops.h2d = [&](int k, int slot, hipStream_t s) -> int {
-            size_t off, c;
-            span(k, off, c);
-            PNX_HIP(hipMemcpyAsync(slots[(size_t)slot].y, y + off * P.n_meas, c * P.n_meas * 8, hipMemcpyHostToDevice, s));
-            return PNX_OK;
-        };
-        ops.launch = [&](int k, int slot, hipStream_t s) -> int {
-            Slot &S = slots[(size_t)slot];
-            size_t off, c;
-            span(k, off, c);
-            int r;
-            if (defer) {
-                NnlsDefer d = dctx;
-                d.base = (int64_t)off;
-                r = nnls_blk_solve_device(&P, (int64_t)c, S.y, max_iter, S.o.spec, S.o.r, S.o.s, S.o.i, s, &d);
-            } else {
-                r = nnls_solve_device(&P, (int64_t)c, S.y, max_iter, S.o.spec, S.o.r, S.o.s, S.o.i, s);
-            }
-            return r ? r : analyse(c, S.o, s);
-        };
-        ops.touch = [&](int k) {
-            size_t off, c;
-            span(k, off, c);
-            touch_pages(rnorm + off, c * 8);
-            if (status) touch_pages(status + off, c);
-            if (iters) touch_pages(iters + off, c * 4);
-            if (n_peaks) touch_pages(n_peaks + off, c * 4);
-            if (max_peaks > 0) {
-                touch_pages(d_values + off * max_peaks, c * max_peaks * 8);
-                touch_pages(f_values + off * max_peaks, c * max_peaks * 8);
-            }
-            if (n_cut > 0) {
-                touch_pages(d_cut + off * n_cut, c * n_cut * 8);
-                touch_pages(f_cut + off * n_cut, c * n_cut * 8);
-            }
-        };
-        ops.d2h = [&](int k, int slot, hipStream_t s) -> int {
-            const Out &o = slots[(size_t)slot].o;
-            size_t off, c;
-            span(k, off, c);
-            PNX_HIP(hipMemcpyAsync(rnorm + off, o.r, c * 8, hipMemcpyDeviceToHost, s));
-            if (status) PNX_HIP(hipMemcpyAsync(status + off, o.s, c, hipMemcpyDeviceToHost, s));
-            if (iters) PNX_HIP(hipMemcpyAsync(iters + off, o.i, c * 4, hipMemcpyDeviceToHost, s));
-            if (n_peaks) PNX_HIP(hipMemcpyAsync(n_peaks + off, o.np, c * 4, hipMemcpyDeviceToHost, s));
-            if (max_peaks > 0) {
-                PNX_HIP(hipMemcpyAsync(d_values + off * max_peaks, o.d, c * max_peaks * 8, hipMemcpyDeviceToHost, s));
-                PNX_HIP(hipMemcpyAsync(f_values + off * max_peaks, o.f, c * max_peaks * 8, hipMemcpyDeviceToHost, s));
-            }
-            if (n_cut > 0) {
-                PNX_HIP(hipMemcpyAsync(d_cut + off * n_cut, o.dc, c * n_cut * 8, hipMemcpyDeviceToHost, s));
-                PNX_HIP(hipMemcpyAsync(f_cut + off * n_cut, o.fc, c * n_cut * 8, hipMemcpyDeviceToHost, s));
-            }
-            return PNX_OK;
-        };
-        HostCallGuard hg;
-        int r = run_pipeline(n_chunks, n_slots, 1, hg.touchers(), P.device, st, ops);
-        if (r || !defer) return r;
-        int32_t cnt[2] = {0, 0};
-        PNX_HIP(hipMemcpy(cnt, dctx.counters, sizeof(cnt), hipMemcpyDeviceToHost));
-        if (cnt[0] == 0) return PNX_OK;
-        if (cnt[0] < 0 || (size_t)cnt[0] > nv) return set_error(PNX_ERR_HIP, "deferred hand-over: %d voxels counted in a call of %zu", cnt[0], nv);
-        const size_t n_all = (size_t)cnt[0];
-        const size_t n = n_all < (size_t)defer_cap ? n_all : (size_t)defer_cap;  // voxels per batch: what the side buffer holds
-        DevBuf side;
-        Out o;
-        int32_t *iota = nullptr;
-        for (int pass = 0; pass < 2; ++pass) {
-            Carver c;
-            c.base = (char *)side.p;
-            o.carve(c, n, P.n_bins, mp, nc);
-            iota = (int32_t *)c.take(n * 4);
-            if (pass == 0 && (r = side.alloc(c.off))) return r;
-        }
-        std::vector<int32_t> idx(n), where(n_all), hi(n), hn(n);
-        for (size_t i = 0; i < n; ++i) idx[i] = (int32_t)i;
-        PNX_HIP(hipMemcpy(iota, idx.data(), n * 4, hipMemcpyHostToDevice));
-        PNX_HIP(hipMemcpy(where.data(), dctx.bail, n_all * 4, hipMemcpyDeviceToHost));
-        for (size_t i = 0; i < n_all; ++i)
-            if (where[i] < 0 || (size_t)where[i] >= nv)
-                return set_error(PNX_ERR_HIP, "deferred hand-over: voxel index %d outside the call's %zu voxels", where[i], nv);
-        std::vector<double> hr(n), hd(n * mp), hf(n * mp), hdc(n * nc), hfc(n * nc), rows;
-        std::vector<int8_t> hs(n);
-        // the side buffer holds the signal rows of the first batch (gathered chunk by chunk on the device); the rows of the
-        // later ones come from the caller's array
-        for (size_t b0 = 0; b0 < n_all; b0 += n) {
-            const size_t nb = (n_all - b0) < n ? (n_all - b0) : n;
-            if (b0 > 0) {
-                rows.resize(nb * (size_t)P.n_meas);
-                for (size_t i = 0; i < nb; ++i) {
-                    const double *src = y + (size_t)where[b0 + i] * P.n_meas;
-                    for (int j = 0; j < P.n_meas; ++j) rows[i * P.n_meas + j] = src[j];
-                }
-                PNX_HIP(hipMemcpy(dctx.y_side, rows.data(), rows.size() * sizeof(double), hipMemcpyHostToDevice));
-            }
-            if ((r = nnls_blk_redo_device(&P, (int64_t)nb, dctx.y_side, max_iter, o.spec, o.r, o.s, o.i, iota, dctx.counters, st))) return r;
-            if ((r = analyse(nb, o, st))) return r;
-            PNX_HIP(hipStreamSynchronize(st));
-            PNX_HIP(hipMemcpy(hr.data(), o.r, nb * 8, hipMemcpyDeviceToHost));
-            PNX_HIP(hipMemcpy(hs.data(), o.s, nb, hipMemcpyDeviceToHost));
-            PNX_HIP(hipMemcpy(hi.data(), o.i, nb * 4, hipMemcpyDeviceToHost));
-            PNX_HIP(hipMemcpy(hn.data(), o.np, nb * 4, hipMemcpyDeviceToHost));
-            PNX_HIP(hipMemcpy(hd.data(), o.d, nb * mp * 8, hipMemcpyDeviceToHost));
-            PNX_HIP(hipMemcpy(hf.data(), o.f, nb * mp * 8, hipMemcpyDeviceToHost));
-            PNX_HIP(hipMemcpy(hdc.data(), o.dc, nb * nc * 8, hipMemcpyDeviceToHost));
-            PNX_HIP(hipMemcpy(hfc.data(), o.fc, nb * nc * 8, hipMemcpyDeviceToHost));
-            for (size_t i = 0; i < nb; ++i) {
-                const size_t v = (size_t)where[b0 + i];
-                rnorm[v] = hr[i];
-                if (status) status[v] = hs[i];
-                if (iters) iters[v] = hi[i];
-                if (n_peaks) n_peaks[v] = hn[i];
-                for (int j = 0; j < max_peaks; ++j) {
-                    d_values[v * max_peaks + j] = hd[i * mp + j];
-                    f_values[v * max_peaks + j] = hf[i * mp + j];
-                }
-                for (int j = 0; j < n_cut; ++j) {
-                    d_cut[v * n_cut + j] = hdc[i * nc + j];
-                    f_cut[v * n_cut + j] = hfc[i * nc + j];
-                }
-            }
-        }
-        return PNX_OK;
-    };
-    rc = run(can_defer);
-    return rc;
 }
 
 int pnx_nnls_solve_peaks_f64(pnx_nnls_plan *plan, int64_t n_vox, const double *y, int max_iter, const double *bins_host,
@@ -1440,71 +1138,52 @@ int pnx_nnls_solve_peaks_f64(pnx_nnls_plan *plan, int64_t n_vox, const double *y
     hipStream_t st = (hipStream_t)stream;
     if (max_iter <= 0) max_iter = 3 * P.n_bins;
     std::lock_guard<std::mutex> plan_lock(plan->mu);
-    if (mem == PNX_MEM_HOST && dev_env_int("PNX_NNLS_PEAKS_RING", 1, 0, 1))
-        return nnls_solve_peaks_host(plan, n_vox, y, max_iter, bins_host, height, regularized, rel_height, max_peaks, n_peaks, d_values,
-                                     f_values, n_cut, cutoffs_host, d_cut, f_cut, rnorm, status, iters, st);
-    // spectra of one chunk live in device scratch only: solve -> peak analysis -> next chunk
-    const size_t chunk = (size_t)dev_env_int("PNX_NNLS_PEAKS_CHUNK", 1 << 20, 1024, 1 << 22);
-    const size_t nv = (size_t)n_vox, cap = nv < chunk ? nv : chunk;
-    DevBuf spec, stage;
-    int rc;
-    if ((rc = spec.alloc(cap * P.n_bins * sizeof(double)))) return rc;
-    const bool host = mem == PNX_MEM_HOST;
-    Carver c;
-    double *sy = nullptr, *sr = nullptr, *sd = nullptr, *sf = nullptr, *sdc = nullptr, *sfc = nullptr;
-    int8_t *ss = nullptr;
-    int32_t *si = nullptr, *sn = nullptr;
-    if (host) {
-        for (int pass = 0; pass < 2; ++pass) {
-            c = Carver();
-            c.base = (char *)stage.p;
-            sy = (double *)c.take(cap * P.n_meas * 8);
-            sr = (double *)c.take(cap * 8);
-            sd = (double *)c.take(cap * (max_peaks > 0 ? max_peaks : 1) * 8);
-            sf = (double *)c.take(cap * (max_peaks > 0 ? max_peaks : 1) * 8);
-            sdc = (double *)c.take(cap * (n_cut > 0 ? n_cut : 1) * 8);
-            sfc = (double *)c.take(cap * (n_cut > 0 ? n_cut : 1) * 8);
-            si = (int32_t *)c.take(cap * 4);
-            sn = (int32_t *)c.take(cap * 4);
-            ss = (int8_t *)c.take(cap);
-            if (pass == 0 && (rc = stage.alloc(c.off))) return rc;
-        }
+    const size_t nv = (size_t)n_vox;
+    if (mem == PNX_MEM_HOST) {
+        // the chunk ring of nnls_solve with the peak analysis behind every chunk's solve (the chunk's spectra never leave the
+        // device) and the same deferred hand-over: the handed-over voxels' spectra are solved in one pass after the ring,
+        // analysed, and their rows of the peak tables patched on the host
+        if (max_peaks > 0 && (!d_values || !f_values)) return set_error(PNX_ERR_INVALID, "d_values / f_values are NULL");
+        if (n_cut > 0 && (!cutoffs_host || !d_cut || !f_cut)) return set_error(PNX_ERR_INVALID, "cutoffs / d_cut / f_cut are NULL");
+        const size_t mp = (size_t)(max_peaks > 0 ? max_peaks : 1), nc = (size_t)(n_cut > 0 ? n_cut : 1);
+        NnlsHostCall C;
+        C.A.add(y, sizeof(double), P.n_meas, false);
+        C.A.add(nullptr, sizeof(double), P.n_bins, true).always = true;
+        C.A.add(rnorm, sizeof(double), 1, true);
+        C.A.add(status, 1, 1, true).always = true;
+        C.A.add(iters, sizeof(int32_t), 1, true).always = true;
+        C.A.add(n_peaks, sizeof(int32_t), 1, true).always = true;
+        C.A.add(max_peaks > 0 ? d_values : nullptr, sizeof(double), mp, true).always = true;
+        C.A.add(max_peaks > 0 ? f_values : nullptr, sizeof(double), mp, true).always = true;
+        C.A.add(n_cut > 0 ? d_cut : nullptr, sizeof(double), nc, true).always = true;
+        C.A.add(n_cut > 0 ? f_cut : nullptr, sizeof(double), nc, true).always = true;
+        C.chunk = (size_t)dev_env_int("PNX_NNLS_PEAKS_CHUNK", 3 << 18, 1024, 1 << 22);
+        C.post = [&](size_t n, const DevSet &D, hipStream_t s) {
+            return pnx_nnls_spectrum_peaks_f64((int64_t)n, P.n_bins, D.d(NN_SPEC), bins_host, height, regularized, rel_height, max_peaks,
+                                               (int32_t *)D.dev[NN_NPEAKS], D.d(NN_D), D.d(NN_F), n_cut, cutoffs_host, D.d(NN_DC),
+                                               D.d(NN_FC), PNX_MEM_DEVICE, P.device, s);
+        };
+        return nnls_host(P, nv, max_iter, C, st);
     }
+    // device arrays: the spectra of one chunk live in device scratch only: solve -> peak analysis -> next chunk
+    const size_t chunk = (size_t)dev_env_int("PNX_NNLS_PEAKS_CHUNK", 1 << 20, 1024, 1 << 22);
+    DevBuf spec;
+    int rc;
+    if ((rc = spec.alloc((nv < chunk ? nv : chunk) * P.n_bins * sizeof(double)))) return rc;
     for (size_t off = 0; off < nv; off += chunk) {
         const size_t n = (nv - off) < chunk ? (nv - off) : chunk;
-        const double *yd = y + off * P.n_meas;
-        if (host) {
-            PNX_HIP(hipMemcpyAsync(sy, yd, n * P.n_meas * 8, hipMemcpyHostToDevice, st));
-            yd = sy;
-        }
-        double *rd = host ? sr : rnorm + off;
-        int8_t *std_ = host ? ss : (status ? status + off : nullptr);
-        int32_t *itd = host ? si : (iters ? iters + off : nullptr);
-        if ((rc = nnls_solve_device(&P, (int64_t)n, yd, max_iter, (double *)spec.p, rd, std_, itd, st))) return rc;
+        if ((rc = nnls_solve_device(&P, (int64_t)n, y + off * P.n_meas, max_iter, (double *)spec.p, rnorm + off,
+                                    status ? status + off : nullptr, iters ? iters + off : nullptr, st)))
+            return rc;
         rc = pnx_nnls_spectrum_peaks_f64((int64_t)n, P.n_bins, (const double *)spec.p, bins_host, height, regularized, rel_height,
-                                         max_peaks, host ? sn : (n_peaks ? n_peaks + off : nullptr),
-                                         host ? sd : (d_values ? d_values + off * max_peaks : nullptr),
-                                         host ? sf : (f_values ? f_values + off * max_peaks : nullptr), n_cut, cutoffs_host,
-                                         host ? sdc : (d_cut ? d_cut + off * n_cut : nullptr),
-                                         host ? sfc : (f_cut ? f_cut + off * n_cut : nullptr), PNX_MEM_DEVICE, P.device, st);
+                                         max_peaks, n_peaks ? n_peaks + off : nullptr, d_values ? d_values + off * max_peaks : nullptr,
+                                         f_values ? f_values + off * max_peaks : nullptr, n_cut, cutoffs_host,
+                                         d_cut ? d_cut + off * n_cut : nullptr, f_cut ? f_cut + off * n_cut : nullptr,
+                                         PNX_MEM_DEVICE, P.device, st);
         if (rc) return rc;
-        if (host) {
-            PNX_HIP(hipMemcpyAsync(rnorm + off, sr, n * 8, hipMemcpyDeviceToHost, st));
-            if (status) PNX_HIP(hipMemcpyAsync(status + off, ss, n, hipMemcpyDeviceToHost, st));
-            if (iters) PNX_HIP(hipMemcpyAsync(iters + off, si, n * 4, hipMemcpyDeviceToHost, st));
-            if (n_peaks) PNX_HIP(hipMemcpyAsync(n_peaks + off, sn, n * 4, hipMemcpyDeviceToHost, st));
-            if (max_peaks > 0) {
-                PNX_HIP(hipMemcpyAsync(d_values + off * max_peaks, sd, n * max_peaks * 8, hipMemcpyDeviceToHost, st));
-                PNX_HIP(hipMemcpyAsync(f_values + off * max_peaks, sf, n * max_peaks * 8, hipMemcpyDeviceToHost, st));
-            }
-            if (n_cut > 0) {
-                PNX_HIP(hipMemcpyAsync(d_cut + off * n_cut, sdc, n * n_cut * 8, hipMemcpyDeviceToHost, st));
-                PNX_HIP(hipMemcpyAsync(f_cut + off * n_cut, sfc, n * n_cut * 8, hipMemcpyDeviceToHost, st));
-            }
-        }
         // the spectrum scratch is reused by the next chunk: in-order on one stream
     }
-    PNX_HIP(hipStreamSynchronize(st));  // the scratch buffers are freed on return
+    PNX_HIP(hipStreamSynchronize(st));  // the scratch buffer is freed on return
     return PNX_OK;
 }
 

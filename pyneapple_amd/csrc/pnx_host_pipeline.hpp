@@ -2,6 +2,9 @@
 // granules between them), free of HIP types: pnx_api.hip instantiates it on the HIP runtime, tests/host_stub/ builds the same
 // code for the CPU against a stub device and runs it under ThreadSanitizer and AddressSanitizer (tests/test_host_sanitizers.py).
 //
+//   ArrayTable          the arrays a host-array call moves (pointer, element size, width, layout, direction)
+//   chunk_bounds        where the chunk ring cuts a volume
+//   check_rows / gather_rows / patch_rows   the host half of the deferred NNLS hand-over
 //   run_pipeline_t<B>   the chunk ring: IN / LAUNCH / OUT / page-touch stages over n_slots device slots
 //   run_streamed        the state machine around ONE persistent kernel that consumes a volume while it is being uploaded and
 //                       whose results are downloaded granule by granule while it still runs (curve fit from host arrays)
@@ -12,7 +15,9 @@
 #include <atomic>
 #include <chrono>
 #include <condition_variable>
+#include <cstdint>
 #include <cstdio>
+#include <cstring>
 #include <functional>
 #include <mutex>
 #include <string>
@@ -26,6 +31,83 @@ namespace pnx {
 int set_error(int code, const char *fmt, ...) __attribute__((format(printf, 2, 3)));
 // the calling thread's last message (the failing helper thread's message travels to the caller through it)
 const char *last_error_text();
+
+// ---- the arrays of a host-array call ---------------------------------------------------------------------------
+// One entry per array the call may move.  Voxel-major arrays are (n_vox, w) on both sides; parameter-major ones are (w, n_vox)
+// on the host and (w, stride) on the device, one row slice per element of a voxel.  The device computes in fp64: an _f32 entry
+// point's floating-point arrays are `widen`ed (a float transfer buffer beside the fp64 working copy).
+struct HostArray {
+    void *host = nullptr;  // the caller's array; null: not requested
+    int esize = 8;         // bytes per element of the caller's array
+    bool widen = false;    // the caller's array is float, the device's working copy fp64
+    size_t w = 1;          // elements per voxel
+    bool pmajor = false;   // (w, n_vox) instead of (n_vox, w)
+    bool out = false;      // device -> host
+    bool always = false;   // the device buffer is needed even when the caller did not ask for the array
+};
+struct ArrayTable {
+    static constexpr int kMax = 12;
+    HostArray a[kMax];
+    int n = 0;
+    HostArray &add(const void *host, size_t esize, size_t w, bool out, bool widen = false) {
+        HostArray &e = a[n++];
+        e.host = const_cast<void *>(host);
+        e.esize = (int)esize;
+        e.w = w;
+        e.out = out;
+        e.widen = widen;
+        return e;
+    }
+};
+
+// Chunk boundaries of [0, nv): pieces of `chunk` voxels, the last one ragged.  Ramped, with three or more full chunks, the
+// first and the last piece are a quarter chunk: the first kernel starts after a quarter of an upload, and the serial tail (last
+// kernel, last download) is a quarter as long.
+inline std::vector<size_t> chunk_bounds(size_t nv, size_t chunk, bool ramp) {
+    const size_t r = ramp && nv >= 3 * chunk ? chunk / 4 : 0;
+    std::vector<size_t> b(1, 0);
+    size_t v = 0;
+    if (r) b.push_back(v = r);
+    const size_t body_end = nv - r;
+    while (v < body_end) b.push_back(v = (body_end - v) < chunk ? body_end : v + chunk);
+    if (r) b.push_back(nv);
+    return b;
+}
+
+// ---- deferred hand-over, host half: the device has listed `where` (indices within the call) and solved those voxels again
+// into batch buffers; their rows replace the first pass's in the caller's arrays.
+inline int check_rows(const int32_t *where, size_t n, size_t nv) {
+    for (size_t i = 0; i < n; ++i)
+        if (where[i] < 0 || (size_t)where[i] >= nv)
+            return set_error(PNX_ERR_HIP, "deferred hand-over: voxel index %d outside the call's %zu voxels", where[i], nv);
+    return PNX_OK;
+}
+// the signal rows of voxels where[0 .. nb) of the caller's (n_vox, w) array `in`, as fp64
+inline void gather_rows(const HostArray &in, const int32_t *where, size_t nb, double *rows) {
+    for (size_t i = 0; i < nb; ++i)
+        for (size_t j = 0; j < in.w; ++j) {
+            const size_t e = (size_t)where[i] * in.w + j;
+            rows[i * in.w + j] = in.esize == 4 ? (double)((const float *)in.host)[e] : ((const double *)in.host)[e];
+        }
+}
+// rows[k]: batch rows of the requested voxel-major output k of A (fp64 when widened, the caller's type otherwise) -> the
+// caller's rows where[0 .. nb).  Nothing is written unless every index lies in [0, nv).  (float) of a double rounds to nearest,
+// as the device's narrowing copy does.
+inline int patch_rows(const ArrayTable &A, const void *const *rows, const int32_t *where, size_t nb, size_t nv) {
+    if (int rc = check_rows(where, nb, nv)) return rc;
+    for (int k = 0; k < A.n; ++k) {
+        const HostArray &a = A.a[k];
+        if (!a.out || !a.host) continue;
+        for (size_t i = 0; i < nb; ++i) {
+            const size_t v = (size_t)where[i];
+            if (a.widen)
+                for (size_t j = 0; j < a.w; ++j) ((float *)a.host)[v * a.w + j] = (float)((const double *)rows[k])[i * a.w + j];
+            else
+                memcpy((char *)a.host + v * a.w * a.esize, (const char *)rows[k] + i * a.w * a.esize, a.w * a.esize);
+        }
+    }
+    return PNX_OK;
+}
 
 // ---- host-staging pipeline ------------------------------------------------------------------------------------
 // PNX_MEM_HOST calls hand over pageable numpy memory.  The volume is cut into chunks of voxels that flow through a

@@ -15,7 +15,7 @@ import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from pyneapple_amd import api, synth  # noqa: E402
 
-KNOBS = ("PNX_NNLS_HOST_CHUNK", "PNX_NNLS_DEFER_CAP", "PNX_NNLS_PEAKS_CHUNK", "PNX_NNLS_PEAKS_RING", "PNX_HOST_TOUCHERS", "PNX_HOST_RAMP")
+KNOBS = ("PNX_NNLS_HOST_CHUNK", "PNX_NNLS_DEFER_CAP", "PNX_NNLS_PEAKS_CHUNK", "PNX_HOST_TOUCHERS")
 
 
 def run(n_cases=40, seed=0, verbose=True):
@@ -47,8 +47,7 @@ def run(n_cases=40, seed=0, verbose=True):
             chunk = int(rng.integers(1024, 5000))
             cap = str(rng.choice(["16384", "0", str(max(1, n_hand - 1)), "1"]))
             env = {"PNX_NNLS_HOST_CHUNK": str(chunk), "PNX_NNLS_PEAKS_CHUNK": str(chunk), "PNX_NNLS_DEFER_CAP": cap,
-                   "PNX_NNLS_PEAKS_RING": str(int(rng.random() < 0.85)), "PNX_HOST_TOUCHERS": str(int(rng.integers(0, 4))),
-                   "PNX_HOST_RAMP": str(int(rng.random() < 0.7))}
+                   "PNX_HOST_TOUCHERS": str(int(rng.integers(0, 4)))}
             os.environ.update(env)
             many = plan.solve_peaks(yy, bins, **pk) if peaks else plan.solve(yy, 250)
             voxels += n

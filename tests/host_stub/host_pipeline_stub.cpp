@@ -308,7 +308,69 @@ static void streamed_case(int n_vox, int piece, int gran, int n_out, int toucher
     }
 }
 
+// ---- chunk bounds and the host half of the deferred hand-over ---------------------------------------------------------
+static void bounds_case(size_t nv, size_t chunk, bool ramp) {
+    const std::vector<size_t> b = chunk_bounds(nv, chunk, ramp);
+    bool ok = b.size() >= 2 && b.front() == 0 && b.back() == nv;
+    for (size_t k = 0; ok && k + 1 < b.size(); ++k) ok = b[k] < b[k + 1] && b[k + 1] - b[k] <= chunk;
+    CHECK(ok, "chunk_bounds(%zu, %zu, %d) does not tile [0, nv) with pieces of at most a chunk", nv, chunk, (int)ramp);
+    const bool ramped = ramp && nv >= 3 * chunk;
+    if (ramped) CHECK(b[1] == chunk / 4 && nv - b[b.size() - 2] == chunk / 4, "ramped bounds of %zu: first / last piece not a quarter chunk", nv);
+    else CHECK(b.size() - 1 == (nv + chunk - 1) / chunk, "bounds of %zu in chunks of %zu: %zu pieces", nv, chunk, b.size() - 1);
+}
+
+static void patch_case() {
+    const size_t nv = 10, nb = 3;
+    std::vector<float> coeff(nv * 2, -1.0f);
+    std::vector<int8_t> status(nv, 0);
+    ArrayTable A;
+    A.add(nullptr, sizeof(float), 4, false, true);                      // an input: never patched
+    A.add(coeff.data(), sizeof(float), 2, true, true);                   // widened: fp64 rows -> float
+    A.add(nullptr, sizeof(double), 1, true).always = true;               // not requested: skipped
+    A.add(status.data(), 1, 1, true);
+    const double c_rows[nb * 2] = {0.1, 1.0 / 3.0, 2.5, 1e-40, 3.0, 16777217.0};
+    const int8_t s_rows[nb] = {1, 2, 3};
+    const void *rows[ArrayTable::kMax] = {nullptr, c_rows, nullptr, s_rows};
+    const int32_t where[nb] = {7, 0, 9};
+    CHECK(patch_rows(A, rows, where, nb, nv) == PNX_OK, "patch_rows: %s", last_error_text());
+    for (size_t i = 0; i < nb; ++i) {
+        for (size_t j = 0; j < 2; ++j)
+            CHECK(coeff[where[i] * 2 + j] == (float)c_rows[i * 2 + j], "patched coefficient %zu,%zu is not the double rounded to float", i, j);
+        CHECK(status[where[i]] == s_rows[i], "patched status %zu", i);
+    }
+    int untouched = 0;
+    for (size_t v = 0; v < nv; ++v) untouched += v != 7 && v != 0 && v != 9 && coeff[v * 2] == -1.0f && coeff[v * 2 + 1] == -1.0f && status[v] == 0;
+    CHECK(untouched == 7, "patch_rows wrote rows it was not given");
+    // an index outside [0, nv) anywhere in the batch: an error, and nothing is written
+    for (int32_t bad : {-1, (int32_t)nv}) {
+        std::vector<float> c2(nv * 2, -1.0f);
+        std::vector<int8_t> s2(nv, 0);
+        A.a[1].host = c2.data();
+        A.a[3].host = s2.data();
+        const int32_t w2[nb] = {2, 5, bad};
+        CHECK(patch_rows(A, rows, w2, nb, nv) == PNX_ERR_HIP, "patch_rows accepted voxel index %d of %zu", bad, nv);
+        CHECK(check_rows(w2, nb, nv) == PNX_ERR_HIP, "check_rows accepted voxel index %d", bad);
+        bool clean = true;
+        for (size_t v = 0; v < nv; ++v) clean = clean && c2[v * 2] == -1.0f && c2[v * 2 + 1] == -1.0f && s2[v] == 0;
+        CHECK(clean, "a patch with voxel index %d wrote rows", bad);
+    }
+    // gather: float rows of a (n_vox, 3) input as fp64
+    std::vector<float> y(nv * 3);
+    for (size_t e = 0; e < y.size(); ++e) y[e] = 0.1f * (float)e;
+    ArrayTable B;
+    const HostArray &in = B.add(y.data(), sizeof(float), 3, false, true);
+    double g[nb * 3];
+    gather_rows(in, where, nb, g);
+    for (size_t i = 0; i < nb; ++i)
+        for (size_t j = 0; j < 3; ++j) CHECK(g[i * 3 + j] == (double)y[where[i] * 3 + j], "gathered row %zu,%zu", i, j);
+}
+
 int main() {
+    // chunk bounds: ragged (no ramp, or too few chunks for one) and ramped, over sizes around the chunk multiples
+    for (size_t chunk : {1024, 3000, 4096})
+        for (size_t nv : {(size_t)1, chunk - 1, chunk, chunk + 1, 3 * chunk - 1, 3 * chunk, 3 * chunk + 7, 7 * chunk + chunk / 2})
+            for (bool ramp : {false, true}) bounds_case(nv, chunk, ramp);
+    patch_case();
     // chunk ring: one chunk (no threads), two, many; slots 2-4; one or two kernel streams; 0-3 page-touch helpers
     ring_case(1000, 4096, 3, 2, 2, 0, 0);
     ring_case(5000, 2500, 3, 1, 0, 0, 0);

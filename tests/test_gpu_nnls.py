@@ -414,10 +414,11 @@ def test_host_chunks_defer_the_hand_over_pass(gpu, monkeypatch):
 def test_peak_tables_from_host_arrays_in_chunks(gpu, monkeypatch):
     """pnx_nnls_solve_peaks_f64 on host arrays: chunk ring with the peak analysis behind every chunk's solve and the deferred
     hand-over (the handed-over voxels' peak rows are patched at the end).  Equal to the one-chunk call, to the per-chunk
-    hand-over, to the old serial loop, and to solve() followed by the peak analysis of the returned spectra."""
+    hand-over, to the serial loop of the PNX_MEM_DEVICE entry point on device copies of the same rows, and to solve()
+    followed by the peak analysis of the returned spectra."""
     import torch
 
-    from pyneapple_amd import synth
+    from pyneapple_amd import _lib, synth
 
     bins, basis, reg = synth.nnls_matrices(32)
     _, yt = synth.make_torch_rows("tri_reduced", 0, 1 << 14, 32, torch.device("cuda", 0), sigma=0.01, scale=1000.0)
@@ -435,12 +436,27 @@ def test_peak_tables_from_host_arrays_in_chunks(gpu, monkeypatch):
         np.testing.assert_array_equal(one[k], ref[k], err_msg=k)
     np.testing.assert_array_equal(one["residual"], full["residual"])
     monkeypatch.setenv("PNX_NNLS_PEAKS_CHUNK", "3000")
-    for cap, ring in (("16384", "1"), ("0", "1"), ("16384", "0"), ("1", "1")):  # the last: one handed-over voxel per batch
+    for cap in ("16384", "0", "1"):  # the last: one handed-over voxel per batch
         monkeypatch.setenv("PNX_NNLS_DEFER_CAP", cap)
-        monkeypatch.setenv("PNX_NNLS_PEAKS_RING", ring)
         many = plan.solve_peaks(y, bins, **kw)
         for k in one:
-            np.testing.assert_array_equal(many[k], one[k], err_msg=f"{k} cap={cap} ring={ring}")
+            np.testing.assert_array_equal(many[k], one[k], err_msg=f"{k} cap={cap}")
+    # the serial loop: PNX_MEM_DEVICE on torch copies of the rows, with the arguments NnlsPlan.solve_peaks passes for host arrays
+    dev = torch.device("cuda", 0)
+    n, cut = y.shape[0], np.ascontiguousarray(cuts, np.float64).reshape(-1, 2)
+    out = dict(n_peaks=torch.empty(n, dtype=torch.int32, device=dev), d_values=torch.empty((n, 8), dtype=torch.float64, device=dev),
+               f_values=torch.empty((n, 8), dtype=torch.float64, device=dev), d_cut=torch.empty((n, 3), dtype=torch.float64, device=dev),
+               f_cut=torch.empty((n, 3), dtype=torch.float64, device=dev), residual=torch.empty(n, dtype=torch.float64, device=dev),
+               status=torch.empty(n, dtype=torch.int8, device=dev), iters=torch.empty(n, dtype=torch.int32, device=dev))
+    yd, bins_h = torch.from_numpy(y).to(dev), np.ascontiguousarray(bins, np.float64)
+    torch.cuda.synchronize()
+    _lib.check(_lib.load().pnx_nnls_solve_peaks_f64(plan._h, n, _lib.ptr(yd), 250, _lib.ptr(bins_h), 0.1, 1, 0.5, 8,
+                                                    _lib.ptr(out["n_peaks"]), _lib.ptr(out["d_values"]), _lib.ptr(out["f_values"]), 3,
+                                                    _lib.ptr(cut), _lib.ptr(out["d_cut"]), _lib.ptr(out["f_cut"]), _lib.ptr(out["residual"]),
+                                                    _lib.ptr(out["status"]), _lib.ptr(out["iters"]), _lib.MEM_DEVICE, None))
+    torch.cuda.synchronize()
+    for k in one:
+        np.testing.assert_array_equal(out[k].cpu().numpy(), one[k], err_msg=f"{k} serial loop")
     plan.close()
 
 
