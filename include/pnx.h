@@ -32,9 +32,10 @@
  *   - Environment.  A production process reads five variables, none of which changes a result or selects a kernel:
  *     PNX_STREAM_CACHE_MB (staging slab a host-array curve fit keeps per device, default 8192), PNX_COPY_PIECE_MB (32) and
  *     PNX_COPY_THREADS (4) of pnx_upload / pnx_download, PNX_HOST_TOUCHERS and PNX_STREAM_OUT_THREADS (helper threads of a
- *     host-array call).  Everything else the sources know -- A/B switches between kernels (PNX_NNLS_NO_BLK, PNX_BLK_NO_WIDE,
- *     PNX_NNLS_NO_QR, PNX_NNLS_NO_MFMA, PNX_BLK_ROUTE_PERMILLE ...), chunk sizes of the host pipelines, trace output and the
- *     test hook PNX_NNLS_TEST_REJECT (forces rejected candidate columns in the NNLS block kernel) -- is read ONLY when the
+ *     host-array call).  Everything else the sources know -- the NNLS switches PNX_NNLS_NO_BLK (banded regularisers take the
+ *     Gram form), PNX_BLK_ROUTE_PERMILLE and PNX_BLK_ROUTE_DEBUG (the block kernel's pilot), PNX_NNLS_DEFER_CAP (deferred
+ *     hand-over), chunk sizes of the host pipelines, trace output and the test hook PNX_NNLS_TEST_REJECT (forces rejected
+ *     candidate columns in the NNLS block kernel) -- is read ONLY when the
  *     process was started with PNX_ENABLE_TEST_HOOKS=1 (looked at once, at the first query); the test-suite and the
  *     profiling scripts set it, bench.py and the plugin never do.
  */

@@ -949,7 +949,7 @@ static int nnls_host(NnlsPlanData &P, size_t nv, int max_iter, const NnlsHostCal
     // collect the voxels' indices and signal rows, ONE pass at the end of the call solves them, and their rows are patched
     // into the caller's arrays (C4 from numpy arrays: seven passes -> one).
     const int defer_cap = dev_env_int("PNX_NNLS_DEFER_CAP", 16384, 0, 1 << 22);
-    const bool defer = P.blk && n_chunks >= 2 && defer_cap > 0 && nv < ((size_t)1 << 31);
+    const bool defer = P.path == NnlsPath::Blk && n_chunks >= 2 && defer_cap > 0 && nv < ((size_t)1 << 31);
     const size_t dcap = (size_t)defer_cap;
     DevBuf dslab;
     NnlsDefer dctx{};
@@ -1109,7 +1109,7 @@ static int nnls_solve(pnx_nnls_plan *plan, int64_t n_vox, const T *y, int max_it
     // 768 Ki the last chunk's download (2 KB per voxel) is what grows.  The ramp only for block-kernel plans, whose hand-over
     // pass is deferred (a chunk more costs ~1.5 ms, not 8): the download left exposed at the end is 0.4 GB instead of 1.6.
     C.chunk = (size_t)dev_env_int("PNX_NNLS_HOST_CHUNK", 3 << 18, 1024, 1 << 22);
-    C.ramp = P.blk;
+    C.ramp = P.path == NnlsPath::Blk;
     C.overlap = true;
     return nnls_host(P, nv, max_iter, C, st);
 }

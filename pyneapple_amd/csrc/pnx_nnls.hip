@@ -80,7 +80,6 @@ struct NnlsArgs {
     int rhb;       // its half bandwidth (1 or 2); 0: general regulariser, rows of RT are used instead
     const int32_t *redo_list, *redo_count;  // non-null: only the voxels redo_list[0 .. *redo_count) (handed over by pnx_nnls_blk.hip, or by <8, 4> to <8, 8>)
     int32_t *bail;  // <KB, KP < KB> only: [0] number of voxels whose passive set outgrew 64 KP positions, [1 ..] their indices
-    const int32_t *route = nullptr;  // non-null: the launch only runs when *route == 1 (the pilot of a block-kernel plan chose the Gram form, pnx_nnls_blk.hip)
 };
 
 __device__ inline int tri(int i) { return i * (i + 1) / 2; }
@@ -179,7 +178,6 @@ template <int KB, int KP> __global__ void __launch_bounds__(64, KB == 4 ? PNX_NN
     gen_glb_double *MgT = (gen_glb_double *)Mg;
     const int n = A.n_bins, nm = A.n_meas, nreg = A.n_reg;
     const int m_total = nm + nreg;
-    if (A.route && *A.route != 1) return;  // wave uniform: the pilot kept the block kernel, nothing to do here
 
     for (;;) {
         unsigned long long vq = 0;
@@ -821,17 +819,8 @@ __global__ void basis_kernel(const double *b, const double *bins, int nm, int n,
     out[(size_t)i * n + j] = exp(-b[i] * bins[j]);  // model_functions/nnls.py:41-43
 }
 
-#define PNX_HIPN(call)                                                                             \
-    do {                                                                                           \
-        hipError_t e__ = (call);                                                                   \
-        if (e__ != hipSuccess) return set_error(PNX_ERR_HIP, "%s: %s", #call, hipGetErrorString(e__)); \
-    } while (0)
-
 // rows 0..kLdsRows-1 of M plus a 64-entry broadcast buffer (a uniform-address ds_read_b64 replaces two v_readlane)
-static size_t nnls_lds_bytes() {
-    static const size_t pad = dev_getenv("PNX_NNLS_LDS_PAD") ? (size_t)atoi(dev_getenv("PNX_NNLS_LDS_PAD")) : 0;  // occupancy experiments
-    return sizeof(double) * (kLdsTri + kW) + pad;
-}
+constexpr size_t kNnlsLdsBytes = sizeof(double) * (kLdsTri + kW);
 static_assert(kLdsTri >= 2 + kNnlsWideBins + 2, "the epilogue's bin-ordered scratch aliases the LDS rows of M");
 
 // Is reg what model_functions/nnls.py:46-85 builds for orders 1-3: square, R[i][j] = c[j - i] inside a band of half width
@@ -857,14 +846,23 @@ namespace {
 struct SharedSlabs {
     std::mutex mu;
     int refs = 0;
-    double *blk4 = nullptr, *gram = nullptr;
+    double *blk4 = nullptr, *gram = nullptr;  // allocated together with `last`: all three or none
     size_t blk4_bytes = 0, gram_bytes = 0;
-    hipEvent_t last = nullptr;       // recorded behind the last launch that used the slabs ...
-    hipStream_t last_stream = nullptr;  // ... on this stream
-    bool used = false;
+    hipEvent_t last = nullptr;  // recorded behind the last launch that used the slabs
+    bool used = false;          // ... once there has been one
 };
 constexpr int kMaxSharedDevices = 64;
 SharedSlabs g_shared[kMaxSharedDevices];
+// frees the set on the current device (hipFree synchronises it: nothing enqueued still uses the slabs)
+void shared_free(SharedSlabs &S) {
+    if (S.blk4) (void)hipFree(S.blk4);
+    if (S.gram) (void)hipFree(S.gram);
+    if (S.last) (void)hipEventDestroy(S.last);
+    S.blk4 = S.gram = nullptr;
+    S.last = nullptr;
+    S.blk4_bytes = S.gram_bytes = 0;
+    S.used = false;
+}
 }  // namespace
 
 int nnls_shared_slabs_get(int device, size_t blk4_bytes, size_t gram_bytes, double **blk4, double **gram) {
@@ -873,23 +871,19 @@ int nnls_shared_slabs_get(int device, size_t blk4_bytes, size_t gram_bytes, doub
     std::lock_guard<std::mutex> lk(S.mu);
     if (S.blk4 && (S.blk4_bytes < blk4_bytes || S.gram_bytes < gram_bytes)) {
         if (S.refs) return set_error(PNX_ERR_NOMEM, "device %d: shared NNLS slabs are in use at another size", device);
-        (void)hipFree(S.blk4);
-        (void)hipFree(S.gram);
-        S.blk4 = S.gram = nullptr;
+        shared_free(S);
     }
     if (!S.blk4) {
         hipError_t e = hipMalloc(&S.blk4, blk4_bytes);
         if (e == hipSuccess) e = hipMemset(S.blk4, 0, blk4_bytes);  // the block sweeps read whole blocks, also rows nobody has written yet: finite
         if (e == hipSuccess) e = hipMalloc(&S.gram, gram_bytes);
+        if (e == hipSuccess) e = hipEventCreateWithFlags(&S.last, hipEventDisableTiming);
         if (e != hipSuccess) {  // all or nothing: a half-made set must not be handed to the next plan
-            if (S.blk4) (void)hipFree(S.blk4);
-            S.blk4 = S.gram = nullptr;
+            shared_free(S);
             return set_error(PNX_ERR_NOMEM, "shared NNLS slabs (%zu + %zu bytes) on device %d: %s", blk4_bytes, gram_bytes, device, hipGetErrorString(e));
         }
         S.blk4_bytes = blk4_bytes;
         S.gram_bytes = gram_bytes;
-        if (!S.last) PNX_HIPN(hipEventCreateWithFlags(&S.last, hipEventDisableTiming));
-        S.used = false;
     }
     S.refs += 1;
     *blk4 = S.blk4;
@@ -910,64 +904,58 @@ int nnls_shared_slabs_trim(int device) {
         int cur = 0;
         (void)hipGetDevice(&cur);
         (void)hipSetDevice(device);
-        (void)hipFree(S.blk4);  // synchronises the device: nothing enqueued still uses them
-        (void)hipFree(S.gram);
+        shared_free(S);
         (void)hipSetDevice(cur);
-        S.blk4 = S.gram = nullptr;
-        S.blk4_bytes = S.gram_bytes = 0;
-        S.used = false;
     }
     return 1;
 }
-NnlsSharedUse::NnlsSharedUse(const NnlsPlanData *P_, hipStream_t stream_) : P(P_ && P_->shared_slabs ? P_ : nullptr), stream(stream_) {
-    if (!P) return;
+int nnls_shared_acquire(const NnlsPlanData *P, hipStream_t stream) {
     SharedSlabs &S = g_shared[P->device];
     S.mu.lock();
-    if (S.used && S.last_stream != stream) (void)hipStreamWaitEvent(stream, S.last, 0);
-}
-NnlsSharedUse::~NnlsSharedUse() {
-    if (!P) return;
-    SharedSlabs &S = g_shared[P->device];
-    (void)hipEventRecord(S.last, stream);
-    S.last_stream = stream;
-    S.used = true;
+    // always waited for once the set has been used: on the same stream the wait costs nothing, and a stream handle equal to the
+    // previous one may belong to a new stream
+    const hipError_t e = S.used ? hipStreamWaitEvent(stream, S.last, 0) : hipSuccess;
+    if (e == hipSuccess) return PNX_OK;
     S.mu.unlock();
+    return set_error(PNX_ERR_HIP, "hipStreamWaitEvent (shared NNLS slabs): %s", hipGetErrorString(e));
+}
+int nnls_shared_release(const NnlsPlanData *P, hipStream_t stream) {
+    SharedSlabs &S = g_shared[P->device];
+    const hipError_t e = hipEventRecord(S.last, stream);
+    if (e == hipSuccess)
+        S.used = true;
+    else
+        (void)hipStreamSynchronize(stream);  // this use is not recorded: it ends here, before the next one can be enqueued
+    S.mu.unlock();
+    if (e != hipSuccess) return set_error(PNX_ERR_HIP, "hipEventRecord (shared NNLS slabs): %s", hipGetErrorString(e));
+    return PNX_OK;
 }
 
-int nnls_plan_init(NnlsPlanData *P, int n_meas, int n_bins, const double *basis, const double *reg, int n_reg,
-                   int device, int cus) {
-    P->device = device;
-    P->cus = cus;
-    P->n_meas = n_meas;
-    P->n_bins = n_bins;
-    P->n_reg = n_reg;
-    if (!toeplitz_band(reg, n_reg, n_bins, P->rc, &P->rhb) || dev_getenv("PNX_NNLS_GENERIC_REG")) P->rhb = 0;
-    {   // reg_order = 0 (the reference's default) is an all-zero matrix: without regulariser rows the Gram form squares a
-        // condition number of ~1e16 -- those fits go through the QR-based kernel
-        bool zero = true;
-        for (size_t i = 0; i < (size_t)n_reg * n_bins && zero; ++i) zero = reg[i] == 0.0;
-        // up to 64 measurements with Q and R in LDS, 65 .. 128 with both in a per-wave global slab (pnx_nnls_qr.hip): never a
-        // silently different algorithm, and since round 4 no refusal either -- the reference's default has no limit on the
-        // number of b-values (nnls_solver.py:37, 88-127)
-        P->qr = zero && !dev_getenv("PNX_NNLS_NO_QR");
-    }
-    // more than 256 bins: the wide instantiations (eight bins per lane) of this file's kernel and of the QR-form kernels; no block
-    // kernel (its LDS copy of the basis would leave room for two voxels per CU), no MFMA Gram step (A^T y on the VALU)
-    const bool wide = n_bins > kNnlsMaxBins;
-    P->bstride = wide ? kNnlsWideBins : kNnlsMaxBins;
+// ---- plans --------------------------------------------------------------------------------------------------------------------
+// reg_order = 0 (the reference's default) is an all-zero matrix: without regulariser rows the Gram form squares a condition number
+// of ~1e16 -- those fits take the QR form, at every size (the reference's default has no limit on the number of b-values,
+// nnls_solver.py:37, 88-127).  The banded regularisers of orders 1-3 take the block kernel while its LDS copy of the basis holds
+// the plan (32 measurements, 256 bins), everything else the Gram form; more than 256 bins: its wide instantiations, whose LDS
+// copy of the basis would leave a block kernel room for two voxels per CU
+static NnlsPath nnls_choose_path(bool zero_reg, int rhb, int n_meas, int n_reg, int n_bins) {
+    if (zero_reg) return NnlsPath::Qr;
+    if (n_bins > kNnlsMaxBins) return NnlsPath::GramWide;
+    if (rhb != 0 && n_meas <= kNnlsBlkMaxMeas && n_reg == n_bins && !dev_getenv("PNX_NNLS_NO_BLK")) return NnlsPath::Blk;
+    return NnlsPath::Gram;
+}
+
+// what the Gram form reads (the block kernel gathers columns of G too): B, reg transposed, G = B^T B + reg^T reg in fp64 with rows
+// padded to bstride columns and one row more (the block kernel gathers column 256 -- its padding bin -- of a row), the work queue
+static int gram_setup(NnlsPlanData *P, const double *basis, const double *reg) {
+    const int n_meas = P->n_meas, n_bins = P->n_bins, n_reg = P->n_reg;
     const size_t bs = (size_t)P->bstride;
-    const size_t nb = (size_t)n_meas * n_bins, nr = (size_t)n_reg * n_bins, ng = (bs + 1) * bs;  // one row more: the block kernel gathers column 256 (its padding bin) of a row
-    for (size_t i = 0; i < nb; ++i)
-        if (!std::isfinite(basis[i])) return set_error(PNX_ERR_INVALID, "basis contains non-finite values");
+    const size_t nb = (size_t)n_meas * n_bins, nr = (size_t)n_reg * n_bins, ng = (bs + 1) * bs;
     PNX_HIPN(hipMalloc(&P->B, nb * sizeof(double)));
-    PNX_HIPN(hipMalloc(&P->Bp, (size_t)n_meas * bs * sizeof(double)));
-    PNX_HIPN(hipMemset(P->Bp, 0, (size_t)n_meas * bs * sizeof(double)));
     PNX_HIPN(hipMalloc(&P->RT, (nr ? nr : 1) * sizeof(double)));
     PNX_HIPN(hipMalloc(&P->G, ng * sizeof(double)));
-    PNX_HIPN(hipMemset(P->G, 0, ng * sizeof(double)));  // rows padded to bstride columns
+    PNX_HIPN(hipMemset(P->G, 0, ng * sizeof(double)));
     PNX_HIPN(hipMalloc(&P->queue, sizeof(unsigned long long)));
     PNX_HIPN(hipMemcpy(P->B, basis, nb * sizeof(double), hipMemcpyHostToDevice));
-    PNX_HIPN(hipMemcpy2D(P->Bp, bs * sizeof(double), basis, (size_t)n_bins * sizeof(double), (size_t)n_bins * sizeof(double), n_meas, hipMemcpyHostToDevice));
     if (nr) {
         std::vector<double> rt(nr);
         for (int i = 0; i < n_reg; ++i)
@@ -978,51 +966,82 @@ int nnls_plan_init(NnlsPlanData *P, int n_meas, int n_bins, const double *basis,
             }
         PNX_HIPN(hipMemcpy(P->RT, rt.data(), nr * sizeof(double), hipMemcpyHostToDevice));
     }
-    hipLaunchKernelGGL(gram_kernel, dim3((n_bins + 63) / 64, n_bins), dim3(64), 0, 0, P->B, P->RT, n_meas, n_bins,
-                       n_reg, P->G, P->bstride);
+    hipLaunchKernelGGL(gram_kernel, dim3((n_bins + 63) / 64, n_bins), dim3(64), 0, 0, P->B, P->RT, n_meas, n_bins, n_reg, P->G, P->bstride);
     PNX_HIPN(hipGetLastError());
-    if (!P->qr && !wide && nnls_blk_applicable(P)) {
-        P->blk = true;
-        const int rc_ = nnls_blk_plan_init(P);
-        if (rc_ != PNX_OK) return rc_;
-    }
-    // persistent grid: as many single-wave workgroups as fit (LDS bound), one scratch slab each
+    return PNX_OK;
+}
+
+// the persistent grid of nnls_kernel whose occupancy `kern` has: as many single-wave workgroups as fit (LDS bound), the slab of
+// rows 48 .. 255 of M for each (256 KB; every first-pass instantiation keeps 256 positions)
+static int gram_grid(NnlsPlanData *P, const void *kern) {
     int occ = 0;
-    if (wide) {
-        PNX_HIPN(hipFuncSetAttribute((const void *)nnls_kernel<8, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)nnls_lds_bytes()));
-        PNX_HIPN(hipFuncSetAttribute((const void *)nnls_kernel<6, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)nnls_lds_bytes()));
-        PNX_HIPN(hipFuncSetAttribute((const void *)nnls_kernel<8, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)nnls_lds_bytes()));
-        if (n_bins <= 6 * kW)
-            PNX_HIPN(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, nnls_kernel<6, 4>, kW, nnls_lds_bytes()));
-        else
-            PNX_HIPN(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, nnls_kernel<8, 4>, kW, nnls_lds_bytes()));
-    } else {
-        PNX_HIPN(hipFuncSetAttribute((const void *)nnls_kernel<4, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)nnls_lds_bytes()));
-        PNX_HIPN(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, nnls_kernel<4, 4>, kW, nnls_lds_bytes()));
-    }
+    PNX_HIPN(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kern, kW, kNnlsLdsBytes));
     if (occ < 1) return set_error(PNX_ERR_HIP, "nnls kernel does not fit on a CU");
-    P->n_waves = occ * cus;
-    P->mglob_stride = glob_tri<4>();  // 256 KB per resident wave: rows 48 .. 255 of M (both first-pass kernels keep 256 positions)
-    // a block-kernel plan runs this kernel on the voxels handed over and, when the pilot of a call finds that too many are (strong
-    // regularisers: supports beyond 128 bins), on the whole call (A^T y on the VALU either way): the full grid of slabs (1 GB),
-    // but no 2 GiB chunk buffer for the Gram step unless pnx_nnls_aty asks for one later
-    if (P->qr) P->n_waves = 1;  // a QR-form plan never launches this kernel
-    if (P->blk) {  // the slabs of the kernels behind the first pass: one set per device (pnx_nnls.hpp)
-        const int rs = nnls_shared_slabs_get(device, nnls_blk4_slab_bytes(P), (size_t)P->n_waves * P->mglob_stride * sizeof(double), &P->Mblk4, &P->Mglob);
-        if (rs != PNX_OK) return rs;
+    P->n_waves = occ * P->cus;
+    P->mglob_stride = glob_tri<4>();
+    return PNX_OK;
+}
+static int lds_attr(const void *kern) {
+    PNX_HIPN(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kNnlsLdsBytes));
+    return PNX_OK;
+}
+
+int nnls_plan_init(NnlsPlanData *P, int n_meas, int n_bins, const double *basis, const double *reg, int n_reg,
+                   int device, int cus) {
+    P->device = device;
+    P->cus = cus;
+    P->n_meas = n_meas;
+    P->n_bins = n_bins;
+    P->n_reg = n_reg;
+    if (!toeplitz_band(reg, n_reg, n_bins, P->rc, &P->rhb)) P->rhb = 0;
+    bool zero = true;
+    for (size_t i = 0; i < (size_t)n_reg * n_bins && zero; ++i) zero = reg[i] == 0.0;
+    P->path = nnls_choose_path(zero, P->rhb, n_meas, n_reg, n_bins);
+
+    // every path: the basis, zero padded to rows of 256 (512) doubles; the MFMA Gram step (pnx_nnls_aty) stages it in LDS, n_meas * 2 KiB
+    P->bstride = n_bins > kNnlsMaxBins ? kNnlsWideBins : kNnlsMaxBins;
+    const size_t bs = (size_t)P->bstride, nb = (size_t)n_meas * n_bins;
+    for (size_t i = 0; i < nb; ++i)
+        if (!std::isfinite(basis[i])) return set_error(PNX_ERR_INVALID, "basis contains non-finite values");
+    PNX_HIPN(hipMalloc(&P->Bp, (size_t)n_meas * bs * sizeof(double)));
+    PNX_HIPN(hipMemset(P->Bp, 0, (size_t)n_meas * bs * sizeof(double)));
+    PNX_HIPN(hipMemcpy2D(P->Bp, bs * sizeof(double), basis, (size_t)n_bins * sizeof(double), (size_t)n_bins * sizeof(double), n_meas, hipMemcpyHostToDevice));
+    P->mfma_ok = n_meas <= 64 && n_bins <= kNnlsMaxBins;
+    if (P->mfma_ok) PNX_HIPN(hipFuncSetAttribute((const void *)nnls_aty_mfma_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+
+    int r = PNX_OK;
+    switch (P->path) {
+    case NnlsPath::Qr:  // the QR-form kernels read Bp, and a slab of their own that the first launch needing it allocates
+        break;
+    case NnlsPath::Blk:
+        // the block kernels, and behind the four-slot one nnls_kernel<4, 4> for what it gives up: the slabs of those two are the
+        // device's shared set (pnx_nnls.hpp)
+        if ((r = gram_setup(P, basis, reg)) || (r = nnls_blk_plan_init(P)) || (r = lds_attr((const void *)nnls_kernel<4, 4>)) ||
+            (r = gram_grid(P, (const void *)nnls_kernel<4, 4>)))
+            return r;
+        if ((r = nnls_shared_slabs_get(device, nnls_blk4_slab_bytes(P), (size_t)P->n_waves * P->mglob_stride * sizeof(double), &P->Mblk4, &P->Mglob)))
+            return r;
         P->shared_slabs = true;
-    } else
+        break;
+    case NnlsPath::Gram:  // nnls_kernel<4, 4>, behind the MFMA Gram step up to 64 measurements (2 GiB of A^T y per chunk)
+        if ((r = gram_setup(P, basis, reg)) || (r = lds_attr((const void *)nnls_kernel<4, 4>)) || (r = gram_grid(P, (const void *)nnls_kernel<4, 4>)))
+            return r;
         PNX_HIPN(hipMalloc(&P->Mglob, (size_t)P->n_waves * P->mglob_stride * sizeof(double)));
-    if (wide && !P->qr) {  // the hand-over pass of a wide plan (passive sets beyond 256 positions): one wave per CU, 1 MB of slab each
+        if (P->mfma_ok) PNX_HIPN(hipMalloc(&P->aty, (size_t)kAtyChunk * kNnlsMaxBins * sizeof(double)));
+        break;
+    case NnlsPath::GramWide:
+        // first pass nnls_kernel<6, 4> (up to 384 bins) or <8, 4>; the hand-over pass <8, 8> (passive sets beyond 256 positions):
+        // one wave per CU, 1 MB of slab each
+        if ((r = gram_setup(P, basis, reg)) || (r = lds_attr((const void *)nnls_kernel<8, 4>)) || (r = lds_attr((const void *)nnls_kernel<6, 4>)) ||
+            (r = lds_attr((const void *)nnls_kernel<8, 8>)) ||
+            (r = gram_grid(P, n_bins <= 6 * kW ? (const void *)nnls_kernel<6, 4> : (const void *)nnls_kernel<8, 4>)))
+            return r;
+        PNX_HIPN(hipMalloc(&P->Mglob, (size_t)P->n_waves * P->mglob_stride * sizeof(double)));
         P->wide_waves = cus;
         PNX_HIPN(hipMalloc(&P->Mwide, (size_t)P->wide_waves * glob_tri<8>() * sizeof(double)));
         P->blk_bail_cap = (size_t)kAtyChunk;
         PNX_HIPN(hipMalloc(&P->blk_bail, (P->blk_bail_cap + 1) * sizeof(int32_t)));
-    }
-    P->mfma_ok = !dev_getenv("PNX_NNLS_NO_MFMA") && n_meas <= 64 && !wide;  // LDS stage of Bp: n_meas * 2 KiB
-    if (P->mfma_ok) {
-        if (!P->blk) PNX_HIPN(hipMalloc(&P->aty, (size_t)kAtyChunk * kNnlsMaxBins * sizeof(double)));
-        PNX_HIPN(hipFuncSetAttribute((const void *)nnls_aty_mfma_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        break;
     }
     PNX_HIPN(hipDeviceSynchronize());
     return PNX_OK;
@@ -1050,115 +1069,16 @@ void nnls_plan_free(NnlsPlanData *P) {
     *P = NnlsPlanData();
 }
 
-int nnls_solve_device(NnlsPlanData *P, int64_t n_vox, const double *y_d, int max_iter, double *coeff_d,
-                      double *rnorm_d, int8_t *status_d, int32_t *iters_d, hipStream_t stream) {
-    // Voxels go through in chunks of kAtyChunk: the MFMA Gram step fills ATY for the chunk, the persistent
-    // active-set kernel consumes it (256 voxels per resident wave at full occupancy keep the drain tail small; 2 GiB of ATY scratch).
-    if (P->qr) return nnls_qr_solve_device(P, n_vox, y_d, max_iter, coeff_d, rnorm_d, status_d, iters_d, stream);
-    if (P->blk) return nnls_blk_solve_device(P, n_vox, y_d, max_iter, coeff_d, rnorm_d, status_d, iters_d, stream);
-    const bool use_mfma = P->aty != nullptr;
-    for (int64_t off = 0; off < n_vox; off += kAtyChunk) {
-        const int64_t c = (n_vox - off) < kAtyChunk ? (n_vox - off) : kAtyChunk;
-        NnlsArgs a;
-        a.y = y_d + (size_t)off * P->n_meas;
-        a.coeff = coeff_d + (size_t)off * P->n_bins;
-        a.rnorm = rnorm_d + off;
-        a.status = status_d ? status_d + off : nullptr;
-        a.iters = iters_d ? iters_d + off : nullptr;
-        a.G = P->G;
-        a.Bp = P->Bp;
-        a.RT = P->RT;
-        a.aty = use_mfma ? P->aty : nullptr;
-        a.Mglob = P->Mglob;
-        a.queue = P->queue;
-        a.n_vox = c;
-        a.n_meas = P->n_meas;
-        a.n_bins = P->n_bins;
-        a.n_reg = P->n_reg;
-        a.max_iter = max_iter;
-        for (int k = 0; k < 5; ++k) a.rc[k] = P->rc[k];
-        a.rhb = P->rhb;
-        a.redo_list = a.redo_count = nullptr;
-        a.bail = nullptr;
-        if (use_mfma) {
-            const int kpad = (P->n_meas + 3) & ~3;
-            const size_t lds = (size_t)kpad * kNnlsMaxBins * sizeof(double);
-            const long long strips = (c + 15) / 16;
-            long long grid = (strips + kAtyWaves - 1) / kAtyWaves;
-            const long long cap = (long long)P->cus * 2;
-            if (grid > cap) grid = cap;
-            hipLaunchKernelGGL(nnls_aty_mfma_kernel, dim3((unsigned)grid), dim3(kAtyWaves * 64), lds, stream, a.y, P->Bp, P->aty,
-                               (long long)c, P->n_meas);
-            PNX_HIPN(hipGetLastError());
-        }
-        PNX_HIPN(hipMemsetAsync(P->queue, 0, sizeof(unsigned long long), stream));
-        long long grid = c < P->n_waves ? c : P->n_waves;
-        if (P->bstride == kNnlsWideBins) {
-            // first pass: 256 positions per voxel; the voxels that want more go to the list and through <8, 8> right behind it
-            // (stream order; the count stays on the device: an empty list costs the second launch one queue pull per wave)
-            a.bail = P->blk_bail;
-            PNX_HIPN(hipMemsetAsync(P->blk_bail, 0, sizeof(int32_t), stream));
-            if (P->n_bins <= 6 * kW)
-                hipLaunchKernelGGL((nnls_kernel<6, 4>), dim3((unsigned)grid), dim3(kW), nnls_lds_bytes(), stream, a);
-            else
-                hipLaunchKernelGGL((nnls_kernel<8, 4>), dim3((unsigned)grid), dim3(kW), nnls_lds_bytes(), stream, a);
-            PNX_HIPN(hipGetLastError());
-            PNX_HIPN(hipMemsetAsync(P->queue, 0, sizeof(unsigned long long), stream));
-            a.bail = nullptr;
-            a.redo_list = P->blk_bail + 1;
-            a.redo_count = P->blk_bail;
-            a.Mglob = P->Mwide;
-            long long g2 = c < P->wide_waves ? c : P->wide_waves;
-            hipLaunchKernelGGL((nnls_kernel<8, 8>), dim3((unsigned)g2), dim3(kW), nnls_lds_bytes(), stream, a);
-        } else
-            hipLaunchKernelGGL((nnls_kernel<4, 4>), dim3((unsigned)grid), dim3(kW), nnls_lds_bytes(), stream, a);
-        PNX_HIPN(hipGetLastError());
-    }
-    return PNX_OK;
-}
-
-int nnls_redo_device(NnlsPlanData *P, int64_t n_vox, const double *y_d, int max_iter, double *coeff_d, double *rnorm_d,
-                     int8_t *status_d, int32_t *iters_d, const int32_t *list, const int32_t *count, hipStream_t stream) {
+// the arguments of an nnls_kernel launch over the voxels [off, off + n_vox) of a call: A^T y on the VALU, the plan's first-pass
+// slabs, no voxel lists
+static NnlsArgs nnls_args(const NnlsPlanData *P, int64_t off, int64_t n_vox, const double *y, int max_iter, double *coeff, double *rnorm,
+                          int8_t *status, int32_t *iters) {
     NnlsArgs a;
-    a.y = y_d;
-    a.coeff = coeff_d;
-    a.rnorm = rnorm_d;
-    a.status = status_d;
-    a.iters = iters_d;
-    a.G = P->G;
-    a.Bp = P->Bp;
-    a.RT = P->RT;
-    a.aty = nullptr;
-    a.Mglob = P->Mglob;
-    a.queue = P->queue;
-    a.n_vox = n_vox;
-    a.n_meas = P->n_meas;
-    a.n_bins = P->n_bins;
-    a.n_reg = P->n_reg;
-    a.max_iter = max_iter;
-    for (int k = 0; k < 5; ++k) a.rc[k] = P->rc[k];
-    a.rhb = P->rhb;
-    a.redo_list = list;
-    a.redo_count = count;
-    a.bail = nullptr;
-    NnlsSharedUse use(P, stream);  // block-kernel plans: Mglob is the device's shared slab
-    PNX_HIPN(hipMemsetAsync(P->queue, 0, sizeof(unsigned long long), stream));
-    // the plan's persistent grid: with an empty list a wave costs one queue pull
-    long long grid = P->n_waves;
-    if (grid > n_vox) grid = n_vox;
-    hipLaunchKernelGGL((nnls_kernel<4, 4>), dim3((unsigned)grid), dim3(kW), nnls_lds_bytes(), stream, a);  // block-kernel plans only: never wide
-    PNX_HIPN(hipGetLastError());
-    return PNX_OK;
-}
-
-int nnls_routed_device(NnlsPlanData *P, int64_t n_vox, const double *y_d, int max_iter, double *coeff_d, double *rnorm_d,
-                       int8_t *status_d, int32_t *iters_d, const int32_t *route, hipStream_t stream) {
-    NnlsArgs a;
-    a.y = y_d;
-    a.coeff = coeff_d;
-    a.rnorm = rnorm_d;
-    a.status = status_d;
-    a.iters = iters_d;
+    a.y = y + (size_t)off * P->n_meas;
+    a.coeff = coeff + (size_t)off * P->n_bins;
+    a.rnorm = rnorm + off;
+    a.status = status ? status + off : nullptr;
+    a.iters = iters ? iters + off : nullptr;
     a.G = P->G;
     a.Bp = P->Bp;
     a.RT = P->RT;
@@ -1174,30 +1094,90 @@ int nnls_routed_device(NnlsPlanData *P, int64_t n_vox, const double *y_d, int ma
     a.rhb = P->rhb;
     a.redo_list = a.redo_count = nullptr;
     a.bail = nullptr;
-    a.route = route;
-    NnlsSharedUse use(P, stream);
-    PNX_HIPN(hipMemsetAsync(P->queue, 0, sizeof(unsigned long long), stream));
-    long long grid = P->n_waves;
-    if (grid > n_vox) grid = n_vox;
-    hipLaunchKernelGGL((nnls_kernel<4, 4>), dim3((unsigned)grid), dim3(kW), nnls_lds_bytes(), stream, a);  // block-kernel plans only: never wide
-    PNX_HIPN(hipGetLastError());
-    return PNX_OK;
+    return a;
 }
 
-int nnls_aty_device(NnlsPlanData *P, int64_t n_vox, const double *y_d, double *aty_d, hipStream_t stream) {
-    if (!P->mfma_ok) return set_error(PNX_ERR_UNSUPPORTED, "the MFMA Gram step is disabled for this plan (n_meas=%d)", P->n_meas);
-    if (!aty_d && !P->aty) PNX_HIPN(hipMalloc(&P->aty, (size_t)kAtyChunk * kNnlsMaxBins * sizeof(double)));  // first use by a block-kernel plan
-    if (n_vox > kAtyChunk) return set_error(PNX_ERR_INVALID, "n_vox=%lld > %lld per call", (long long)n_vox, (long long)kAtyChunk);
+// ATY (n_vox, 256) = Y Bp on the matrix cores, n_vox <= kAtyChunk: Bp (n_meas rounded up to the four of an MFMA step) in LDS, at
+// most two workgroups per CU
+static int launch_aty(const NnlsPlanData *P, int64_t n_vox, const double *y, double *aty, hipStream_t stream) {
     const int kpad = (P->n_meas + 3) & ~3;
     const size_t lds = (size_t)kpad * kNnlsMaxBins * sizeof(double);
     const long long strips = (n_vox + 15) / 16;
     long long grid = (strips + kAtyWaves - 1) / kAtyWaves;
     const long long cap = (long long)P->cus * 2;
     if (grid > cap) grid = cap;
-    hipLaunchKernelGGL(nnls_aty_mfma_kernel, dim3((unsigned)grid), dim3(kAtyWaves * 64), lds, stream, y_d, P->Bp, aty_d ? aty_d : P->aty,
-                       (long long)n_vox, P->n_meas);
+    hipLaunchKernelGGL(nnls_aty_mfma_kernel, dim3((unsigned)grid), dim3(kAtyWaves * 64), lds, stream, y, P->Bp, aty, (long long)n_vox, P->n_meas);
     PNX_HIPN(hipGetLastError());
     return PNX_OK;
+}
+
+int nnls_solve_device(NnlsPlanData *P, int64_t n_vox, const double *y_d, int max_iter, double *coeff_d,
+                      double *rnorm_d, int8_t *status_d, int32_t *iters_d, hipStream_t stream) {
+    switch (P->path) {
+    case NnlsPath::Qr:
+        return nnls_qr_solve_device(P, n_vox, y_d, max_iter, coeff_d, rnorm_d, status_d, iters_d, stream);
+    case NnlsPath::Blk:
+        return nnls_blk_solve_device(P, n_vox, y_d, max_iter, coeff_d, rnorm_d, status_d, iters_d, stream);
+    case NnlsPath::Gram:
+    case NnlsPath::GramWide:
+        break;
+    }
+    // Voxels go through in chunks of kAtyChunk: the MFMA Gram step fills ATY for the chunk, the persistent
+    // active-set kernel consumes it (256 voxels per resident wave at full occupancy keep the drain tail small; 2 GiB of ATY scratch).
+    for (int64_t off = 0; off < n_vox; off += kAtyChunk) {
+        const int64_t c = (n_vox - off) < kAtyChunk ? (n_vox - off) : kAtyChunk;
+        NnlsArgs a = nnls_args(P, off, c, y_d, max_iter, coeff_d, rnorm_d, status_d, iters_d);
+        if (P->mfma_ok) {  // Gram plans only (a wide one has none)
+            a.aty = P->aty;
+            const int r = launch_aty(P, c, a.y, P->aty, stream);
+            if (r) return r;
+        }
+        PNX_HIPN(hipMemsetAsync(P->queue, 0, sizeof(unsigned long long), stream));
+        const long long grid = c < P->n_waves ? c : P->n_waves;
+        if (P->path == NnlsPath::GramWide) {
+            // first pass: 256 positions per voxel; the voxels that want more go to the list and through <8, 8> right behind it
+            // (stream order; the count stays on the device: an empty list costs the second launch one queue pull per wave)
+            a.bail = P->blk_bail;
+            PNX_HIPN(hipMemsetAsync(P->blk_bail, 0, sizeof(int32_t), stream));
+            if (P->n_bins <= 6 * kW)
+                hipLaunchKernelGGL((nnls_kernel<6, 4>), dim3((unsigned)grid), dim3(kW), kNnlsLdsBytes, stream, a);
+            else
+                hipLaunchKernelGGL((nnls_kernel<8, 4>), dim3((unsigned)grid), dim3(kW), kNnlsLdsBytes, stream, a);
+            PNX_HIPN(hipGetLastError());
+            PNX_HIPN(hipMemsetAsync(P->queue, 0, sizeof(unsigned long long), stream));
+            a.bail = nullptr;
+            a.redo_list = P->blk_bail + 1;
+            a.redo_count = P->blk_bail;
+            a.Mglob = P->Mwide;
+            const long long g2 = c < P->wide_waves ? c : P->wide_waves;
+            hipLaunchKernelGGL((nnls_kernel<8, 8>), dim3((unsigned)g2), dim3(kW), kNnlsLdsBytes, stream, a);
+        } else
+            hipLaunchKernelGGL((nnls_kernel<4, 4>), dim3((unsigned)grid), dim3(kW), kNnlsLdsBytes, stream, a);
+        PNX_HIPN(hipGetLastError());
+    }
+    return PNX_OK;
+}
+
+int nnls_redo_device(NnlsPlanData *P, int64_t n_vox, const double *y_d, int max_iter, double *coeff_d, double *rnorm_d,
+                     int8_t *status_d, int32_t *iters_d, const int32_t *list, const int32_t *count, hipStream_t stream) {
+    NnlsArgs a = nnls_args(P, 0, n_vox, y_d, max_iter, coeff_d, rnorm_d, status_d, iters_d);
+    a.redo_list = list;
+    a.redo_count = count;
+    return nnls_shared_use(P, stream, [&]() -> int {  // Mglob of a block-kernel plan is the device's shared slab
+        PNX_HIPN(hipMemsetAsync(P->queue, 0, sizeof(unsigned long long), stream));
+        // the plan's persistent grid: with an empty list a wave costs one queue pull
+        const long long grid = n_vox < P->n_waves ? n_vox : P->n_waves;
+        hipLaunchKernelGGL((nnls_kernel<4, 4>), dim3((unsigned)grid), dim3(kW), kNnlsLdsBytes, stream, a);  // block-kernel plans only: never wide
+        PNX_HIPN(hipGetLastError());
+        return PNX_OK;
+    });
+}
+
+int nnls_aty_device(NnlsPlanData *P, int64_t n_vox, const double *y_d, double *aty_d, hipStream_t stream) {
+    if (!P->mfma_ok) return set_error(PNX_ERR_UNSUPPORTED, "the MFMA Gram step is disabled for this plan (n_meas=%d)", P->n_meas);
+    if (n_vox > kAtyChunk) return set_error(PNX_ERR_INVALID, "n_vox=%lld > %lld per call", (long long)n_vox, (long long)kAtyChunk);
+    if (!aty_d && !P->aty) PNX_HIPN(hipMalloc(&P->aty, (size_t)kAtyChunk * kNnlsMaxBins * sizeof(double)));  // first use by a QR-form or block-kernel plan
+    return launch_aty(P, n_vox, y_d, aty_d ? aty_d : P->aty, stream);
 }
 
 int nnls_build_basis(int n_meas, const double *b, int n_bins, const double *bins, double *basis) {

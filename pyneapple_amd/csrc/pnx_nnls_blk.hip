@@ -98,30 +98,20 @@
 
 namespace pnx {
 
-#define PNX_HIPB(call)                                                                             \
-    do {                                                                                           \
-        hipError_t e__ = (call);                                                                   \
-        if (e__ != hipSuccess) return set_error(PNX_ERR_HIP, "%s: %s", #call, hipGetErrorString(e__)); \
-    } while (0)
-
-bool nnls_blk_applicable(const NnlsPlanData *P) {
-    return P->rhb != 0 && P->n_meas <= blk2::kBMeas && P->n_reg == P->n_bins && !dev_getenv("PNX_NNLS_NO_BLK");
-}
-
 // scratch of the block kernels: one workgroup per CU, Variant::mslab doubles of M per wave (zero initialised: the block sweeps
 // read whole blocks, also rows no voxel of this wave has written yet).  slab == nullptr: the grid only (the four-slot kernel's
 // slabs are the device's shared set, pnx_nnls.hpp)
 template <class V> static int blk_variant_init(const NnlsPlanData *P, int *groups, double **slab) {
-    PNX_HIPB(hipFuncSetAttribute(V::kernel(), hipFuncAttributeMaxDynamicSharedMemorySize, (int)V::lds_bytes()));
-    if (V::kernel_hook()) PNX_HIPB(hipFuncSetAttribute(V::kernel_hook(), hipFuncAttributeMaxDynamicSharedMemorySize, (int)V::lds_bytes()));
+    PNX_HIPN(hipFuncSetAttribute(V::kernel(), hipFuncAttributeMaxDynamicSharedMemorySize, (int)V::lds_bytes()));
+    if (V::kernel_hook()) PNX_HIPN(hipFuncSetAttribute(V::kernel_hook(), hipFuncAttributeMaxDynamicSharedMemorySize, (int)V::lds_bytes()));
     int occ = 0;
-    PNX_HIPB(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, V::kernel(), V::waves * kW, V::lds_bytes()));
+    PNX_HIPN(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, V::kernel(), V::waves * kW, V::lds_bytes()));
     if (occ < 1) return set_error(PNX_ERR_HIP, "nnls block kernel does not fit on a CU");
     *groups = occ * P->cus;
     if (!slab) return PNX_OK;
     const size_t bytes = (size_t)*groups * V::waves * V::mslab * sizeof(double);
-    PNX_HIPB(hipMalloc(slab, bytes));
-    PNX_HIPB(hipMemset(*slab, 0, bytes));
+    PNX_HIPN(hipMalloc(slab, bytes));
+    PNX_HIPN(hipMemset(*slab, 0, bytes));
     return PNX_OK;
 }
 size_t nnls_blk4_slab_bytes(const NnlsPlanData *P) { return (size_t)P->blk4_groups * blk4::Variant::waves * blk4::Variant::mslab * sizeof(double); }
@@ -130,10 +120,10 @@ int nnls_blk_plan_init(NnlsPlanData *P) {
     if ((r = blk_variant_init<blk2::Variant>(P, &P->blk_groups, &P->Mblk))) return r;
     if ((r = blk_variant_init<blk4::Variant>(P, &P->blk4_groups, nullptr))) return r;
     P->blk_bail_cap = (size_t)kAtyChunk;
-    PNX_HIPB(hipMalloc(&P->blk_bail, (1 + P->blk_bail_cap) * sizeof(int32_t)));   // [0]: count, [1 ..]: voxel indices
-    PNX_HIPB(hipMalloc(&P->blk4_bail, (1 + P->blk_bail_cap) * sizeof(int32_t)));  // the same for what blk4 hands to the Gram-form kernel
-    PNX_HIPB(hipMalloc(&P->route, sizeof(int32_t)));
-    PNX_HIPB(hipMemset(P->route, 0, sizeof(int32_t)));
+    PNX_HIPN(hipMalloc(&P->blk_bail, (1 + P->blk_bail_cap) * sizeof(int32_t)));   // [0]: count, [1 ..]: voxel indices
+    PNX_HIPN(hipMalloc(&P->blk4_bail, (1 + P->blk_bail_cap) * sizeof(int32_t)));  // the same for what blk4 hands to the Gram-form kernel
+    PNX_HIPN(hipMalloc(&P->route, sizeof(int32_t)));
+    PNX_HIPN(hipMemset(P->route, 0, sizeof(int32_t)));
     return PNX_OK;
 }
 
@@ -212,24 +202,24 @@ static int blk_launch(const BlkCall &C, int64_t off, int64_t c, long long vox_ba
     a.route_want = route_want;
     a.redo_list = list;
     a.redo_count = count;
-    NnlsSharedUse use(V::max_pos == 128 ? nullptr : P, C.stream);  // the four-slot kernel's slabs are the device's shared set
-    PNX_HIPB(hipMemsetAsync(P->queue, 0, sizeof(unsigned long long), C.stream));
-    const int groups = V::max_pos == 128 ? P->blk_groups : P->blk4_groups;
-    long long grid = (c + V::waves - 1) / V::waves;
-    if (grid > groups) grid = groups;
-    V::launch(dim3((unsigned)grid), V::lds_bytes(), C.stream, a);
-    PNX_HIPB(hipGetLastError());
-    return PNX_OK;
+    auto enqueue = [&]() -> int {
+        PNX_HIPN(hipMemsetAsync(P->queue, 0, sizeof(unsigned long long), C.stream));
+        const int groups = V::max_pos == 128 ? P->blk_groups : P->blk4_groups;
+        long long grid = (c + V::waves - 1) / V::waves;
+        if (grid > groups) grid = groups;
+        V::launch(dim3((unsigned)grid), V::lds_bytes(), C.stream, a);
+        PNX_HIPN(hipGetLastError());
+        return PNX_OK;
+    };
+    return V::max_pos == 128 ? enqueue() : nnls_shared_use(P, C.stream, enqueue);  // the four-slot kernel's slabs are the device's shared set
 }
 
 // The voxels list[0 .. min(*count, n_vox)) of a call through blk4 (every passive set of a 256-bin plan fits its 256 positions);
 // what blk4 itself gives up (a ninth rejected candidate in one outer iteration: test hook only) goes to the Gram-form kernel.
 int nnls_blk_redo_device(NnlsPlanData *P, int64_t n_vox, const double *y_d, int max_iter, double *coeff_d, double *rnorm_d,
                          int8_t *status_d, int32_t *iters_d, const int32_t *list, const int32_t *count, hipStream_t stream) {
-    if (dev_getenv("PNX_BLK_NO_WIDE"))  // (A/B) the round-4 hand-over target
-        return nnls_redo_device(P, n_vox, y_d, max_iter, coeff_d, rnorm_d, status_d, iters_d, list, count, stream);
     const BlkCall C{P, y_d, coeff_d, rnorm_d, status_d, iters_d, max_iter, stream};
-    PNX_HIPB(hipMemsetAsync(P->blk4_bail, 0, sizeof(int32_t), stream));
+    PNX_HIPN(hipMemsetAsync(P->blk4_bail, 0, sizeof(int32_t), stream));
     int r = blk_launch<blk4::Variant>(C, 0, n_vox, 0, P->blk4_bail, P->blk4_bail + 1, nullptr, 0, list, count);
     if (r) return r;
     return nnls_redo_device(P, n_vox, y_d, max_iter, coeff_d, rnorm_d, status_d, iters_d, P->blk4_bail + 1, P->blk4_bail, stream);
@@ -244,58 +234,44 @@ int nnls_blk_solve_device(NnlsPlanData *P, int64_t n_vox, const double *y_d, int
         (void)hipFree(P->blk4_bail);
         P->blk_bail = P->blk4_bail = nullptr;
         P->blk_bail_cap = (size_t)n_vox;
-        PNX_HIPB(hipMalloc(&P->blk_bail, (1 + P->blk_bail_cap) * sizeof(int32_t)));
-        PNX_HIPB(hipMalloc(&P->blk4_bail, (1 + P->blk_bail_cap) * sizeof(int32_t)));
+        PNX_HIPN(hipMalloc(&P->blk_bail, (1 + P->blk_bail_cap) * sizeof(int32_t)));
+        PNX_HIPN(hipMalloc(&P->blk4_bail, (1 + P->blk_bail_cap) * sizeof(int32_t)));
     }
-    if (!defer) PNX_HIPB(hipMemsetAsync(P->blk_bail, 0, sizeof(int32_t), stream));
+    if (!defer) PNX_HIPN(hipMemsetAsync(P->blk_bail, 0, sizeof(int32_t), stream));
     const BlkCall C{P, y_d, coeff_d, rnorm_d, status_d, iters_d, max_iter, stream};
     int32_t *n_bail = defer ? defer->counters : P->blk_bail, *bail = defer ? defer->bail : P->blk_bail + 1;
     const long long base = defer ? defer->base : 0;
-    // ONE launch for the rest of the call: the kernel needs no per-chunk buffer (A^T y is never formed), and every launch ends in
-    // a drain tail of ~1.4 ms (C4 volume: 488.2 ms in four launches of 2^20 voxels, 484.1 ms in one; PNX_BLK_CHUNK_LOG2 = 20
-    // brings the launches of kAtyChunk voxels back)
-    int64_t chunk = n_vox;
-    if (const char *t = dev_getenv("PNX_BLK_CHUNK_LOG2")) {
-        const int l2 = atoi(t);
-        if (l2 >= 10 && l2 <= 30) chunk = (int64_t)1 << l2;
-    }
     // the pilot (see blk_route_kernel): in the first chunk of a call; the later chunks of a host-array call follow its route
     // (they run on the same stream, behind it)
     int permille = 150;  // the two-pass plan (blk2, then blk4 for what it hands over) against one pass of blk4, by share handed over: equal at ~14 % (profiles/nnls_mu_probe.py)
     if (const char *t = dev_getenv("PNX_BLK_ROUTE_PERMILLE")) permille = atoi(t);  // <= 0: no pilot, blk2 first for everything
-    const bool wide_route = !dev_getenv("PNX_BLK_NO_WIDE");
     const bool first = !defer || defer->base == 0;
     const int64_t pilot = (permille > 0 && first && n_vox >= 4 * kBlkPilot) ? kBlkPilot : 0;
     const int32_t *route = nullptr;
-    if (permille > 0 && defer && first && !pilot) PNX_HIPB(hipMemsetAsync(P->route, 0, sizeof(int32_t), stream));  // a short first chunk: blk2
+    if (permille > 0 && defer && first && !pilot) PNX_HIPN(hipMemsetAsync(P->route, 0, sizeof(int32_t), stream));  // a short first chunk: blk2
     if (permille > 0 && (pilot || (defer && !first))) route = P->route;
     int r;
     if (pilot) {
         if ((r = blk_launch<blk2::Variant>(C, 0, pilot, base, n_bail, bail, nullptr, 0, nullptr, nullptr))) return r;
         hipLaunchKernelGGL(blk_route_kernel, dim3(1), dim3(1), 0, stream, n_bail, (int)pilot, permille, P->route);
-        PNX_HIPB(hipGetLastError());
+        PNX_HIPN(hipGetLastError());
         if (dev_getenv("PNX_BLK_ROUTE_DEBUG")) {  // diagnostic (synchronises): what the pilot saw
             int32_t cnt = 0, rt = 0;
-            PNX_HIPB(hipStreamSynchronize(stream));
-            PNX_HIPB(hipMemcpy(&cnt, n_bail, sizeof(cnt), hipMemcpyDeviceToHost));
-            PNX_HIPB(hipMemcpy(&rt, P->route, sizeof(rt), hipMemcpyDeviceToHost));
+            PNX_HIPN(hipStreamSynchronize(stream));
+            PNX_HIPN(hipMemcpy(&cnt, n_bail, sizeof(cnt), hipMemcpyDeviceToHost));
+            PNX_HIPN(hipMemcpy(&rt, P->route, sizeof(rt), hipMemcpyDeviceToHost));
             fprintf(stderr, "pnx nnls pilot: %d of %d voxels handed over (%.1f %%), threshold %.1f %% -> %s\n", cnt, (int)pilot, 100.0 * cnt / (double)pilot,
-                    permille / 10.0, rt ? (wide_route ? "four-slot block kernel" : "Gram-form kernel") : "block kernel");
+                    permille / 10.0, rt ? "four-slot block kernel" : "block kernel");
         }
     }
-    for (int64_t off = pilot; off < n_vox; off += chunk) {
-        const int64_t c = (n_vox - off) < chunk ? (n_vox - off) : chunk;
-        if ((r = blk_launch<blk2::Variant>(C, off, c, base + off, n_bail, bail, route, 0, nullptr, nullptr))) return r;
-    }
-    if (route) {  // the same voxels through the other kernel -- which leaves at once unless the pilot chose it
-        if (wide_route) {
-            PNX_HIPB(hipMemsetAsync(P->blk4_bail, 0, sizeof(int32_t), stream));
-            if ((r = blk_launch<blk4::Variant>(C, pilot, n_vox - pilot, pilot, P->blk4_bail, P->blk4_bail + 1, route, 1, nullptr, nullptr))) return r;
-            // what blk4 gives up (test hook only): the Gram-form kernel, indices relative to this call's arrays
-            if ((r = nnls_redo_device(P, n_vox, y_d, max_iter, coeff_d, rnorm_d, status_d, iters_d, P->blk4_bail + 1, P->blk4_bail, stream))) return r;
-        } else if ((r = nnls_routed_device(P, n_vox - pilot, y_d + (size_t)pilot * P->n_meas, max_iter, coeff_d + (size_t)pilot * P->n_bins, rnorm_d + pilot,
-                                           status_d ? status_d + pilot : nullptr, iters_d ? iters_d + pilot : nullptr, route, stream)))
-            return r;
+    // ONE launch for the rest of the call: the kernel needs no per-chunk buffer (A^T y is never formed), and every launch ends in
+    // a drain tail of ~1.4 ms (C4 volume: 488.2 ms in four launches of 2^20 voxels, 484.1 ms in one)
+    if ((r = blk_launch<blk2::Variant>(C, pilot, n_vox - pilot, base + pilot, n_bail, bail, route, 0, nullptr, nullptr))) return r;
+    if (route) {  // the same voxels through blk4 -- which leaves at once unless the pilot chose it
+        PNX_HIPN(hipMemsetAsync(P->blk4_bail, 0, sizeof(int32_t), stream));
+        if ((r = blk_launch<blk4::Variant>(C, pilot, n_vox - pilot, pilot, P->blk4_bail, P->blk4_bail + 1, route, 1, nullptr, nullptr))) return r;
+        // what blk4 gives up (test hook only): the Gram-form kernel, indices relative to this call's arrays
+        if ((r = nnls_redo_device(P, n_vox, y_d, max_iter, coeff_d, rnorm_d, status_d, iters_d, P->blk4_bail + 1, P->blk4_bail, stream))) return r;
     }
     // voxels whose passive set outgrew blk2 (about one in 10^4 on the reference workload, and the slowest ones: a single
     // launch for the whole call, so that their long solves overlap): blk4, from scratch
@@ -305,7 +281,7 @@ int nnls_blk_solve_device(NnlsPlanData *P, int64_t n_vox, const double *y_d, int
         // they are the longest solves there are)
         hipLaunchKernelGGL(bail_gather_kernel, dim3(1), dim3(256), 0, stream, defer->counters, defer->bail, y_d, (long long)defer->base,
                            P->n_meas, defer->y_side, defer->cap);
-        PNX_HIPB(hipGetLastError());
+        PNX_HIPN(hipGetLastError());
         return PNX_OK;
     }
     return nnls_blk_redo_device(P, n_vox, y_d, max_iter, coeff_d, rnorm_d, status_d, iters_d, P->blk_bail + 1, P->blk_bail, stream);

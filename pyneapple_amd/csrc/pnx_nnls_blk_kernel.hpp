@@ -4,7 +4,7 @@
 namespace pnx {
 namespace PNX_BLK_NS {
 
-constexpr int kBMeas = 32;                  // measurements the LDS copy of the basis holds
+constexpr int kBMeas = kNnlsBlkMaxMeas;     // measurements the LDS copy of the basis holds
 constexpr int kBStride = kNnlsMaxBins + 2;  // even: rows stay 16-byte aligned for ds_read_b128; a column gather (lane = measurement) is 2-way bank conflicted
 constexpr int kBlkWaves = PNX_BLK_WAVES;    // waves per workgroup = voxels in flight per CU (12: 168 registers per wave, no scratch; 16 waves at 128
                                             // registers measured 7.2 against 8.2 M voxels/s; the four-slot instantiation: 8 waves, 256 registers)
@@ -452,9 +452,6 @@ __device__ __forceinline__ double bx_gather(const double *Bl, const double *xbuf
 // rows >= n_meas of the LDS basis are zero: the product stops at `mrows` = n_meas rounded up to the eight rows of a loop step
 typedef double dbl2v __attribute__((ext_vector_type(2)));
 typedef __attribute__((address_space(1))) const dbl2v glb_cdbl2v;
-#ifndef PNX_BLK_DIET
-#define PNX_BLK_DIET 1  // round 5, instruction diet of the dual (0: as before; A/B builds)
-#endif
 // `between` runs behind the first eight row reads and leaves in `start` what the sums start from (the negated regulariser term of the
 // dual: four subtractions behind the product become none)
 template <class F>
@@ -469,7 +466,7 @@ __device__ __forceinline__ void bt_times_h(const double *Bl, const double *v, in
     }
     between();
 #pragma unroll
-    for (int s = 0; s < kSlots; ++s) out[s] = PNX_BLK_DIET ? -start[s] : 0.0;
+    for (int s = 0; s < kSlots; ++s) out[s] = -start[s];
 #pragma unroll 1
     for (int m = 0; m < mrows; m += 8) {
         const double *nx = col + (m + 4) * kBStride;
@@ -512,9 +509,6 @@ __device__ __forceinline__ void bt_times_h(const double *Bl, const double *v, in
 }
 // w = B^T (y - B_P x_P) - R^T (R x), all out of LDS.  LDS round trips in sequence: bins of the first positions -> column
 // gathers (one per 16 positions) -> B^T r; the stencil of R rides on the first gathers, the one of R^T on the first row reads.
-#ifndef PNX_BLK_RTR
-#define PNX_BLK_RTR 1  // half bandwidth 1 (orders 1 and 2): R^T (R x) as one five-point stencil of x (0: two three-point passes through LDS; A/B builds)
-#endif
 // the pair of bins at the centre of w: sum_e g[|e|] x[j + e], e = -2 .. 2
 __device__ __forceinline__ void rtr_eval(const Win &w, double g0, double g1, double g2, double &o0, double &o1) {
     double a = g2 * w.lo.x, b = g2 * w.lo.y;
@@ -539,7 +533,7 @@ __device__ __forceinline__ void dual_residual_form(const double *Bl, double *xbu
     // Half bandwidth 1 (orders 1 and 2): (R^T R x)_j = rg[2] (x_{j-2} + x_{j+2}) + rg[1] (x_{j-1} + x_{j+1}) + rg[0] x_j, minus what the rows
     // -1 and n -- which R does not have -- would have added to the bins 0 and n - 1 (x is zero outside [0, n)): one stencil of x, no
     // second pass, no round trip of t through LDS.  Half bandwidth 2 (order 3): t = R x by bin through xbuf, then R^T t.
-    const bool merged = PNX_BLK_RTR && hb == 1;  // wave uniform
+    const bool merged = hb == 1;  // wave uniform
     double t[kSlots], u[kSlots];
     // the stencil's coefficients are read BEFORE the gathers are issued: scalar loads share their counter with LDS, so a load behind
     // them waits for every gather in flight (it did: the stencil was meant to ride on that round trip and ran behind it)
@@ -594,10 +588,6 @@ __device__ __forceinline__ void dual_residual_form(const double *Bl, double *xbu
         if (!merged) band_eval4<true>(hb, ul, uh, rc, u);  // (R^T t)_j = sum_d c[d + 2] t_{j - d}
     }, u);
     lds_order();
-    if (!PNX_BLK_DIET) {
-#pragma unroll
-        for (int s = 0; s < kSlots; ++s) w[s] -= u[s];
-    }
     // (the caller masks the passive bins)
 }
 
@@ -1061,11 +1051,7 @@ template <bool HOOK> __device__ __forceinline__ void blk_body() {
                 const int ld = fresh(lane);
                 KArgs *K = kargs();
                 const double rc[5] = {K->rc[0], K->rc[1], K->rc[2], K->rc[3], K->rc[4]};
-#ifdef PNX_BLK_FULL_ROWS  // (A/B builds) all 32 rows of the LDS basis whatever the plan's number of measurements, as up to round 4
-                const int mrows = kBMeas;
-#else
                 const int mrows = (K->n_meas + 7) & ~7;
-#endif
                 if (S.p == 0) {  // x = 0: the dual is A^T y, worked out when the voxel was fetched
 #pragma unroll
                     for (int s = 0; s < kSlots; ++s) w[s] = w0[s];
@@ -1078,11 +1064,8 @@ template <bool HOOK> __device__ __forceinline__ void blk_body() {
                 // alone is replaced (0xffe00000: -8.99e307 or below whatever the low word holds; one select per bin instead of two for -inf)
 #pragma unroll
                 for (int s = 0; s < kSlots; ++s) {
-                    if (PNX_BLK_DIET) {
-                        const int hi = __builtin_amdgcn_inverse_ballot_w64(S.inP[s]) ? (int)0xffe00000 : __double2hiint(w[s]);
-                        w[s] = __hiloint2double(hi, __double2loint(w[s]));
-                    } else if (__builtin_amdgcn_inverse_ballot_w64(S.inP[s]))
-                        w[s] = -INFINITY;
+                    const int hi = __builtin_amdgcn_inverse_ballot_w64(S.inP[s]) ? (int)0xffe00000 : __double2hiint(w[s]);
+                    w[s] = __hiloint2double(hi, __double2loint(w[s]));
                 }
             }
             STAMP(1);

@@ -70,19 +70,12 @@ __device__ inline int wave_min_i(int v) {
 // acc += a * b on the lanes of `mask` only (wave-uniform mask).  One VALU instruction: the mask goes through EXEC on the
 // scalar unit instead of a v_cmp + two v_cndmask per fp64 value.  EXEC is saved and restored inside the statement, so the
 // compiler never sees it changed.
-#ifndef PNX_NNLS_ASM_MASK
-#define PNX_NNLS_ASM_MASK 1
-#endif
 __device__ inline void fma_on(double &acc, double a, double b, unsigned long long mask) {
-#if PNX_NNLS_ASM_MASK
     unsigned long long keep;
     asm volatile("s_and_saveexec_b64 %1, %4\n\tv_fma_f64 %0, %2, %3, %0\n\ts_mov_b64 exec, %1"
                  : "+v"(acc), "=&s"(keep)
                  : "v"(a), "v"(b), "s"(mask)
                  : "scc");
-#else
-    if (__builtin_amdgcn_inverse_ballot_w64(mask)) acc = fma(a, b, acc);
-#endif
 }
 // 1 / sqrt(a) for a wave-uniform a > 0: v_rsq_f64 (~2^-26) + two Newton steps instead of the IEEE sqrt + divide
 // expansions (~60 VALU instructions per candidate column)

@@ -12,8 +12,9 @@
 //
 // One wavefront owns one voxel.  lane = measurement for vectors in R^m (residual, candidate column, columns of Q),
 // lane = passive position for x / z / Q^T b / the diagonal of R, four bins per lane for the dual (same bin ownership
-// as pnx_nnls.hip).  Q is stored position major (Qt[i][m], row stride MP + 1: contiguous for lane = m, bank-conflict
+// as pnx_nnls.hip).  Q is stored position major (Qt[i][m], row stride kMP + 1: contiguous for lane = m, bank-conflict
 // free for lane = i), R column major (Rc[k][i] = R[i][k]): the column that is appended is exactly the vector l = Q^T a.
+// Q and R live in LDS up to 32 measurements (nnls_qr_kernel), in a per-wave global slab from 33 to 128 (nnls_qr_big_kernel).
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -27,6 +28,7 @@ namespace pnx {
 namespace {
 constexpr int kW = 64;
 constexpr int kNone = 1 << 30;
+constexpr int kMP = 32;  // measurements of the LDS kernel: Q and R of kMP x (kMP + 1) doubles each (33 .. 128: the slab kernel)
 
 struct QrArgs {
     const double *y;
@@ -88,14 +90,14 @@ __device__ inline void givens(double f, double g, double &c, double &s, double &
 
 // KB: bins per lane -- 4 up to 256 bins, 8 for the wide plans (257 .. 512 bins; the bins only appear in the dual, the arg-max,
 // the passive flags and the output)
-template <int MP, int KB> __global__ void __launch_bounds__(kW) nnls_qr_kernel(const QrArgs A) {
-    constexpr int ST = MP + 1;
+template <int KB> __global__ void __launch_bounds__(kW) nnls_qr_kernel(const QrArgs A) {
+    constexpr int ST = kMP + 1;
     constexpr int kBS = kW * KB;
     extern __shared__ double lds[];
-    double *Qt = lds;             // [MP][ST]  Qt[i][m]: column i of Q
-    double *Rc = Qt + MP * ST;    // [MP][ST]  Rc[k][i] = R[i][k]
-    double *abuf = Rc + MP * ST;  // [64] broadcast buffer (by measurement)
-    double *lbuf = abuf + kW;     // [64] broadcast buffer (by position)
+    double *Qt = lds;              // [kMP][ST]  Qt[i][m]: column i of Q
+    double *Rc = Qt + kMP * ST;    // [kMP][ST]  Rc[k][i] = R[i][k]
+    double *abuf = Rc + kMP * ST;  // [64] broadcast buffer (by measurement)
+    double *lbuf = abuf + kW;      // [64] broadcast buffer (by position)
     const int lane = threadIdx.x;
     const int n = A.n_bins, nm = A.n_meas;
 
@@ -175,7 +177,7 @@ template <int MP, int KB> __global__ void __launch_bounds__(kW) nnls_qr_kernel(c
                     lds_order();
                     lbuf[lane] = li;
                     lds_order();
-                    if (lane < MP)  // rows of Qt / Rc hold MP entries: lanes beyond stay at v = 0
+                    if (lane < kMP)  // rows of Qt / Rc hold kMP entries: lanes beyond stay at v = 0
                         for (int i = 0; i < p; ++i) v = fma(-Qt[i * ST + lane], lbuf[i], v);  // lanes >= nm hold zeros of Q
                     l += li;
                 }
@@ -203,7 +205,7 @@ template <int MP, int KB> __global__ void __launch_bounds__(kW) nnls_qr_kernel(c
             {
                 const double qv = v / lam;
                 lds_order();
-                if (lane < MP) {
+                if (lane < kMP) {
                     Qt[p * ST + lane] = qv;  // lanes >= nm: v = 0
                     Rc[p * ST + lane] = lane < p ? l : (lane == p ? lam : 0.0);
                 }
@@ -260,9 +262,9 @@ template <int MP, int KB> __global__ void __launch_bounds__(kW) nnls_qr_kernel(c
                     const int bin_out = __builtin_amdgcn_readlane(pidx, jj);
                     lds_order();
                     for (int k = jj; k < p - 1; ++k) {
-                        const double cv = lane < MP ? Rc[(k + 1) * ST + lane] : 0.0;
+                        const double cv = lane < kMP ? Rc[(k + 1) * ST + lane] : 0.0;
                         lds_order();
-                        if (lane < MP) Rc[k * ST + lane] = cv;
+                        if (lane < kMP) Rc[k * ST + lane] = cv;
                         lds_order();
                     }
                     for (int i = jj; i < p - 1; ++i) {
@@ -275,7 +277,7 @@ template <int MP, int KB> __global__ void __launch_bounds__(kW) nnls_qr_kernel(c
                             Rc[lane * ST + i] = lane == i ? r : c * a + s * b;
                             Rc[lane * ST + i + 1] = lane == i ? 0.0 : c * b - s * a;
                         }
-                        if (lane < MP) {  // columns i, i + 1 of Q (lane = measurement)
+                        if (lane < kMP) {  // columns i, i + 1 of Q (lane = measurement)
                             const double a = Qt[i * ST + lane], b = Qt[(i + 1) * ST + lane];
                             Qt[i * ST + lane] = c * a + s * b;
                             Qt[(i + 1) * ST + lane] = c * b - s * a;
@@ -289,7 +291,7 @@ template <int MP, int KB> __global__ void __launch_bounds__(kW) nnls_qr_kernel(c
                         lds_order();
                     }
                     // the last (rotated) direction leaves the basis: its share of b goes back into the residual
-                    res = fma(lane < MP ? Qt[(p - 1) * ST + lane] : 0.0, rl(qtb, p - 1), res);
+                    res = fma(lane < kMP ? Qt[(p - 1) * ST + lane] : 0.0, rl(qtb, p - 1), res);
                     {  // positions above jj move down by one
                         const double xs = __shfl_down(xpos, 1);
                         const int ps = __shfl_down(pidx, 1);
@@ -358,28 +360,26 @@ template <int MP, int KB> __global__ void __launch_bounds__(kW) nnls_qr_kernel(c
 #endif
 }
 
-template <int MP> size_t qr_lds_bytes() { return sizeof(double) * (2 * MP * (MP + 1) + 2 * kW); }
+constexpr size_t kQrLdsBytes = sizeof(double) * (2 * kMP * (kMP + 1) + 2 * kW);
 
-template <int MP, int KB> int launch_qr(NnlsPlanData *P, const QrArgs &a, hipStream_t stream) {
+template <int KB> int launch_qr(NnlsPlanData *P, const QrArgs &a, hipStream_t stream) {
     static bool attr_done[64] = {false};
-    auto kern = nnls_qr_kernel<MP, KB>;
+    auto kern = nnls_qr_kernel<KB>;
     if (!attr_done[P->device & 63]) {
-        if (hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)qr_lds_bytes<MP>()) != hipSuccess)
-            return set_error(PNX_ERR_HIP, "hipFuncSetAttribute(nnls_qr_kernel) failed");
+        PNX_HIPN(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kQrLdsBytes));
         attr_done[P->device & 63] = true;
     }
     int occ = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kern, kW, qr_lds_bytes<MP>()) != hipSuccess || occ < 1)
-        return set_error(PNX_ERR_HIP, "nnls_qr_kernel does not fit on a CU");
+    PNX_HIPN(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kern, kW, kQrLdsBytes));
+    if (occ < 1) return set_error(PNX_ERR_HIP, "nnls_qr_kernel does not fit on a CU");
     long long grid = (long long)occ * P->cus;
     if (grid > a.n_vox) grid = a.n_vox;
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(kW), qr_lds_bytes<MP>(), stream, a);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return set_error(PNX_ERR_HIP, "nnls_qr launch: %s", hipGetErrorString(e));
+    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(kW), kQrLdsBytes, stream, a);
+    PNX_HIPN(hipGetLastError());
     return PNX_OK;
 }
 
-// ---- 65 .. 128 measurements (round 4) ---------------------------------------------------------------------------
+// ---- 33 .. 128 measurements (round 4) ---------------------------------------------------------------------------
 // The reference's default regulariser (reg_order = 0) has no limit on the number of b-values (nnls_solver.py:37, 88-127).  With
 // more than 64 of them a measurement-indexed vector takes two register slots per lane, and Q and R (128 x 129 doubles each) no
 // longer fit the LDS of a CU: they live in a per-wave slab in global memory (zero pages until touched; the passive set of an
@@ -729,8 +729,8 @@ template <int KB> __global__ void __launch_bounds__(kW) nnls_qr_big_kernel(const
 
 template <int KB> int launch_qr_big(NnlsPlanData *P, const QrArgs &a, hipStream_t stream) {
     int occ = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, nnls_qr_big_kernel<KB>, kW, 0) != hipSuccess || occ < 1)
-        return set_error(PNX_ERR_HIP, "nnls_qr_big_kernel does not fit on a CU");
+    PNX_HIPN(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, nnls_qr_big_kernel<KB>, kW, 0));
+    if (occ < 1) return set_error(PNX_ERR_HIP, "nnls_qr_big_kernel does not fit on a CU");
     if (occ > 8) occ = 8;  // 264 KB of Q / R per wave: 8 waves per CU are 540 MB of slab, of which a fit touches the rows of its passive set
     long long grid = (long long)occ * P->cus;
     if (!P->qr_slab || P->qr_slab_groups < grid) {
@@ -747,8 +747,7 @@ template <int KB> int launch_qr_big(NnlsPlanData *P, const QrArgs &a, hipStream_
     ba.a = a;
     ba.slab = P->qr_slab;
     hipLaunchKernelGGL(nnls_qr_big_kernel<KB>, dim3((unsigned)grid), dim3(kW), 0, stream, ba);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return set_error(PNX_ERR_HIP, "nnls_qr_big launch: %s", hipGetErrorString(e));
+    PNX_HIPN(hipGetLastError());
     return PNX_OK;
 }
 }  // namespace
@@ -767,16 +766,12 @@ int nnls_qr_solve_device(NnlsPlanData *P, int64_t n_vox, const double *y_d, int 
     a.n_meas = P->n_meas;
     a.n_bins = P->n_bins;
     a.max_iter = max_iter;
-    {
-        // 33 .. 64 measurements fit the LDS kernel (MP = 64: 67 KB, two waves per CU), but the slab kernel with its eight waves
-        // per CU is the faster one there too: 4.16 against 2.82 M voxels/s at 33 b-values, 2.85 against 1.72 M at 64
-        // (profiles/nnls_cliff_probe.py); PNX_NNLS_QR_SLAB_FROM=65 brings the LDS kernel back for comparison
-        static const int slab_from = dev_getenv("PNX_NNLS_QR_SLAB_FROM") ? atoi(dev_getenv("PNX_NNLS_QR_SLAB_FROM")) : 33;
-        const bool wide = P->bstride == kNnlsWideBins;
-        if (P->n_meas >= slab_from || P->n_meas > 64) return wide ? launch_qr_big<8>(P, a, stream) : launch_qr_big<4>(P, a, stream);
-        if (wide) return P->n_meas <= 32 ? launch_qr<32, 8>(P, a, stream) : launch_qr<64, 8>(P, a, stream);
-    }
-    return P->n_meas <= 32 ? launch_qr<32, 4>(P, a, stream) : launch_qr<64, 4>(P, a, stream);
+    // beyond 32 measurements the slab kernel: 33 .. 64 would fit the LDS kernel (Q and R of 64 x 65 doubles: 67 KB, two waves
+    // per CU), but the slab kernel with its eight waves per CU is the faster one there too: 4.16 against 2.82 M voxels/s at 33
+    // b-values, 2.85 against 1.72 M at 64 (profiles/nnls_cliff_probe.py)
+    const bool wide = P->bstride == kNnlsWideBins;
+    if (P->n_meas > kMP) return wide ? launch_qr_big<8>(P, a, stream) : launch_qr_big<4>(P, a, stream);
+    return wide ? launch_qr<8>(P, a, stream) : launch_qr<4>(P, a, stream);
 }
 
 }  // namespace pnx

@@ -250,17 +250,20 @@ def test_builders_on_device(gpu):
     np.testing.assert_allclose(basis, d["basis"], rtol=4e-16, atol=0)  # exp() within 1-2 ulp of numpy's
 
 
-def test_mfma_gram_step_matches_numpy(gpu):
-    """pnx_nnls_aty_f64 (v_mfma_f64_16x16x4 Gram step): aty = y @ basis to fp64 rounding, padding columns zero."""
+@pytest.mark.parametrize("regularised", [True, False], ids=["reg", "reg_none"])
+def test_mfma_gram_step_matches_numpy(gpu, regularised):
+    """pnx_nnls_aty_f64 (v_mfma_f64_16x16x4 Gram step): aty = y @ basis to fp64 rounding, padding columns zero -- on a
+    block-kernel plan and on a QR-form plan (reg=None), whose A^T y scratch is allocated by the first call that needs it."""
     import torch
 
     from pyneapple_amd import synth
 
     _, basis, reg = synth.nnls_matrices(32)
     _, y, _ = synth.make_numpy("tri_reduced", 1000 + 13, 32, sigma=0.01, seed=1, scale=1000.0)
-    plan = gpu.NnlsPlan(basis, reg, 0)
+    plan = gpu.NnlsPlan(basis, reg if regularised else None, 0)
     dev = torch.device("cuda", 0)
     yt = torch.tensor(y, device=dev)
+    plan.aty_device(y.shape[0], yt, None, torch.cuda.current_stream().cuda_stream)  # into the plan's own scratch
     aty = torch.full((y.shape[0], 256), float("nan"), dtype=torch.float64, device=dev)
     plan.aty_device(y.shape[0], yt, aty, torch.cuda.current_stream().cuda_stream)
     torch.cuda.synchronize()
