@@ -34,7 +34,10 @@
  *     PNX_COPY_THREADS (4) of pnx_upload / pnx_download, PNX_HOST_TOUCHERS and PNX_STREAM_OUT_THREADS (helper threads of a
  *     host-array call).  Everything else the sources know -- the NNLS switches PNX_NNLS_NO_BLK (banded regularisers take the
  *     Gram form), PNX_BLK_ROUTE_PERMILLE and PNX_BLK_ROUTE_DEBUG (the block kernel's pilot), PNX_NNLS_DEFER_CAP (deferred
- *     hand-over), chunk sizes of the host pipelines, trace output and the test hook PNX_NNLS_TEST_REJECT (forces rejected
+ *     hand-over), chunk sizes of the host pipelines, trace output (PNX_HOST_TRACE; PNX_LAUNCH_TRACE: one stderr line per
+ *     curve-fit launch -- model, free parameters, FD / PV / T1 / STREAM instantiation, n_b, waves per block, LDS bytes, grid --
+ *     and per sweep call the kernel it chose: full-tile 16 / 32, generic, or full-tile then generic, the generic kernel with
+ *     its block size and copy path) and the test hook PNX_NNLS_TEST_REJECT (forces rejected
  *     candidate columns in the NNLS block kernel) -- is read ONLY when the
  *     process was started with PNX_ENABLE_TEST_HOOKS=1 (looked at once, at the first query); the test-suite and the
  *     profiling scripts set it, bench.py and the plugin never do.
@@ -363,7 +366,9 @@ PNX_API int pnx_label_sums_f64(const double *rows, const int32_t *labels, int64_
  * Residual / Jacobian / normal-equation sweep at given parameters (one pass of the LM inner loop as a
  * standalone, HBM-streaming kernel): for every voxel reads y (n_b) and params (n_all), writes
  * cost = 0.5*||r||^2, g = J^T r (n_all) and the upper triangle of J^T J (n_all(n_all+1)/2).
- * Device pointers only.  T = float (f32) or double (f64).
+ * Device pointers only.  T = float (f32) or double (f64).  1 <= n_b <= PNX_MAX_BVALUES for both (PNX_ERR_INVALID beyond): the
+ * tile of a block lives in LDS, so the generic kernel runs 256 threads per block up to 78 b-values in f64 (any count in f32)
+ * and 128 from 79 to 128; 16 and 32 b-values with a 16-byte aligned y take full-tile instantiations.
  *   y (n_vox, n_b); params (n_all, n_vox); out_cost (n_vox); out_g (n_all, n_vox); out_jtj (n_tri, n_vox)
  */
 PNX_API int pnx_sweep_f32(int model, int64_t n_vox, int n_b, const float *b_host, const float *y, const float *params,

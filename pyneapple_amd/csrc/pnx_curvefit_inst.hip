@@ -1,5 +1,7 @@
 // pnx_curvefit_inst.hip -- explicit instantiations of the TRF kernel for ONE model (compile with
 // -DPNX_MODEL=<0..6>); one translation unit per model keeps the build parallel.
+#include <cstdio>
+
 #include "pnx_curvefit_kernel.hpp"
 #include "pnx_internal.hpp"
 
@@ -54,6 +56,9 @@ static int launch_one(const CurvefitArgs &args, int device_cus, hipStream_t stre
     long long cap = (long long)occ * device_cus;
     int grid = (int)(want < cap ? want : cap);
     if (grid < 1) grid = 1;
+    if (dev_getenv("PNX_LAUNCH_TRACE"))  // diagnostic: which instantiation and block shape this launch uses
+        fprintf(stderr, "[pnx launch] curvefit model=%d N=%d FD=%d PV=%d T1=%d STREAM=%d n_b=%d sigma=%d waves=%d lds=%zu grid=%d\n",
+                MODEL, N, (int)FD, (int)PV, (int)T1, (int)STREAM, args.n_b, args.use_sigma ? 1 : 0, waves, shmem, grid);
     hipLaunchKernelGGL(kern, dim3(grid), dim3(block), shmem, stream, args);
     e = hipGetLastError();
     if (e != hipSuccess) return set_error(PNX_ERR_HIP, "curvefit launch: %s", hipGetErrorString(e));

@@ -13,6 +13,7 @@
 // all outputs are parameter-major (k, n_vox), i.e. coalesced across the wavefront axis.
 #include <hip/hip_runtime.h>
 
+#include <cstdio>
 #include <cstdlib>
 
 #include "pnx_curvefit_kernel.hpp"
@@ -406,10 +407,16 @@ static int launch_sweep_full(const SweepArgs<T> &a, long long n_full, int cus, i
 
 template <int MODEL, typename T, int NT>
 static int launch_sweep_nt(const SweepArgs<T> &a, int cus, hipStream_t st) {
-    const int block = 256;
-    const size_t shmem = sizeof(T) * (kMaxB + (size_t)(block / kWave) * kWave * (a.n_b + 1));
+    // the largest block of 4 / 2 / 1 waves whose padded tiles fit the LDS (the kernel derives its tile count from blockDim.x);
+    // fp64 keeps 4 waves up to 78 b-values and 2 up to 128, fp32 keeps 4 waves everywhere
+    auto bytes = [&](int blk) { return sizeof(T) * (kMaxB + (size_t)blk * (a.n_b + 1)); };
+    int block = 256;
+    while (block > kWave && bytes(block) > 160 * 1024) block >>= 1;
+    const size_t shmem = bytes(block);
+    if (shmem > 160 * 1024) return set_error(PNX_ERR_UNSUPPORTED, "n_b=%d does not fit the LDS tile", a.n_b);
+    const int waves = block / kWave;
     const long long n_tiles = (a.n_vox + kWave - 1) / kWave - a.v_first / kWave;
-    long long want = (n_tiles + 3) / 4;
+    long long want = (n_tiles + waves - 1) / waves;
     static const int bpc = dev_getenv("PNX_SWEEP_BLOCKS_PER_CU") ? atoi(dev_getenv("PNX_SWEEP_BLOCKS_PER_CU")) : 32;
     long long cap = (long long)cus * bpc;  // memory-bound: ~2048 blocks, grid-stride the rest
     int grid = (int)(want < cap ? want : cap);
@@ -423,7 +430,11 @@ static int launch_sweep_nt(const SweepArgs<T> &a, int cus, hipStream_t st) {
         if (ea != hipSuccess) return set_error(PNX_ERR_HIP, "hipFuncSetAttribute: %s", hipGetErrorString(ea));
         attr_set = true;
     }
-    if (shmem > 160 * 1024) return set_error(PNX_ERR_UNSUPPORTED, "n_b=%d does not fit the LDS tile", a.n_b);
+    if (dev_getenv("PNX_LAUNCH_TRACE")) {  // diagnostic: the copy path is the kernel's own predicate (vec_ok)
+        const bool vec = (a.n_b % (int)(16 / sizeof(T))) == 0 && (reinterpret_cast<uintptr_t>(a.y) % 16) == 0;
+        fprintf(stderr, "[pnx launch] sweep generic model=%d f%d n_b=%d v_first=%lld block=%d lds=%zu grid=%d copy=%s\n", MODEL,
+                (int)(8 * sizeof(T)), a.n_b, a.v_first, block, shmem, grid, vec ? "vector" : "scalar");
+    }
     hipLaunchKernelGGL((sweep_kernel<MODEL, T, NT>), dim3(grid), dim3(block), shmem, st, a);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return set_error(PNX_ERR_HIP, "sweep launch: %s", hipGetErrorString(e));
@@ -435,15 +446,22 @@ template <int MODEL, typename T> static int launch_sweep(SweepArgs<T> a, int cus
     // 64 blocks of 4 waves per CU: at C3 every wave gets one tile (measured 4 / 8 / 16 / 32 / 64 / 128: 5.51 / 5.59 / 5.59 /
     // 5.52 / 5.70 / 5.74 TB/s -- flat; the hardware's own wave scheduling hides as much as the software pipeline does)
     static const int bpc = dev_getenv("PNX_SWEEP_BLOCKS_PER_CU") ? atoi(dev_getenv("PNX_SWEEP_BLOCKS_PER_CU")) : 64;
+    const bool trace = dev_getenv("PNX_LAUNCH_TRACE") != nullptr;  // diagnostic: which kernel(s) this call runs
     const long long n_full = a.n_vox / kWave;
     const bool aligned = (reinterpret_cast<uintptr_t>(a.y) % 16) == 0;
     a.v_first = 0;
     if (!generic_only && aligned && n_full > 0 && (a.n_b == 16 || a.n_b == 32)) {
+        const bool tail = n_full * kWave != a.n_vox;
+        if (trace)
+            fprintf(stderr, "[pnx launch] sweep model=%d f%d n_b=%d n_vox=%lld kernel=full-tile %d%s\n", MODEL, (int)(8 * sizeof(T)),
+                    a.n_b, a.n_vox, a.n_b, tail ? " then generic" : "");
         const int rc = a.n_b == 32 ? launch_sweep_full<MODEL, T, 32>(a, n_full, cus, bpc, st)
                                    : launch_sweep_full<MODEL, T, 16>(a, n_full, cus, bpc, st);
         if (rc != PNX_OK) return rc;
         a.v_first = n_full * kWave;  // ragged last tile, if any, goes through the generic kernel
-        if (a.v_first == a.n_vox) return PNX_OK;
+        if (!tail) return PNX_OK;
+    } else if (trace) {
+        fprintf(stderr, "[pnx launch] sweep model=%d f%d n_b=%d n_vox=%lld kernel=generic\n", MODEL, (int)(8 * sizeof(T)), a.n_b, a.n_vox);
     }
     return launch_sweep_nt<MODEL, T, 3>(a, cus, st);
 }

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Differential fuzzing of the HIP curve-fit path against the oracle on unusual inputs (`python tests/fuzz_gpu_vs_oracle.py [n_cases] [seed] [--hostile] [--json out.json]` on a GPU box;
+"""Differential fuzzing of the HIP curve-fit path against the oracle on unusual inputs (`python tests/fuzz_gpu_vs_oracle.py [n_cases] [seed] [--hostile] [--wide-b] [--json out.json]` on a GPU box;
 tests/test_gpu_parity_large.py runs 100 fixed-seed cases of it in the GPU suite).  Every case draws a model, a b-value
 set (1..64 values, uniform or clinical or with duplicates), signal scale (1e-6..1e6), noise level, bounds (tight, loose,
 half infinite), start values (random inside the box, on a bound, equal to the truth), Jacobian mode, optional
@@ -44,7 +44,7 @@ def forward(model, b, P, t1_mode=0, tr=0.0, tm=0.0):
     return s
 
 
-def draw_case(rng):
+def draw_case(rng, wide_b=False):
     model = rng.choice(list(NAMES))
     nm = list(NAMES[model])
     t1_mode = int(rng.choice([0, 0, 0, 1, 2]))
@@ -55,16 +55,22 @@ def draw_case(rng):
     hostile = HOSTILE  # also draw ill-posed problems (fewer b-values than parameters, free T1 next to a free amplitude,
     # infinite upper bounds on D, far-away starts): SciPy itself is not reproducible there, only crashes / hangs count
     kind = rng.choice(["lin", "clinical", "dup", "few"] if hostile else ["lin", "clinical", "dup"])
+    if wide_b:  # 65..128 b-values (extra draws: the default sequence of cases stays what it was)
+        kind = str(rng.choice(["lin", "lin", "dup"]))
     if kind == "lin" and hostile:
         n_b = int(rng.integers(n_all + 1, 65))
         b = np.linspace(0, float(rng.choice([800, 1200, 3000])), n_b)
     elif kind == "lin":
         n_b = int(rng.integers(16, 65))
         b = np.linspace(0, float(rng.choice([800, 1200])), n_b)
+        if wide_b:
+            b = np.linspace(0, b[-1], int(rng.integers(65, 129)))
     elif kind == "clinical":
         b = np.array([0, 5, 10, 20, 30, 40, 50, 75, 100, 150, 200, 400, 600, 800, 1000, 1500], float)[: int(rng.integers(max(n_all + 1, 6), 17))]
     elif kind == "dup":
         b = np.repeat(np.linspace(0, 1000, int(rng.integers(4, 12) if hostile else rng.integers(12, 20))), 3)
+        if wide_b:
+            b = np.repeat(np.linspace(0, 1000, int(rng.integers(22, 43))), 3)  # 66 .. 126
     else:
         b = np.sort(rng.uniform(0, 1000, int(rng.integers(1, n_all + 2))))  # fewer b-values than parameters is allowed
     n_b = len(b)
@@ -158,14 +164,15 @@ def draw_case(rng):
 HOSTILE = "--hostile" in sys.argv
 
 
-def run(n_cases=300, seed=0, verbose=True, n_threads=8):
-    """n_cases random cases from `seed`; returns the summary dict that `--json` writes and the GPU suite asserts on."""
+def run(n_cases=300, seed=0, verbose=True, n_threads=8, wide_b=False):
+    """n_cases random cases from `seed`; returns the summary dict that `--json` writes and the GPU suite asserts on.
+    wide_b: every case draws 65..128 b-values."""
     say = print if verbose else (lambda *a, **k: None)
     rng = np.random.default_rng(seed)
     bad_cases = 0
     tot_vox = tot_param_bad = tot_status_bad = tot_cost_bad = tot_sentinel_bad = 0
     for c in range(n_cases):
-        desc, model, b, y, p0, lo, hi, kw = draw_case(rng)
+        desc, model, b, y, p0, lo, hi, kw = draw_case(rng, wide_b)
         try:
             o = oracle.curvefit(model, b, y, p0, lo, hi, n_threads=n_threads, **kw)
         except Exception as e:  # oracle rejects (e.g. m < n is fine, but some combos are invalid): the GPU must reject too
@@ -212,7 +219,7 @@ def run(n_cases=300, seed=0, verbose=True, n_threads=8):
         f"parameter-only disagreements on determined voxels {tot_param_bad}; failing cases {bad_cases}")
     from pyneapple_amd import _build
 
-    return {"fuzzer": "curvefit", "hostile": HOSTILE, "n_cases": n_cases, "seed": seed, "voxels": tot_vox,
+    return {"fuzzer": "curvefit", "hostile": HOSTILE, "wide_b": wide_b, "n_cases": n_cases, "seed": seed, "voxels": tot_vox,
             "status_sign_disagreements": tot_status_bad, "cost_disagreements": tot_cost_bad,
             "parameter_only_disagreements_on_determined_voxels": tot_param_bad, "sentinel_disagreements": tot_sentinel_bad,
             "failing_cases": bad_cases,
@@ -227,6 +234,9 @@ def main():
 
     if HOSTILE:
         sys.argv.remove("--hostile")
+    wide_b = "--wide-b" in sys.argv
+    if wide_b:
+        sys.argv.remove("--wide-b")
     out = None
     if "--json" in sys.argv:
         i = sys.argv.index("--json")
@@ -234,7 +244,7 @@ def main():
         del sys.argv[i:i + 2]
     n_cases = int(sys.argv[1]) if len(sys.argv) > 1 else 300
     seed = int(sys.argv[2]) if len(sys.argv) > 2 else 0
-    res = run(n_cases, seed)
+    res = run(n_cases, seed, wide_b=wide_b)
     if out:
         with open(out, "w") as fh:
             json.dump(res, fh, indent=1)

@@ -4,7 +4,7 @@ random configurations: model, number of b-values (odd: no LDS-DMA refill), volum
 on / off, Jacobian mode, a shared or per-voxel fixed parameter, per-voxel start values and bounds, the T1 factor, granule size,
 upload piece size, download and page-touch thread counts, a small evaluation budget (failure sentinels).  Every output must be
 bit-identical, and the streamed call must neither time out nor fall back.
-    python tests/fuzz_stream_vs_ring.py [n_cases] [seed]          (on a GPU box; 40 fixed-seed cases run in the GPU suite)"""
+    python tests/fuzz_stream_vs_ring.py [n_cases] [seed] [--wide-b]          (on a GPU box; 40 fixed-seed cases run in the GPU suite)"""
 from __future__ import annotations
 import os as _os; _os.environ.setdefault("PNX_ENABLE_TEST_HOOKS", "1")  # this script drives developer switches of the library (include/pnx.h, "Environment")
 
@@ -22,9 +22,11 @@ KNOBS = ("PNX_HOST_STREAM", "PNX_STREAM_GRANULE_SHIFT", "PNX_STREAM_IN_CHUNK", "
          "PNX_HOST_CHUNK")
 
 
-def draw_case(rng):
+def draw_case(rng, wide_b=False):
     model = str(rng.choice(["mono", "bi_reduced", "tri_reduced"]))
     n_b = int(rng.integers(6, 41))
+    if wide_b:  # an extra draw, so the default sequence of cases stays what it was
+        n_b = int(rng.integers(41, 129))
     n_vox = int(rng.integers(1100, 30000))
     dtype = np.float32 if rng.random() < 0.4 else np.float64
     b, y, P = synth.make_numpy(model, n_vox, n_b, sigma=float(rng.choice([0.0, 0.01, 0.05])), seed=int(rng.integers(1 << 30)))
@@ -58,14 +60,15 @@ def draw_case(rng):
     return desc, model, b, y.astype(dtype), p0, lo, hi, kw, env
 
 
-def run(n_cases=100, seed=0, verbose=True):
+def run(n_cases=100, seed=0, verbose=True, wide_b=False):
+    """wide_b: 41..128 b-values instead of 6..40 (the fit kernel's blocks of 3, 2 and 1 waves)."""
     say = print if verbose else (lambda *a, **k: None)
     rng = np.random.default_rng(seed)
     saved = {k: os.environ.get(k) for k in KNOBS + ("PNX_HOST_TRACE",)}
     bad, streamed, voxels = 0, 0, 0
     try:
         for c in range(n_cases):
-            desc, model, b, y, p0, lo, hi, kw, env = draw_case(rng)
+            desc, model, b, y, p0, lo, hi, kw, env = draw_case(rng, wide_b)
             os.environ.update(env)
             os.environ["PNX_HOST_STREAM"] = "0"
             os.environ.pop("PNX_HOST_TRACE", None)
@@ -97,7 +100,7 @@ def run(n_cases=100, seed=0, verbose=True):
             else:
                 os.environ[k] = v
     say(f"{n_cases} cases, {voxels} voxels, {streamed} streamed: {bad} failing")
-    return {"fuzzer": "stream_vs_ring", "n_cases": n_cases, "seed": seed, "voxels": voxels, "streamed_cases": streamed, "failing_cases": bad}
+    return {"fuzzer": "stream_vs_ring", "n_cases": n_cases, "seed": seed, "wide_b": wide_b, "voxels": voxels, "streamed_cases": streamed, "failing_cases": bad}
 
 
 def _stderr_of(fn):
@@ -118,7 +121,7 @@ def _stderr_of(fn):
 
 if __name__ == "__main__":
     a = [x for x in sys.argv[1:] if not x.startswith("--")]
-    out = run(int(a[0]) if a else 100, int(a[1]) if len(a) > 1 else 0)
+    out = run(int(a[0]) if a else 100, int(a[1]) if len(a) > 1 else 0, wide_b="--wide-b" in sys.argv)
     if "--json" in sys.argv:
         import json
         from pyneapple_amd import _build

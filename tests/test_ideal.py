@@ -203,6 +203,47 @@ def test_device_resident_pyramid_equals_host_pyramid(gpu):
 
 
 @pytest.mark.gpu
+def test_device_resident_pyramid_equals_host_pyramid_at_96_b_values(gpu):
+    """The device-resident level loop calls pnx_sweep_f64 at every level after the first; its generic kernel used to refuse more
+    than 78 b-values in fp64 (the 256-thread tile did not fit the LDS) although the fit itself takes 128.  Same assertions as
+    test_device_resident_pyramid_equals_host_pyramid, on 96 b-values."""
+    from pyneapple_amd.solvers import HipCurveFitSolver
+
+    rng = np.random.default_rng(4)
+    b = np.linspace(0, 1200, 96)
+    X, Y, Z = 12, 10, 2
+    f1 = 0.2 + 0.1 * rng.random((X, Y, Z))
+    D1 = 0.02 + 0.01 * rng.random((X, Y, Z))
+    D2 = 0.001 + 0.0005 * rng.random((X, Y, Z))
+    img = f1[..., None] * np.exp(-b * D1[..., None]) + (1 - f1[..., None]) * np.exp(-b * D2[..., None])
+    img = img * (1 + 0.01 * rng.standard_normal(img.shape))
+    seg = np.zeros((X, Y, Z), int)
+    seg[2:10, 1:8, :] = 1
+    steps = np.array([[3, 3], [6, 5], [12, 10]])
+    tol = {"f1": 0.5, "D1": 0.5, "D2": 0.5}
+
+    def run(resident, segmentation):
+        solver = HipCurveFitSolver(model=BiExpModel(), max_iter=250, tol=1e-8, p0={"f1": 0.2, "D1": 0.01, "D2": 0.001},
+                                   bounds={"f1": (0.0, 1.0), "D1": (1e-3, 0.1), "D2": (1e-5, 5e-3)})
+        f = HipIDEALFitter(solver, steps, tol, device_resident=resident)
+        f.fit(b, img, segmentation)
+        return f, solver
+
+    for segmentation in (None, seg):
+        fh, sh = run(False, segmentation)
+        fd, sd = run(True, segmentation)
+        assert len(fd.step_params) == 3
+        for a, c in zip(fh.step_params, fd.step_params):
+            assert a.shape == c.shape
+            np.testing.assert_allclose(c, a, rtol=1e-6, atol=1e-12)
+        np.testing.assert_array_equal(fd.pixel_indices, fh.pixel_indices)
+        for k in ("f1", "D1", "D2"):
+            np.testing.assert_allclose(fd.fitted_params_[k], fh.fitted_params_[k], rtol=1e-6)
+        np.testing.assert_array_equal(sd.diagnostics_["status"], sh.diagnostics_["status"])
+        assert sd.diagnostics_["pcov"].shape == sh.diagnostics_["pcov"].shape and len(sd.pixel_results_) == len(sh.pixel_results_)
+
+
+@pytest.mark.gpu
 def test_config5_triexp_three_levels_full_size(gpu, oracle):
     """BASELINE configs[4]: IDEAL multi-resolution triexp, 64^2 -> 128^2 -> 256^2, 64 slices, 32 b-values, through the
     HBM-resident pyramid (fitters/ideal.py:167-254 of the reference).  Size-independent properties on all 4.19 M
