@@ -40,6 +40,9 @@ template <int N> constexpr int row_blk() { return N >= 7 ? 2 : (N >= 5 ? 4 : 8);
 #endif
 constexpr double kEps = 2.220446049250313e-16;
 constexpr double kSqrtEps = 1.4901161193847656e-08;
+template <bool B> struct BoolC {  // compile-time flag handed to a generic lambda
+    static constexpr bool value = B;
+};
 typedef __attribute__((address_space(3))) void lds_void;
 
 // Control block of a streamed launch.  `ready` is written by 8-byte H2D copies enqueued behind each granule's upload (stream
@@ -684,7 +687,7 @@ __global__ void __launch_bounds__(64 * PNX_CF_BLOCK_WAVES, PNX_CF_WAVES_PER_SIMD
     double *bsh = smem;                                   // [kMaxB]
     const int lane = threadIdx.x & (kWave - 1);
     const int wave = threadIdx.x / kWave;
-    const bool use_w = A.use_sigma != 0;                  // wave uniform: a scalar branch per row, nothing else changes without sigma
+    const bool use_w = A.use_sigma != 0;                  // wave uniform: selects the row loop of a pass, nothing else changes without sigma
     const double *wsh = smem + kMaxB;                     // [kMaxB] 1 / sigma per measurement -- only allocated with sigma
     double *ytile = smem + (use_w ? 2 * kMaxB : kMaxB) + (size_t)wave * PK::per_wave(n_b);  // [ceil(n_b/2)][64][2], wave-uniform base
     double *ysh = ytile + 2 * lane;                                         // this lane's pair column
@@ -693,6 +696,13 @@ __global__ void __launch_bounds__(64 * PNX_CF_BLOCK_WAVES, PNX_CF_WAVES_PER_SIMD
     for (int i = threadIdx.x; i < n_b; i += blockDim.x) bsh[i] = A.b[i];
     if (use_w)
         for (int i = threadIdx.x; i < n_b; i += blockDim.x) smem[kMaxB + i] = A.w[i];
+    // largest |b| of the table (wave uniform; infinite when a b-value is not finite): the row pass tests the range of the FD
+    // factor's argument against it once per pass instead of once per row
+    double bmax = 0;
+    for (int i = 0; i < n_b; ++i) {
+        const double ab = fabs(A.b[i]);
+        bmax = (ab < INFINITY) ? fmax(bmax, ab) : INFINITY;
+    }
     __syncthreads();
     // the refill uses asynchronous 16-byte global->LDS loads, one per pair of b-values.  The global side needs no more than the
     // 8-byte alignment every row of doubles has (rows of an odd number of b-values start on odd multiples of 8), and the last
@@ -916,16 +926,38 @@ __global__ void __launch_bounds__(64 * PNX_CF_BLOCK_WAVES, PNX_CF_WAVES_PER_SIMD
                 for (int j = 0; j < N; ++j) Rn[i][j] = 0;
             }
             constexpr int kRowBlk = row_blk<N>();
-            for (int i0 = 0; i0 < n_b; i0 += kRowBlk) {
+            static_assert(kRowBlk % 2 == 0, "a block reads its signal values as [pair][lane][2] pairs");
+            // One block of kRowBlk rows: residuals, Jacobian rows, J^T f, then the Householder merge.  The variants differ in
+            // control flow only, never in an arithmetic operation or its order:
+            //   FASTGZ  the pass has established that |b dx| < 2e-4 holds for every row and every lane, so the FD factor is the
+            //           cubic the per-row test would have selected -- no compare, no branch;
+            //   USEW    rows are scaled by 1 / sigma (the tail block tests use_w at run time instead);
+            //   TAIL    the last, partial block of an n_b that is no multiple of kRowBlk: rows beyond n_b are evaluated at row 0
+            //           and replaced by zeros.  A full block needs none of those selects and reads b and y as 16-byte pairs up
+            //           front, which leaves it one basic block up to qr_merge's sig > 0 tests: the scheduler is free to
+            //           interleave the exp chains of all its rows and to cover the LDS latency once per block.
+            auto row_block = [&](auto fastgz_c, auto usew_c, auto tail_c, const int i0) __attribute__((always_inline)) {
+                constexpr bool FASTGZ = decltype(fastgz_c)::value, USEW = decltype(usew_c)::value, TAIL = decltype(tail_c)::value;
                 double blk[kRowBlk][N + 1];
+                double bv[TAIL ? 1 : kRowBlk], yv[TAIL ? 1 : kRowBlk];
+                if constexpr (!TAIL) {
+#pragma unroll
+                    for (int r = 0; r < kRowBlk; r += 2) {  // i0 is even: rows (i0 + r, i0 + r + 1) are one pair of the tile
+                        const double2 b2 = *reinterpret_cast<const double2 *>(bsh + i0 + r);
+                        const double2 y2 = *reinterpret_cast<const double2 *>(ysh + (size_t)(i0 + r) * kWave);
+                        bv[r] = b2.x;
+                        bv[r + 1] = b2.y;
+                        yv[r] = y2.x;
+                        yv[r + 1] = y2.y;
+                    }
+                }
 #pragma unroll
                 for (int r = 0; r < kRowBlk; ++r) {
-                    const int i = i0 + r;
-                    const bool live = i < n_b;
-                    const int ii = live ? i : 0;
-                    const double bb = bsh[ii];
+                    const bool live = !TAIL || (i0 + r < n_b);
+                    const int ii = live ? i0 + r : 0;
+                    const double bb = TAIL ? bsh[ii] : bv[TAIL ? 0 : r];
                     const double nb = -bb;
-                    const double yi = ysh[(ii >> 1) * 2 * kWave + (ii & 1)];
+                    const double yi = TAIL ? ysh[(ii >> 1) * 2 * kWave + (ii & 1)] : yv[TAIL ? 0 : r];
                     yfinite = yfinite && isfinite(yi);
                     double E[NC];
 #pragma unroll
@@ -950,7 +982,7 @@ __global__ void __launch_bounds__(64 * PNX_CF_BLOCK_WAVES, PNX_CF_WAVES_PER_SIMD
                                     const double z = nb * dxv[k];
                                     double gz;
 #if PNX_CF_FAST_EXP
-                                    if (PNX_LIKELY(fabs(z) < 2e-4))  // dx ~ 1.5e-8 max(1, |D|): the normal case; z^4 / 120 < 2e-17
+                                    if (FASTGZ || PNX_LIKELY(fabs(z) < 2e-4))  // dx ~ 1.5e-8 max(1, |D|): the normal case; z^4 / 120 < 2e-17
                                         gz = fma(z, fma(z, fma(z, 1.0 / 24, 1.0 / 6), 0.5), 1.0);
                                     else
 #endif
@@ -967,7 +999,7 @@ __global__ void __launch_bounds__(64 * PNX_CF_BLOCK_WAVES, PNX_CF_WAVES_PER_SIMD
                             for (int k = 0; k < NALL; ++k) ja[k] *= fac;
                             ja[NP - 1] = base * dfac;
                         }
-                        if (use_w) {  // transform * (f - y), transform[:, None] * jac (the 2-point quotient of scaled residuals)
+                        if (TAIL ? use_w : USEW) {  // transform * (f - y), transform[:, None] * jac (the 2-point quotient of scaled residuals)
                             const double t = wsh[ii];
                             r0 *= t;
 #pragma unroll
@@ -1001,6 +1033,38 @@ __global__ void __launch_bounds__(64 * PNX_CF_BLOCK_WAVES, PNX_CF_WAVES_PER_SIMD
                 CFSTAMP(1);  // rows of the block: exp, model, Jacobian row, J^T f (diagnostic builds: -DPNX_CF_STAMP)
                 qr_merge<N, kRowBlk>(Rn, qn, blk);
                 CFSTAMP(6);  // the sequential Householder merge of the block into R
+            };
+            auto row_loop = [&](auto fastgz_c, auto usew_c) __attribute__((always_inline)) {
+                int i0 = 0;
+                for (; i0 + kRowBlk <= n_b; i0 += kRowBlk) row_block(fastgz_c, usew_c, BoolC<false>{}, i0);
+                if (i0 < n_b) row_block(BoolC<false>{}, BoolC<false>{}, BoolC<true>{}, i0);
+            };
+            // FD factor range test, once per pass instead of once per row and column: rounded multiplication is monotone in |b|,
+            // so a lane whose |bmax dx_k| is below the threshold passes the per-row test in every row; with every lane of the
+            // wave passing (the normal case: dx ~ 1.5e-8 max(1, |D|)) the loop without the test computes the same bits.  A NaN
+            // dx fails the comparison and takes the generic loop.
+            // The instantiations with six and more free parameters use all 512 registers of a lane and spill: the specialised
+            // loops cost them scratch, so they keep the one generic loop (the tail variant run over every block).
+            constexpr bool kOneLoop = (N >= 6);
+            bool gz_cubic = FD && PNX_CF_FAST_EXP && !kOneLoop;
+            if (FD && PNX_CF_FAST_EXP && !kOneLoop) {
+                bool in_range = true;
+#pragma unroll
+                for (int k = 0; k < NALL; ++k)
+                    if (comp_of_param<MODEL>(k) >= 0) in_range = in_range && (fabs(bmax * dxv[k]) < 2e-4);
+                gz_cubic = __ballot(!in_range) == 0;
+            }
+            if constexpr (kOneLoop) {
+                for (int i0 = 0; i0 < n_b; i0 += kRowBlk) row_block(BoolC<false>{}, BoolC<false>{}, BoolC<true>{}, i0);
+            } else if (PNX_LIKELY(!use_w && (gz_cubic || !FD))) {
+                if constexpr (FD && PNX_CF_FAST_EXP)
+                    row_loop(BoolC<true>{}, BoolC<false>{});
+                else
+                    row_loop(BoolC<false>{}, BoolC<false>{});
+            } else if (use_w) {
+                row_loop(BoolC<false>{}, BoolC<true>{});
+            } else {
+                if constexpr (FD) row_loop(BoolC<false>{}, BoolC<false>{});
             }
             cost_new *= 0.5;
         }
