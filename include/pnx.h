@@ -301,6 +301,38 @@ PNX_API int pnx_nnls_solve_peaks_f64(pnx_nnls_plan *plan, int64_t n_vox, const d
                              double *d_values, double *f_values, int n_cut, const double *cutoffs_host, double *d_cut,
                              double *f_cut, double *rnorm, int8_t *status, int32_t *iters, int mem, void *stream);
 /*
+ * The same call with the data-term residual of every voxel: solve -> ss_res -> peak table on the device while the chunk's spectra
+ * are resident.  Every argument of pnx_nnls_solve_peaks_f64, in its order, then ss_res (n_vox,) host|device as `mem`, required:
+ * 8 bytes per voxel of download instead of the 2 KB spectrum, so that R^2 exists on the peak-table path too.
+ */
+PNX_API int pnx_nnls_solve_peaks_stats_f64(pnx_nnls_plan *plan, int64_t n_vox, const double *y, int max_iter, const double *bins_host,
+                                   double height, int regularized, double rel_height, int max_peaks, int32_t *n_peaks,
+                                   double *d_values, double *f_values, int n_cut, const double *cutoffs_host, double *d_cut,
+                                   double *f_cut, double *rnorm, int8_t *status, int32_t *iters, int mem, void *stream,
+                                   double *ss_res);
+/*
+ * Prediction and data-term residual of a batch of spectra (what BaseFitter._compute_r_squared and predict do with
+ * `coefficients @ basis.T`, fitters/base.py:90-186):  pred (n_vox, n_meas) = coeff . basis^T,
+ * ss_res (n_vox,) = sum_j (y_ij - pred_ij)^2 over the plan's n_meas data rows -- NOT rnorm^2, which contains the regulariser rows.
+ *   y (n_vox, n_meas), coeff (n_vox, n_bins) in; ss_res and pred out, either may be NULL but not both (y may be NULL when ss_res
+ *   is); all host|device as `mem`; `device` must be the plan's.  The product runs on the fp64 matrix cores for every plan
+ *   (any n_meas <= 128, n_bins <= 512); the plan is only read, so calls need no ordering against solves.
+ */
+PNX_API int pnx_nnls_fit_stats_f64(pnx_nnls_plan *plan, int64_t n_vox, const double *y, const double *coeff, double *ss_res,
+                           double *pred, int mem, int device, void *stream);
+/*
+ * Forward model of the seven parametric layouts for all voxels (model.forward per voxel in the reference, fitters/base.py:90-131,
+ * 142-186), at n_x <= PNX_MAX_BVALUES x-values that need not be the fitted b-values (PNX_ERR_INVALID beyond).
+ *   opts: only model, n_free, n_fixed, free_idx, fixed_idx, fixed_per_voxel, t1_mode, tr, tm are read (n_b is ignored);
+ *   x (n_x,) host; params (n_free, n_vox) parameter-major as popt of the fit; fixed (n_fixed,) host or (n_fixed, n_vox) as the fit
+ *   takes it; y (n_vox, n_x) or NULL; pred (n_vox, n_x) or NULL; ss_res (n_vox,) = sum_i (pred_i - y_i)^2 or NULL (needs y);
+ *   pred and ss_res may not both be NULL.  params, per-voxel fixed, y, pred, ss_res host|device as `mem`.
+ *   The arithmetic is the fit's own (same exp, same operation order, same T1 / STEAM factor).
+ */
+PNX_API int pnx_curvefit_predict_f64(const pnx_curvefit_opts *opts, int64_t n_vox, int n_x, const double *x, const double *params,
+                             const double *fixed, const double *y, double *pred, double *ss_res, int mem, int device,
+                             void *stream);
+/*
  * float32 parameter maps (io/nifti.py:279-312 reconstruct_maps): out (n_spatial, k) zero filled, then
  * out[linear_index[i], :] = (float) values[i, :] for the n_px fitted voxels (linear_index = C-order index into the
  * (X, Y, Z) grid).  values (n_px, k) float64, linear_index (n_px) int64, out float32: host|device as `mem`.

@@ -31,6 +31,7 @@ SOURCE_GROUPS = {
     "curvefit": ["pnx_curvefit_kernel.hpp", "pnx_curvefit_inst.hip"],
     "nnls": ["pnx_nnls.hip", "pnx_nnls.hpp", "pnx_nnls_dev.hpp", "pnx_nnls_qr.hip", "pnx_nnls_blk.hip", "pnx_nnls_blk_kernel.hpp"],
     "sweep": ["pnx_sweep.hip"],
+    "predict": ["pnx_predict.hip", "pnx_predict.hpp"],
     # the host boundary (streamed path, chunk ring, deferred NNLS hand-over, peak tables): host-mode / PCIe-inclusive figures and
     # the host-path fuzz summaries are stamped with this id, so that they are not replayed as current after pnx_api.hip changes
     # (round 4: the orchestration of both host paths moved into pnx_host_pipeline.hpp; the peak analysis the rings call is pnx_spectrum.hip)
@@ -57,7 +58,7 @@ def _units():
     units = [("pnx_api.o", "pnx_api.hip", []), ("pnx_nnls.o", "pnx_nnls.hip", NNLS_FLAGS), ("pnx_nnls_qr.o", "pnx_nnls_qr.hip", NNLS_FLAGS),
              ("pnx_nnls_blk.o", "pnx_nnls_blk.hip", NNLS_FLAGS),
              ("pnx_sweep.o", "pnx_sweep.hip", []), ("pnx_spectrum.o", "pnx_spectrum.hip", []),
-             ("pnx_resize.o", "pnx_resize.hip", [])]
+             ("pnx_resize.o", "pnx_resize.hip", []), ("pnx_predict.o", "pnx_predict.hip", [])]
     for m in range(N_MODELS):
         units.append((f"pnx_curvefit_m{m}.o", "pnx_curvefit_inst.hip", [f"-DPNX_MODEL={m}", *CURVEFIT_FLAGS]))
     return [u for u in units if os.path.exists(os.path.join(CSRC, u[1]))]

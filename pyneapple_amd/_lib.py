@@ -26,6 +26,7 @@ ABI_SYMBOLS = [
     "pnx_resize2d_f64", "pnx_ideal_bounds_f64", "pnx_nnls_spectrum_peaks_f64", "pnx_nnls_solve_peaks_f64", "pnx_scatter_maps_f32",
     "pnx_mask_select_f64", "pnx_gather_rows_f64", "pnx_scatter_rows_t_f64", "pnx_row_ss_tot_f64", "pnx_upload", "pnx_download",
     "pnx_label_sums_f64", "pnx_release_staging", "pnx_queue_order_f64",
+    "pnx_nnls_fit_stats_f64", "pnx_nnls_solve_peaks_stats_f64", "pnx_curvefit_predict_f64",
 ]
 
 
@@ -136,6 +137,12 @@ def load():
     lib.pnx_nnls_solve_peaks_f64.restype = C.c_int
     lib.pnx_nnls_solve_peaks_f64.argtypes = [vp, C.c_int64, vp, C.c_int, dp, C.c_double, C.c_int, C.c_double, C.c_int, vp, vp, vp,
                                              C.c_int, dp, vp, vp, vp, vp, vp, C.c_int, vp]
+    lib.pnx_nnls_solve_peaks_stats_f64.restype = C.c_int
+    lib.pnx_nnls_solve_peaks_stats_f64.argtypes = [*lib.pnx_nnls_solve_peaks_f64.argtypes, vp]
+    lib.pnx_nnls_fit_stats_f64.restype = C.c_int
+    lib.pnx_nnls_fit_stats_f64.argtypes = [vp, C.c_int64, vp, vp, vp, vp, C.c_int, C.c_int, vp]
+    lib.pnx_curvefit_predict_f64.restype = C.c_int
+    lib.pnx_curvefit_predict_f64.argtypes = [C.POINTER(CurvefitOpts), C.c_int64, C.c_int, dp, vp, vp, vp, vp, vp, C.c_int, C.c_int, vp]
     lib.pnx_scatter_maps_f32.restype = C.c_int
     lib.pnx_scatter_maps_f32.argtypes = [vp, vp, C.c_int64, C.c_int, C.c_int64, vp, C.c_int, C.c_int, vp]
     lib.pnx_mask_select_f64.restype = C.c_int

@@ -185,10 +185,48 @@ class NnlsPlan:
         """Enqueue the MFMA Gram step alone: aty (n_vox, 256) = y @ basis (None: into the plan's own scratch)."""
         check(load().pnx_nnls_aty_f64(self._h, int(n_vox), ptr(y), ptr(aty), stream))
 
-    def solve_peaks(self, y, bins, max_iter=250, height=0.1, regularized=False, rel_height=0.5, max_peaks=8, cutoffs=None):
+    def fit_stats(self, y, coeff, want_pred=False):
+        """Data-term residual of a batch of spectra on the device (pnx_nnls_fit_stats_f64): dict(ss_res (n_vox,) =
+        sum_j (y - coeff @ basis.T)^2 over the measurements -- not `residual`^2 of a regularised solve, which contains the
+        regulariser rows -- and pred (n_vox, n_meas) = coeff @ basis.T when want_pred, else None).  y None: the prediction
+        alone (ss_res None).  numpy arrays, or torch device tensors for both (then the outputs are tensors and the call only
+        enqueues)."""
+        tensor = _is_torch(coeff)
+        if y is None and not want_pred:
+            raise ValueError("nothing to compute: no signal y for ss_res and want_pred=False")
+        if y is not None and tensor != _is_torch(y):
+            raise ValueError("y and coeff must both be numpy arrays or both be device tensors")
+        if not tensor:
+            y = None if y is None else np.ascontiguousarray(np.atleast_2d(y), np.float64)
+            coeff = np.ascontiguousarray(np.atleast_2d(coeff), np.float64)
+        if len(coeff.shape) != 2 or coeff.shape[1] != self.n_bins:
+            raise ValueError(f"coeff has shape {tuple(coeff.shape)}, expected (n_vox, {self.n_bins})")
+        n_vox = int(coeff.shape[0])
+        if y is not None and tuple(y.shape) != (n_vox, self.n_meas):
+            raise ValueError(f"signal has shape {tuple(y.shape)}, expected ({n_vox}, {self.n_meas})")
+        if tensor:
+            import torch
+
+            for t in (y, coeff):
+                if t is not None and (t.dtype != torch.float64 or not t.is_contiguous()):
+                    raise ValueError("device tensors must be contiguous float64")
+            ss = torch.empty(n_vox, dtype=torch.float64, device=coeff.device) if y is not None else None
+            pred = torch.empty((n_vox, self.n_meas), dtype=torch.float64, device=coeff.device) if want_pred else None
+            stream = torch.cuda.current_stream(coeff.device).cuda_stream
+        else:
+            ss = np.empty(n_vox) if y is not None else None
+            pred = np.empty((n_vox, self.n_meas)) if want_pred else None
+            stream = None
+        check(load().pnx_nnls_fit_stats_f64(self._h, n_vox, ptr(y), ptr(coeff), ptr(ss), ptr(pred), MEM_DEVICE if tensor else MEM_HOST,
+                                            int(self.device), stream))
+        return dict(ss_res=ss, pred=pred)
+
+    def solve_peaks(self, y, bins, max_iter=250, height=0.1, regularized=False, rel_height=0.5, max_peaks=8, cutoffs=None,
+                    with_ss_res=False):
         """Solve and reduce every spectrum to its peak table on the device (pnx_nnls_solve_peaks_f64): the (n_vox, n_bins)
         spectra never cross PCIe.  Returns dict(n_peaks, d_values, f_values (n_vox, max_peaks) NaN padded, d_cut, f_cut
-        (n_vox, n_cut) or None, residual, status, iters)."""
+        (n_vox, n_cut) or None, residual, status, iters).  with_ss_res: also ss_res (n_vox,), the data-term residual
+        sum_j (y - B x)^2 of every spectrum, reduced while it is resident (pnx_nnls_solve_peaks_stats_f64)."""
         y = np.ascontiguousarray(np.atleast_2d(y), np.float64)
         n_vox = y.shape[0]
         if y.shape[1] != self.n_meas:
@@ -201,10 +239,15 @@ class NnlsPlan:
         out = dict(n_peaks=np.empty(n_vox, np.int32), d_values=np.empty((n_vox, max_peaks)), f_values=np.empty((n_vox, max_peaks)),
                    d_cut=np.empty((n_vox, n_cut)) if n_cut else None, f_cut=np.empty((n_vox, n_cut)) if n_cut else None,
                    residual=np.empty(n_vox), status=np.empty(n_vox, np.int8), iters=np.empty(n_vox, np.int32))
-        check(load().pnx_nnls_solve_peaks_f64(self._h, n_vox, ptr(y), int(max_iter), ptr(bins), float(height), int(bool(regularized)),
-                                              float(rel_height), int(max_peaks), ptr(out["n_peaks"]), ptr(out["d_values"]),
-                                              ptr(out["f_values"]), n_cut, ptr(cut), ptr(out["d_cut"]), ptr(out["f_cut"]),
-                                              ptr(out["residual"]), ptr(out["status"]), ptr(out["iters"]), MEM_HOST, None))
+        args = (self._h, n_vox, ptr(y), int(max_iter), ptr(bins), float(height), int(bool(regularized)),
+                float(rel_height), int(max_peaks), ptr(out["n_peaks"]), ptr(out["d_values"]),
+                ptr(out["f_values"]), n_cut, ptr(cut), ptr(out["d_cut"]), ptr(out["f_cut"]),
+                ptr(out["residual"]), ptr(out["status"]), ptr(out["iters"]), MEM_HOST, None)
+        if with_ss_res:
+            out["ss_res"] = np.empty(n_vox)
+            check(load().pnx_nnls_solve_peaks_stats_f64(*args, ptr(out["ss_res"])))
+        else:
+            check(load().pnx_nnls_solve_peaks_f64(*args))
         return out
 
     def close(self):
@@ -217,6 +260,71 @@ class NnlsPlan:
             self.close()
         except Exception:
             pass
+
+
+NNLSPlan = NnlsPlan
+
+PREDICT_MAX_X = 128  # PNX_MAX_BVALUES
+
+
+def predict(model, x, params, fixed_idx=(), fixed_vals=None, y=None, want_pred=True, t1_mode=0, tr=0.0, tm=0.0, device=0, out=None):
+    """Forward model of a parametric layout for all voxels on the device (pnx_curvefit_predict_f64).
+
+    x (n_x <= 128,) need not be the fitted b-values; params (n_free, n_vox) parameter-major as `curvefit` returns popt;
+    fixed_idx / fixed_vals ((n_fixed,) or (n_fixed, n_vox)) as `curvefit` takes them; y (n_vox, n_x) optional signal.
+    Returns dict(pred (n_vox, n_x) or None when not want_pred, ss_res (n_vox,) = sum_i (pred_i - y_i)^2 or None without y).
+    numpy arrays, or torch device tensors for params / per-voxel fixed_vals / y (then the outputs are tensors and the call
+    only enqueues).  `out`: optional dict of preallocated numpy result arrays ("pred", "ss_res")."""
+    tensor = _is_torch(params)
+    x = np.ascontiguousarray(x, np.float64)
+    if x.ndim != 1 or not 1 <= x.size <= PREDICT_MAX_X:
+        raise ValueError(f"x must be 1-D with 1 .. {PREDICT_MAX_X} values, got shape {x.shape}")
+    if not want_pred and y is None:
+        raise ValueError("nothing to compute: want_pred=False and no signal y for ss_res")
+    if model not in MODEL_IDS:
+        raise ValueError(f"unknown model {model!r}")
+    if not tensor:
+        params = np.ascontiguousarray(params, np.float64)
+    fpv = False
+    fv = None
+    if len(fixed_idx):
+        if fixed_vals is None:
+            raise ValueError("fixed_idx without fixed_vals")
+        fv = fixed_vals if _is_torch(fixed_vals) else np.ascontiguousarray(fixed_vals, np.float64)
+        fpv = len(fv.shape) == 2
+    o = make_opts(model, x.size, fixed_idx, False, fpv, jac="analytic", t1_mode=t1_mode, tr=tr, tm=tm)
+    if len(params.shape) != 2 or params.shape[0] != o.n_free:
+        raise ValueError(f"params has shape {tuple(params.shape)}, expected ({o.n_free}, n_vox)")
+    n_vox = int(params.shape[1])
+    if fv is not None and tuple(fv.shape) != ((o.n_fixed, n_vox) if fpv else (o.n_fixed,)):
+        raise ValueError("fixed_vals has the wrong shape")
+    if fv is not None and _is_torch(fv) != (tensor and fpv):
+        raise ValueError("per-voxel fixed_vals live where params live; shared fixed_vals are a host array")
+    if y is not None:
+        if _is_torch(y) != tensor:
+            raise ValueError("y and params must both be numpy arrays or both be device tensors")
+        if not tensor:
+            y = np.ascontiguousarray(np.atleast_2d(y), np.float64)
+        if tuple(y.shape) != (n_vox, x.size):
+            raise ValueError(f"y has shape {tuple(y.shape)}, expected ({n_vox}, {x.size})")
+    if tensor:
+        import torch
+
+        for t in (params, y, fv if fpv else None):
+            if t is not None and (t.dtype != torch.float64 or not t.is_contiguous()):
+                raise ValueError("device tensors must be contiguous float64")
+        pred = torch.empty((n_vox, x.size), dtype=torch.float64, device=params.device) if want_pred else None
+        ss = torch.empty(n_vox, dtype=torch.float64, device=params.device) if y is not None else None
+        device = params.device.index
+        stream = torch.cuda.current_stream(params.device).cuda_stream
+    else:
+        pred = _out(out, "pred", (n_vox, x.size), np.float64) if want_pred else None
+        ss = _out(out, "ss_res", (n_vox,), np.float64) if y is not None else None
+        stream = None
+    _lib.require_device()
+    check(load().pnx_curvefit_predict_f64(C.byref(o), n_vox, int(x.size), ptr(x), ptr(params), ptr(fv), ptr(y), ptr(pred), ptr(ss),
+                                          MEM_DEVICE if tensor else MEM_HOST, int(device), stream))
+    return dict(pred=pred, ss_res=ss)
 
 
 def nnls(basis, reg, y, max_iter=250, device=0, out=None):
@@ -361,6 +469,26 @@ def queue_order_device(key, order, device, stream=None):
 
 def row_ss_tot_device(y, n, c, out, device, stream=None):
     check(load().pnx_row_ss_tot_f64(ptr(y), int(n), int(c), ptr(out), int(device), stream))
+
+
+def row_ss_tot(y, device=0):
+    """sum_j (y_ij - mean_i)^2 per row of a host array (n, c), reduced on the device (pnx_row_ss_tot_f64) in pieces of 2^20 rows:
+    the SS_tot of R^2 (fitters/base.py:179-183)."""
+    import torch
+
+    _lib.require_device()
+    y = np.ascontiguousarray(np.atleast_2d(y), np.float64)
+    n, c = y.shape
+    out = np.empty(n)
+    dev = torch.device("cuda", int(device))
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    for a in range(0, n, 1 << 20):
+        e = min(n, a + (1 << 20))
+        y_d = upload(y[a:e], torch.empty((e - a, c), dtype=torch.float64, device=dev), int(device), stream)
+        ss_d = torch.empty(e - a, dtype=torch.float64, device=dev)
+        row_ss_tot_device(y_d, e - a, c, ss_d, int(device), stream)
+        out[a:e] = download(ss_d, int(device), stream)
+    return out
 
 
 LABEL_TABLE_MAX = 8192  # n_labels * (c + 1) entries of the kernel's 64 KB LDS table

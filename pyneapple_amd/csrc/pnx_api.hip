@@ -20,6 +20,7 @@
 #include "pnx_host_pipeline.hpp"
 #include "pnx_internal.hpp"
 #include "pnx_nnls.hpp"
+#include "pnx_predict.hpp"
 
 namespace pnx {
 
@@ -450,6 +451,35 @@ static void touch(const ArrayTable &A, const Span &s) {  // the result pages of 
     }
 }
 
+// The chunk ring of a host-array call whose kernels keep no state between chunks: three device slots, `launch` enqueues the
+// work of c voxels on the slot's fp64 buffers; widening, narrowing, the page touches and both copies are the table's.
+typedef std::function<int(size_t c, const DevSet &D, hipStream_t st)> ChunkLaunch;
+static int chunk_ring(const ArrayTable &A, size_t nv, size_t chunk, int max_slots, int k_streams, int touchers, int device,
+                      hipStream_t user_stream, const ChunkLaunch &launch) {
+    const std::vector<size_t> bounds = chunk_bounds(nv, chunk, true);
+    const int n_chunks = (int)bounds.size() - 1;
+    const int n_slots = n_chunks < 3 ? n_chunks : max_slots;
+    struct Slot {
+        DevBuf slab;
+        DevSet D;
+    };
+    std::vector<Slot> slots(n_slots);
+    for (auto &S : slots)
+        if (int rc = alloc_carved(S.slab, A, nv < chunk ? nv : chunk, S.D)) return rc;
+    PipeOps ops;
+    ops.h2d = [&](int k, int slot, hipStream_t st) { return h2d(A, slots[slot].D, ring_span(bounds, k), st); };
+    ops.launch = [&](int k, int slot, hipStream_t st) -> int {
+        const DevSet &D = slots[slot].D;
+        const Span s = ring_span(bounds, k);
+        int r;
+        if ((r = widen(A, D, s, st)) || (r = launch(s.c, D, st))) return r;
+        return narrow(A, D, s, st);
+    };
+    ops.touch = [&](int k) { touch(A, ring_span(bounds, k)); };
+    ops.d2h = [&](int k, int slot, hipStream_t st) { return d2h(A, slots[slot].D, ring_span(bounds, k), st); };
+    return run_pipeline(n_chunks, n_slots, k_streams, touchers, device, user_stream, ops);
+}
+
 // ---- host-pointer calls, streamed --------------------------------------------------------------------------------
 // The chunk ring above launches one persistent kernel per chunk, and every one of them ends in a drain tail (lanes whose
 // queue ran dry idle until the slowest voxel of their wave has converged): seven tails cost C3 about 10 ms of its 50.
@@ -826,28 +856,8 @@ static int curvefit_batch(const pnx_curvefit_opts *o, int64_t n_vox, const T *b,
     // float32 transfers are half as long per voxel: a larger chunk (fewer drain tails of the persistent kernel) at the same
     // exposed transfer latency -- C3 float32: 86.3 M voxels/s at 768 Ki, 89.8 M at 1 Mi, 82.5 M at 2 Mi (profiles/host_chunk_sweep_f32.py)
     const size_t chunk = (size_t)dev_env_int("PNX_HOST_CHUNK", F32 ? 1 << 20 : 3 << 18, 1024, 1 << 26);
-    const std::vector<size_t> bounds = chunk_bounds(nv, chunk, true);
-    const int n_chunks = (int)bounds.size() - 1;
-    const int n_slots = n_chunks < 3 ? n_chunks : dev_env_int("PNX_HOST_SLOTS", 3, 2, 8);
-    struct Slot {
-        DevBuf slab;
-        DevSet D;
-    };
-    std::vector<Slot> slots(n_slots);
-    for (auto &S : slots)
-        if ((rc = alloc_carved(S.slab, A, nv < chunk ? nv : chunk, S.D))) return rc;
-    PipeOps ops;
-    ops.h2d = [&](int k, int slot, hipStream_t st) { return h2d(A, slots[slot].D, ring_span(bounds, k), st); };
-    ops.launch = [&](int k, int slot, hipStream_t st) -> int {
-        const DevSet &D = slots[slot].D;
-        const Span s = ring_span(bounds, k);
-        int r;
-        if ((r = widen(A, D, s, st)) || (r = curvefit_on(o, A, sh, D, s.c, dev, st))) return r;
-        return narrow(A, D, s, st);
-    };
-    ops.touch = [&](int k) { touch(A, ring_span(bounds, k)); };
-    ops.d2h = [&](int k, int slot, hipStream_t st) { return d2h(A, slots[slot].D, ring_span(bounds, k), st); };
-    return run_pipeline(n_chunks, n_slots, dev_env_int("PNX_HOST_KSTREAMS", 2, 1, 4), hg.touchers(), device, (hipStream_t)stream, ops);
+    return chunk_ring(A, nv, chunk, dev_env_int("PNX_HOST_SLOTS", 3, 2, 8), dev_env_int("PNX_HOST_KSTREAMS", 2, 1, 4), hg.touchers(), device,
+                      (hipStream_t)stream, [&](size_t c, const DevSet &D, hipStream_t st) { return curvefit_on(o, A, sh, D, c, dev, st); });
 }
 
 extern "C" {
@@ -879,6 +889,45 @@ int pnx_curvefit_batch_f32(const pnx_curvefit_opts *o, int64_t n_vox, const floa
                            const float *lo, const float *hi, const float *fixed, float *popt, float *pcov, int8_t *status,
                            int32_t *nfev, float *cost, int mem, int device, void *stream) {
     return curvefit_batch<float>(o, n_vox, b, y, p0, lo, hi, fixed, popt, pcov, status, nfev, cost, mem, device, stream);
+}
+
+int pnx_curvefit_predict_f64(const pnx_curvefit_opts *o, int64_t n_vox, int n_x, const double *x, const double *params,
+                             const double *fixed, const double *y, double *pred, double *ss_res, int mem, int device, void *stream) {
+    if (!o) return set_error(PNX_ERR_INVALID, "opts is NULL");
+    if (n_x < 1 || n_x > PNX_MAX_BVALUES) return set_error(PNX_ERR_INVALID, "n_x=%d out of range [1,%d]", n_x, PNX_MAX_BVALUES);
+    // the fields predict reads, checked as the fit checks them: n_b, jac_mode and the tolerances are not looked at
+    pnx_curvefit_opts c = *o;
+    c.n_b = n_x;
+    c.jac_mode = PNX_JAC_ANALYTIC;
+    c.ftol = c.xtol = c.gtol = 0.0;
+    int rc = check_curvefit_opts(&c);
+    if (rc) return rc;
+    if (!pred && !ss_res) return set_error(PNX_ERR_INVALID, "pred and ss_res are both NULL");
+    if (ss_res && !y) return set_error(PNX_ERR_INVALID, "ss_res needs the signal y");
+    if (n_vox < 0 || !x || (n_vox && !params)) return set_error(PNX_ERR_INVALID, "NULL data pointer");
+    if (c.n_fixed && !fixed) return set_error(PNX_ERR_INVALID, "fixed is NULL but n_fixed=%d", c.n_fixed);
+    if (mem != PNX_MEM_HOST && mem != PNX_MEM_DEVICE) return set_error(PNX_ERR_INVALID, "mem=%d", mem);
+    if (n_vox == 0) return PNX_OK;
+    DeviceInfo *dev;
+    if ((rc = get_device(device, &dev))) return rc;
+    PNX_HIP(hipSetDevice(device));
+    hipStream_t st = (hipStream_t)stream;
+    if (!ss_res) y = nullptr;
+    if (mem == PNX_MEM_DEVICE) return model_predict_device(&c, n_vox, n_x, x, params, fixed, y, pred, ss_res, st);
+    const bool fpv = c.n_fixed && c.fixed_per_voxel;
+    enum { PR_P, PR_FX, PR_Y, PR_PRED, PR_SS };
+    ArrayTable A;
+    A.add(params, sizeof(double), c.n_free, false).pmajor = true;
+    A.add(fpv ? fixed : nullptr, sizeof(double), c.n_fixed, false).pmajor = true;
+    A.add(y, sizeof(double), n_x, false);
+    A.add(pred, sizeof(double), n_x, true);
+    A.add(ss_res, sizeof(double), 1, true);
+    HostCallGuard hg;
+    return chunk_ring(A, (size_t)n_vox, (size_t)dev_env_int("PNX_PREDICT_HOST_CHUNK", 3 << 18, 1024, 1 << 22), 3, 2, hg.touchers(), device, st,
+                      [&](size_t n, const DevSet &D, hipStream_t s) {
+                          return model_predict_device(&c, (int64_t)n, n_x, x, D.d(PR_P), fpv ? D.d(PR_FX) : fixed, D.d(PR_Y), D.d(PR_PRED),
+                                                      D.d(PR_SS), s);
+                      });
 }
 
 // ------------------------------------------------------------------------------------------- NNLS
@@ -918,13 +967,14 @@ int pnx_nnls_plan_destroy(pnx_nnls_plan *plan) {
 }  // extern "C"
 
 // the arrays of an NNLS call, in table order: the signal, the spectra, the solver's per-voxel outputs, the peak tables
-enum { NN_Y, NN_SPEC, NN_RNORM, NN_STAT, NN_ITERS, NN_NPEAKS, NN_D, NN_F, NN_DC, NN_FC };
+enum { NN_Y, NN_SPEC, NN_RNORM, NN_STAT, NN_ITERS, NN_NPEAKS, NN_D, NN_F, NN_DC, NN_FC, NN_SS };
 struct NnlsHostCall {
     ArrayTable A;          // NN_* order; the spectra are downloaded (solve) or only analysed on the device (solve_peaks)
     size_t chunk = 0;      // voxels per chunk of the ring
     bool ramp = false;     // quarter-chunk ramp at both ends (chunk_bounds)
     bool overlap = false;  // the first deferred pass runs behind the last chunk's solve, beside its download (else after the ring)
-    std::function<int(size_t n, const DevSet &D, hipStream_t s)> post;  // behind every solve, on its stream (may be empty)
+    // behind every solve, on its stream (may be empty); y: the n signal rows on the device (the deferred pass has them in its side buffer)
+    std::function<int(size_t n, const double *y, const DevSet &D, hipStream_t s)> post;
 };
 
 // NNLS from host arrays: the chunk ring of the curve fit with ONE kernel stream -- the plan's device scratch (ATY chunk, M
@@ -1014,7 +1064,7 @@ static int nnls_host(NnlsPlanData &P, size_t nv, int max_iter, const NnlsHostCal
         } else {
             r = nnls_solve_device(&P, (int64_t)sp.c, D.d(NN_Y), max_iter, D.d(NN_SPEC), D.d(NN_RNORM), stat, iters, s);
         }
-        if (!r && C.post) r = C.post(sp.c, D, s);
+        if (!r && C.post) r = C.post(sp.c, D.d(NN_Y), D, s);
         return r ? r : narrow(A, D, sp, s);
     };
     ops.touch = [&](int k) { touch(A, ring_span(bounds, k)); };
@@ -1051,7 +1101,7 @@ static int nnls_host(NnlsPlanData &P, size_t nv, int max_iter, const NnlsHostCal
             PNX_HIP(hipMemcpy(dctx.y_side, y_rows.data(), y_rows.size() * sizeof(double), hipMemcpyHostToDevice));
         }
         if ((b0 > 0 || !C.overlap) && (rc = redo(nb))) return rc;
-        if (C.post && (rc = C.post(nb, side, ss.s))) return rc;
+        if (C.post && (rc = C.post(nb, dctx.y_side, side, ss.s))) return rc;
         PNX_HIP(hipStreamSynchronize(ss.s));
         for (int k = 0; k < A.n; ++k)
             if (rows[k]) PNX_HIP(hipMemcpy((void *)rows[k], side.dev[k], nb * A.a[k].w * (A.a[k].widen ? sizeof(double) : A.a[k].esize), hipMemcpyDeviceToHost));
@@ -1125,10 +1175,11 @@ int pnx_nnls_solve_f32(pnx_nnls_plan *plan, int64_t n_vox, const float *y, int m
     return nnls_solve<float>(plan, n_vox, y, max_iter, coeff, rnorm, status, iters, mem, stream);
 }
 
-int pnx_nnls_solve_peaks_f64(pnx_nnls_plan *plan, int64_t n_vox, const double *y, int max_iter, const double *bins_host,
-                             double height, int regularized, double rel_height, int max_peaks, int32_t *n_peaks,
-                             double *d_values, double *f_values, int n_cut, const double *cutoffs_host, double *d_cut,
-                             double *f_cut, double *rnorm, int8_t *status, int32_t *iters, int mem, void *stream) {
+// solve -> [data-term residual] -> peak table per chunk, while the chunk's spectra are resident; ss_res null: no residual pass
+static int nnls_solve_peaks(pnx_nnls_plan *plan, int64_t n_vox, const double *y, int max_iter, const double *bins_host,
+                            double height, int regularized, double rel_height, int max_peaks, int32_t *n_peaks,
+                            double *d_values, double *f_values, int n_cut, const double *cutoffs_host, double *d_cut,
+                            double *f_cut, double *rnorm, int8_t *status, int32_t *iters, int mem, void *stream, double *ss_res) {
     if (!plan) return set_error(PNX_ERR_INVALID, "plan is NULL");
     if (n_vox < 0 || (n_vox && (!y || !rnorm))) return set_error(PNX_ERR_INVALID, "NULL data pointer");
     if (mem != PNX_MEM_HOST && mem != PNX_MEM_DEVICE) return set_error(PNX_ERR_INVALID, "mem=%d", mem);
@@ -1157,8 +1208,11 @@ int pnx_nnls_solve_peaks_f64(pnx_nnls_plan *plan, int64_t n_vox, const double *y
         C.A.add(max_peaks > 0 ? f_values : nullptr, sizeof(double), mp, true).always = true;
         C.A.add(n_cut > 0 ? d_cut : nullptr, sizeof(double), nc, true).always = true;
         C.A.add(n_cut > 0 ? f_cut : nullptr, sizeof(double), nc, true).always = true;
+        C.A.add(ss_res, sizeof(double), 1, true);
         C.chunk = (size_t)dev_env_int("PNX_NNLS_PEAKS_CHUNK", 3 << 18, 1024, 1 << 22);
-        C.post = [&](size_t n, const DevSet &D, hipStream_t s) {
+        C.post = [&](size_t n, const double *y_d, const DevSet &D, hipStream_t s) {
+            if (ss_res)
+                if (int r = nnls_fit_stats_device(&P, (int64_t)n, y_d, D.d(NN_SPEC), D.d(NN_SS), nullptr, s)) return r;
             return pnx_nnls_spectrum_peaks_f64((int64_t)n, P.n_bins, D.d(NN_SPEC), bins_host, height, regularized, rel_height, max_peaks,
                                                (int32_t *)D.dev[NN_NPEAKS], D.d(NN_D), D.d(NN_F), n_cut, cutoffs_host, D.d(NN_DC),
                                                D.d(NN_FC), PNX_MEM_DEVICE, P.device, s);
@@ -1175,6 +1229,7 @@ int pnx_nnls_solve_peaks_f64(pnx_nnls_plan *plan, int64_t n_vox, const double *y
         if ((rc = nnls_solve_device(&P, (int64_t)n, y + off * P.n_meas, max_iter, (double *)spec.p, rnorm + off,
                                     status ? status + off : nullptr, iters ? iters + off : nullptr, st)))
             return rc;
+        if (ss_res && (rc = nnls_fit_stats_device(&P, (int64_t)n, y + off * P.n_meas, (const double *)spec.p, ss_res + off, nullptr, st))) return rc;
         rc = pnx_nnls_spectrum_peaks_f64((int64_t)n, P.n_bins, (const double *)spec.p, bins_host, height, regularized, rel_height,
                                          max_peaks, n_peaks ? n_peaks + off : nullptr, d_values ? d_values + off * max_peaks : nullptr,
                                          f_values ? f_values + off * max_peaks : nullptr, n_cut, cutoffs_host,
@@ -1185,6 +1240,50 @@ int pnx_nnls_solve_peaks_f64(pnx_nnls_plan *plan, int64_t n_vox, const double *y
     }
     PNX_HIP(hipStreamSynchronize(st));  // the scratch buffer is freed on return
     return PNX_OK;
+}
+
+int pnx_nnls_solve_peaks_f64(pnx_nnls_plan *plan, int64_t n_vox, const double *y, int max_iter, const double *bins_host,
+                             double height, int regularized, double rel_height, int max_peaks, int32_t *n_peaks,
+                             double *d_values, double *f_values, int n_cut, const double *cutoffs_host, double *d_cut,
+                             double *f_cut, double *rnorm, int8_t *status, int32_t *iters, int mem, void *stream) {
+    return nnls_solve_peaks(plan, n_vox, y, max_iter, bins_host, height, regularized, rel_height, max_peaks, n_peaks, d_values, f_values,
+                            n_cut, cutoffs_host, d_cut, f_cut, rnorm, status, iters, mem, stream, nullptr);
+}
+
+int pnx_nnls_solve_peaks_stats_f64(pnx_nnls_plan *plan, int64_t n_vox, const double *y, int max_iter, const double *bins_host,
+                                   double height, int regularized, double rel_height, int max_peaks, int32_t *n_peaks,
+                                   double *d_values, double *f_values, int n_cut, const double *cutoffs_host, double *d_cut,
+                                   double *f_cut, double *rnorm, int8_t *status, int32_t *iters, int mem, void *stream,
+                                   double *ss_res) {
+    if (n_vox > 0 && !ss_res) return set_error(PNX_ERR_INVALID, "ss_res is NULL");
+    return nnls_solve_peaks(plan, n_vox, y, max_iter, bins_host, height, regularized, rel_height, max_peaks, n_peaks, d_values, f_values,
+                            n_cut, cutoffs_host, d_cut, f_cut, rnorm, status, iters, mem, stream, ss_res);
+}
+
+int pnx_nnls_fit_stats_f64(pnx_nnls_plan *plan, int64_t n_vox, const double *y, const double *coeff, double *ss_res, double *pred,
+                           int mem, int device, void *stream) {
+    if (!plan) return set_error(PNX_ERR_INVALID, "plan is NULL");
+    if (!ss_res && !pred) return set_error(PNX_ERR_INVALID, "ss_res and pred are both NULL");
+    if (n_vox < 0 || (n_vox && (!coeff || (ss_res && !y)))) return set_error(PNX_ERR_INVALID, "NULL data pointer");
+    if (mem != PNX_MEM_HOST && mem != PNX_MEM_DEVICE) return set_error(PNX_ERR_INVALID, "mem=%d", mem);
+    const NnlsPlanData &P = plan->d;
+    if (device != P.device) return set_error(PNX_ERR_INVALID, "device %d, but the plan lives on device %d", device, P.device);
+    if (n_vox == 0) return PNX_OK;
+    PNX_HIP(hipSetDevice(P.device));
+    hipStream_t st = (hipStream_t)stream;
+    if (mem == PNX_MEM_DEVICE) return nnls_fit_stats_device(&P, n_vox, y, coeff, ss_res, pred, st);
+    // the kernel only reads the plan (its padded basis): no lock, two kernel streams
+    enum { FS_Y, FS_X, FS_SS, FS_PRED };
+    ArrayTable A;
+    A.add(ss_res ? y : nullptr, sizeof(double), P.n_meas, false);
+    A.add(coeff, sizeof(double), P.n_bins, false);
+    A.add(ss_res, sizeof(double), 1, true);
+    A.add(pred, sizeof(double), P.n_meas, true);
+    HostCallGuard hg;
+    return chunk_ring(A, (size_t)n_vox, (size_t)dev_env_int("PNX_STATS_HOST_CHUNK", 1 << 18, 1024, 1 << 22), 3, 2, hg.touchers(), P.device, st,
+                      [&](size_t c, const DevSet &D, hipStream_t s) {
+                          return nnls_fit_stats_device(&P, (int64_t)c, D.d(FS_Y), D.d(FS_X), D.d(FS_SS), D.d(FS_PRED), s);
+                      });
 }
 
 int pnx_nnls_aty_f64(pnx_nnls_plan *plan, int64_t n_vox, const double *y_dev, double *aty_dev, void *stream) {

@@ -183,17 +183,22 @@ class HipFitterBase(_FitterBase):
             success = status == 1
             coeffs = np.atleast_2d(s.params_["coefficients"])
             basis = np.asarray(s.model.get_basis(xdata))
-            ss_res = np.empty(n_px)
-            for a in range(0, n_px, 1 << 18):
-                e = min(n_px, a + (1 << 18))
-                ss_res[a:e] = np.sum((pixels[a:e] - coeffs[a:e] @ basis.T) ** 2, axis=1)
+            if self.device_stats:
+                ss_res = self._nnls_stats(basis, pixels, coeffs)["ss_res"]
+            else:
+                ss_res = np.empty(n_px)
+                for a in range(0, n_px, 1 << 18):
+                    e = min(n_px, a + (1 << 18))
+                    ss_res[a:e] = np.sum((pixels[a:e] - coeffs[a:e] @ basis.T) ** 2, axis=1)
             covariance, residuals = None, np.atleast_1d(d["residual"]).astype(np.float64)
         else:
             status = np.asarray(d["status"])
             success = status > 0
             ss_res = 2.0 * np.atleast_1d(d["cost"]).astype(np.float64)  # cost = 0.5 * sum(res^2) at the returned x
             bad = ~success
-            if bad.any():  # failed voxels return p0: evaluate the model there (a handful of voxels)
+            if bad.any() and self.device_stats:  # failed voxels return p0: the predict kernel's residual there
+                ss_res[bad] = self._curvefit_predict(xdata, np.nonzero(bad)[0], y=pixels[bad], want_pred=False)["ss_res"]
+            elif bad.any():  # failed voxels return p0: evaluate the model there (a handful of voxels)
                 names = list(self.fitted_params_.keys())
                 arr = np.stack([np.atleast_1d(self.fitted_params_[n]) for n in names])[:, bad]
                 fixed = getattr(s.model, "fixed_params", None) or {}
@@ -215,6 +220,10 @@ class HipFitterBase(_FitterBase):
             msgs = [None] * n_px
             for i in np.nonzero(~success)[0]:
                 msgs[i] = view[int(i)].message
+        if ss_tot is None and self.device_stats:
+            from . import api
+
+            ss_tot = api.row_ss_tot(pixels, getattr(s, "device", 0))
         if ss_tot is None:
             ss_tot = _ss_tot(pixels)
         with np.errstate(divide="ignore", invalid="ignore"):
@@ -225,6 +234,42 @@ class HipFitterBase(_FitterBase):
                          n_pixels=n_px, solver_name=type(s).__name__, model_name=type(s.model).__name__)
 
     _pixel_fixed = None  # per-pixel fixed parameter columns of the last fit (HipPixelWiseFitter sets it)
+
+    @property
+    def device_stats(self) -> bool:
+        """Constructor keyword `device_stats=True`: SS_res of an NNLS fit (pnx_nnls_fit_stats_f64), SS_res of failed curve-fit
+        voxels (pnx_curvefit_predict_f64) and SS_tot (pnx_row_ss_tot_f64) are reduced on the device instead of in numpy."""
+        return bool((getattr(self, "fitter_kwargs", None) or {}).get("device_stats", False))
+
+    def _nnls_stats(self, basis, pixels, coeffs, want_pred=False):
+        from . import api
+
+        plan = api.NnlsPlan(basis, None, getattr(self.solver, "device", 0))
+        try:
+            return plan.fit_stats(pixels, coeffs, want_pred=want_pred)
+        finally:
+            plan.close()
+
+    def _curvefit_predict(self, xdata, rows=None, y=None, want_pred=True):
+        """api.predict on the fitted parameters (of the voxels `rows`, default all): free columns from fitted_params_, per-pixel
+        fixed maps and the model's scalar fixed parameters as the fit took them."""
+        from . import api
+        from .solvers import kernel_model_key, kernel_t1
+
+        s = self.solver
+        all_names = list(s.model._all_param_names)
+        pix = self._pixel_fixed or {}
+        scalar = dict(getattr(s.model, "fixed_params", None) or {}) if not pix else {}
+        sel = (lambda v: np.atleast_1d(v)) if rows is None else (lambda v: np.atleast_1d(v)[rows])
+        fixed_idx = [i for i, n in enumerate(all_names) if n in pix or n in scalar]
+        free = [n for n in all_names if n not in pix and n not in scalar]
+        params = np.ascontiguousarray(np.stack([sel(self.fitted_params_[n]) for n in free]), np.float64)
+        if pix:
+            fixed_vals = np.ascontiguousarray(np.stack([sel(pix[all_names[i]]) for i in fixed_idx]), np.float64)
+        else:
+            fixed_vals = np.array([float(scalar[all_names[i]]) for i in fixed_idx]) if fixed_idx else None
+        return api.predict(kernel_model_key(s.model), xdata, params, fixed_idx=fixed_idx, fixed_vals=fixed_vals, y=y,
+                           want_pred=want_pred, device=getattr(s, "device", 0), **kernel_t1(s.model))
 
     def _reconstruct_volume(self, flat_values, pixel_indices, spatial_shape):
         """fitters/base.py:310-331 with an (n_px, 3) index array instead of a list of tuples."""
@@ -270,13 +315,21 @@ class HipFitterBase(_FitterBase):
         args = [cols[n][:, None] if n in cols else np.full((n_px, 1), float(fixed[n])) for n in s.model._all_param_names]
         return s.model.forward(xdata[None, :], *args)
 
-    def predict(self, xdata, **predict_kwargs):
-        """(X, Y, Z, len(xdata)) volume of model predictions, zeros outside the fitted voxels (fitters/base.py:90-131)."""
+    def predict(self, xdata, on_device: bool = False, **predict_kwargs):
+        """(X, Y, Z, len(xdata)) volume of model predictions, zeros outside the fitted voxels (fitters/base.py:90-131).
+        on_device: the forward model runs on the GPU (pnx_nnls_fit_stats_f64 / pnx_curvefit_predict_f64, at most 128 x-values for
+        a parametric model) instead of in numpy."""
         self._check_fitted()
         xdata = np.asarray(xdata, float)
         if xdata.ndim != 1:
             raise ValueError(f"xdata must be a 1D array of independent variable values, got shape {xdata.shape}.")
-        pred = self.predict_pixels(xdata)
+        if not on_device:
+            pred = self.predict_pixels(xdata)
+        elif "coefficients" in self.fitted_params_:
+            basis = np.asarray(self.solver.model.get_basis(xdata), float)
+            pred = self._nnls_stats(basis, None, np.atleast_2d(self.fitted_params_["coefficients"]), want_pred=True)["pred"]
+        else:
+            pred = self._curvefit_predict(xdata)["pred"]
         return self._reconstruct_volume(pred, self.pixel_indices, tuple(self.image_shape[:-1]) + (xdata.size,))
 
 

@@ -390,12 +390,14 @@ class HipNNLSSolver(NNLSBase):
         return np.concatenate((signal, np.zeros((signal.shape[0], self.model.n_bins))), axis=1)
 
     def fit_peaks(self, xdata: np.ndarray, signal: np.ndarray, height: float = 0.1, cutoffs=None, max_peaks: int = 8,
-                  regularized: bool | None = None) -> "HipNNLSSolver":
+                  regularized: bool | None = None, r_squared: bool = False) -> "HipNNLSSolver":
         """Fit and reduce every spectrum to its peak table on the device (pnx_nnls_solve_peaks_f64): what a caller of the
         reference does with `fit` followed by a Python loop over `find_spectrum_peaks` / `apply_cutoffs`
         (utility/spectrum.py:51-215), without the (n_pixels, n_bins) coefficient array -- 8.4 GB for a 256 x 256 x 64
         volume -- crossing PCIe.  `regularized` defaults to reg_order != 0 (spectrum.py:68-71).
-        params_: "d_values", "f_values" (n_pixels, max_peaks) NaN padded, "n_peaks", and with `cutoffs` "d_cut", "f_cut"."""
+        params_: "d_values", "f_values" (n_pixels, max_peaks) NaN padded, "n_peaks", and with `cutoffs` "d_cut", "f_cut".
+        r_squared: also reduce every spectrum's data-term residual while it is resident (pnx_nnls_solve_peaks_stats_f64) and
+        SS_tot on the device; diagnostics_ then carries "ss_res" and "r_squared" (NaN for a constant signal, fitters/base.py:179-183)."""
         self._reset_state()
         xdata = np.asarray(xdata, float)
         signal = np.asarray(signal, float)
@@ -410,13 +412,18 @@ class HipNNLSSolver(NNLSBase):
             res = plan.solve_peaks(np.ascontiguousarray(signal), np.asarray(self.model.bins, float),
                                    int(self.max_iter) if self.max_iter else 0, height=height,
                                    regularized=bool(self.reg_order) if regularized is None else regularized,
-                                   max_peaks=max_peaks, cutoffs=cutoffs)
+                                   max_peaks=max_peaks, cutoffs=cutoffs, **({"with_ss_res": True} if r_squared else {}))
         finally:
             plan.close()
         for key in ("d_values", "f_values", "n_peaks", "d_cut", "f_cut"):
             if res[key] is not None:
                 self.params_[key] = res[key]
         self.diagnostics_.update(residual=res["residual"], status=res["status"], iters=res["iters"])
+        if r_squared:
+            ss_tot = api.row_ss_tot(signal, self.device)
+            with np.errstate(divide="ignore", invalid="ignore"):
+                r2 = np.where(ss_tot > 0, 1.0 - res["ss_res"] / ss_tot, np.nan)
+            self.diagnostics_.update(ss_res=res["ss_res"], r_squared=r2)
         return self
 
     def fit(self, xdata: np.ndarray, signal: np.ndarray, pixel_fixed_params=None, **kwargs) -> "HipNNLSSolver":
