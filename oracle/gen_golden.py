@@ -9,7 +9,7 @@ seeded synthetic inputs and stores inputs + outputs as small ``.npz`` fixtures
 under ``tests/golden/``.  Only data is written; no reference source travels.
 
 Run (from any cwd):  python3 oracle/gen_golden.py            (batches g1-g9)
-                     python3 oracle/gen_golden.py g10 | g11 | g12   (later batches, each with its own seed)
+                     python3 oracle/gen_golden.py g10 | g11 | g12 | g14   (later batches, each with its own seed)
 """
 from __future__ import annotations
 
@@ -531,8 +531,105 @@ def main_g12():
                  solver_kwargs=dict(sigma=4.0 * (1.0 + np.linspace(0.0, 1200.0, 24) / 300.0), absolute_sigma=True))
 
 
+def adversarial_rows(n, n_rows, rng):
+    """Constructed spectra for main_g14, (n_rows, n): at most 16 peaks each, six kinds in turn.  Anchor bins a < b < c (n // 4,
+    n // 2, 3 n // 4) carry peaks in the comb rows, so that cutoff ends placed on bins[a], bins[b], bins[c] sit on peaks."""
+    a, b, c = n // 4, n // 2, 3 * n // 4
+    j = np.arange(n)
+
+    def bumps(k_max, centres=()):
+        x = np.zeros(n)
+        for cen in list(centres) + [int(rng.integers(0, n)) for _ in range(int(rng.integers(1, k_max + 1)))]:
+            x += rng.uniform(0.3, 50) * np.exp(-0.5 * ((j - cen) / rng.uniform(0.6, 12)) ** 2)
+        x[x < 1e-3] = 0.0  # NNLS spectra are exactly zero between the peaks
+        return x
+
+    def comb(plateaus):
+        x = np.zeros(n)
+        cluster = [a - 6, a - 3, a, b, c]  # three peaks below and on bins[a]: several peaks inside one range
+        free = [p for p in range(3, n - 4, 4) if min(abs(p - q) for q in cluster) >= 4]
+        pos = cluster + [int(p) for p in rng.choice(free, int(rng.integers(0, 12)), replace=False)]
+        for i, p in enumerate(pos):
+            amp = rng.uniform(3, 40) if i < len(cluster) else rng.uniform(0.15, 40)
+            x[p] = amp
+            if plateaus and i % 2 == 0:
+                x[p + 1] = amp  # a flat top of two samples: the peak is its left sample (midpoint rule)
+        return x
+
+    rows = []
+    for k in range(n_rows):
+        kind = k % 6
+        if kind == 0:    # flat top on the highest bump
+            x = bumps(6)
+            i = int(np.argmax(x))
+            x[max(i - 2, 1):i + 3] = x[i]
+        elif kind == 1:  # smooth bumps, the wave path
+            x = bumps(6)
+        elif kind == 2:  # isolated spikes, the wave path with merged ranges
+            x = comb(False)
+        elif kind == 3:  # the same with flat tops: the one-lane path with merged ranges
+            x = comb(True)
+        elif kind == 4:  # one decimal: many exact ties
+            x = np.round(bumps(5), 1)
+        else:            # bumps centred on the anchors, every other row with a three-sample plateau on a shoulder
+            x = bumps(2, centres=(a, b, c))
+            if k % 12 == 5:
+                s = min(a + 5, n - 3)
+                x[s:s + 3] = x[s + 1] + 1.0
+        rows.append(x)
+    return np.array(rows)
+
+
+def main_g14():
+    """Ninth batch: the reference's find_spectrum_peaks + apply_cutoffs on constructed rows that reach what no NNLS spectrum of
+    the g9 / g11 fixtures does: flat-topped rises, several peaks inside one cutoff range on such a row, overlapping, nested and
+    empty ranges, a range end equal to a bin value that carries a peak.  Bins are the reference's own (the g9 / g11 NNLS
+    fixtures, d_range (0.0008, 0.5)); at most 16 peaks per row, inside the table of the device's one-lane path."""
+    from pyneapple.utility.spectrum import apply_cutoffs, find_spectrum_peaks
+
+    rng = np.random.default_rng(SEED + 14)
+    MAXP, NROWS = 16, 48
+    for src in ("g9_nnls_250_r0", "g11_nnls_300_r2", "g11_nnls_512_r2"):
+        bins = np.load(os.path.join(OUT, src + ".npz"))["bins"]
+        n = len(bins)
+        spec = adversarial_rows(n, NROWS, rng)
+        a, b, c = n // 4, n // 2, 3 * n // 4
+        mid = lambda i: 0.5 * (bins[i] + bins[i + 1])
+        disjoint = [(bins[0], bins[a]), (mid(a), bins[b]), (mid(b), 0.5), (0.6, 0.9)]           # an end on a peak's bin; an empty range
+        overlap = [(bins[0], bins[b]), (bins[a], bins[-1]), (bins[c], bins[c]), (0.02, 0.003)]  # overlapping, nested, inverted
+        for regularized in (False, True):
+            for height in (0.1, 2.0):
+                overlapping = regularized != (height == 2.0)
+                cutoffs = overlap if overlapping else disjoint
+                n_peaks = np.zeros(NROWS, dtype=np.int32)
+                dv = np.full((NROWS, MAXP), np.nan)
+                fv = np.full((NROWS, MAXP), np.nan)
+                dc = np.full((NROWS, len(cutoffs)), np.nan)
+                fc = np.full((NROWS, len(cutoffs)), np.nan)
+                for i in range(NROWS):
+                    dd, ff = find_spectrum_peaks(spec[i], bins, height=height, regularized=regularized)
+                    assert len(dd) <= MAXP
+                    n_peaks[i] = len(dd)
+                    dv[i, :len(dd)] = dd
+                    fv[i, :len(dd)] = ff
+                    dc[i], fc[i] = apply_cutoffs(dd, ff, cutoffs)
+                name = f"g14_spectrum_adversarial_{n}_r{int(regularized)}_h{height:g}".replace(".", "p")
+                np.savez_compressed(os.path.join(OUT, name + ".npz"), spectrum=spec, bins=bins, height=height,
+                                    regularized=np.array(regularized), n_peaks=n_peaks, d_values=dv, f_values=fv,
+                                    cutoffs=np.array(cutoffs), overlapping_cutoffs=np.array(overlapping), d_cut=dc, f_cut=fc,
+                                    **_versions())
+                print(f"{name}: peaks/row mean {n_peaks.mean():.2f} max {n_peaks.max()}")
+
+
 if __name__ == "__main__":
-    if len(sys.argv) > 1 and sys.argv[1] == "g12":
+    if len(sys.argv) > 1 and sys.argv[1] == "g14":
+        os.environ.setdefault("PYNEAPPLE_QUIET", "1")
+        sys.dont_write_bytecode = True
+        sys.path.insert(0, REF_SRC)
+        _install_shims()
+        os.makedirs(OUT, exist_ok=True)
+        main_g14()
+    elif len(sys.argv) > 1 and sys.argv[1] == "g12":
         os.environ.setdefault("PYNEAPPLE_QUIET", "1")
         sys.dont_write_bytecode = True
         sys.path.insert(0, REF_SRC)

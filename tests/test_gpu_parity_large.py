@@ -93,6 +93,16 @@ def test_nnls_fuzz_wide_40_cases(gpu, oracle):
     assert r["rnorm_disagreements"] <= 2, r
 
 
+def test_spectrum_fuzz_100_cases(gpu):
+    """Random spectra, bin counts (3..512), heights, rel_height, table sizes and cutoff ranges through the peak / width / cutoff
+    kernels against scipy.signal (tests/fuzz_spectrum_vs_scipy.py): no row differs, and the draw reaches the one-lane path and
+    the table limits."""
+    r = _load("tests/fuzz_spectrum_vs_scipy.py", "fuzz_spectrum").run(100, seed=20261017, verbose=True)
+    assert r["failing_cases"] == 0 and r["differing_rows"] == 0, r
+    assert r["rows"] > 3000 and r["rows_with_peaks"] > 1500, r
+    assert r["one_lane_rows"] > 300 and r["table_overflow_rows"] > 20, r
+
+
 def test_streamed_host_path_fuzz_40_cases(gpu):
     """Random configurations of the streamed host path against the chunk ring (tests/fuzz_stream_vs_ring.py): bit-identical
     outputs, no watermark time-out, streamed exactly when the batch has two or more granules."""
