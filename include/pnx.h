@@ -194,6 +194,30 @@ PNX_API int pnx_curvefit_batch_f32(const pnx_curvefit_opts *opts, int64_t n_vox,
                            int8_t *status, int32_t *nfev, float *cost, int mem, int device, void *stream);
 
 /*
+ * The same bounded TRF fit with fp32 ARITHMETIC: a second, independent kernel whose every operation of the iteration is float
+ * (native v_exp_f32, half the registers per lane, two waves per SIMD).  Argument list of pnx_curvefit_batch_f32, float arrays
+ * in and out; PNX_MEM_DEVICE only enqueues, PNX_MEM_HOST goes through the chunk ring.  Statuses, failure sentinels (popt = p0,
+ * NaN pcov) and the meaning of max_nfev are those of pnx_curvefit_batch_f64.  Results are minima as good as float32 arithmetic
+ * allows, NOT SciPy-parity results (measured agreement: DESIGN.md).  Differences from the fp64 fit:
+ *   - analytic Jacobian only (SciPy's 2-point step of 1.5e-8 is below fp32 resolution);
+ *   - tolerances below fp32 resolution cannot be honoured and are raised to floors (FLT_EPSILON = 2^-23 = 1.19e-7):
+ *       ftol -> max(ftol, 4 FLT_EPSILON),  xtol -> max(xtol, FLT_EPSILON)  (a smaller step does not change a float);
+ *     gtol is an ABSOLUTE test on the scaled gradient and has no floor that fits every signal amplitude: it is used as given --
+ *     one below the gradient's rounding noise never fires and the fit ends through the tests above (a floor of 4 FLT_EPSILON
+ *     was measured to stop noise-free unit-amplitude voxels 10 to 900 times the rounding cost above their minimum);
+ *     besides SciPy's ftol test, a step whose predicted AND actual cost change both lie below
+ *     ftol * cost + n_b (FLT_EPSILON max|y|)^2 / 8  (the second term is a quarter of the cost of fp32 rounding of the model
+ *     itself) ends the fit with status 2 instead of shrinking the trust radius until xtol trips;
+ *   - a start value on a bound is moved 8 FLT_EPSILON max(1, |bound|) inside (SciPy: 1e-10);
+ *   - pcov drops singular values below FLT_EPSILON max(n_b, n_free) s_max (SciPy: the fp64 epsilon); the epilogue is fp64.
+ * Not built, PNX_ERR_UNSUPPORTED with a message: fixed parameters (fixed must be NULL), the T1 / STEAM factor, sigma,
+ * queue_order, PNX_JAC_FD.
+ */
+PNX_API int pnx_curvefit_fast_f32(const pnx_curvefit_opts *opts, int64_t n_vox, const float *b, const float *y, const float *p0,
+                          const float *lo, const float *hi, const float *fixed, float *popt, float *pcov,
+                          int8_t *status, int32_t *nfev, float *cost, int mem, int device, void *stream);
+
+/*
  * NNLS plan: everything that is shared by all voxels of one fit -- the regularised design matrix
  * A = [basis; reg] (nnls_solver.py:61-73) -- is uploaded and factored into its Gram form once.
  *   basis (n_meas, n_bins) row-major host;  reg (n_reg, n_bins) row-major host or NULL (n_reg = 0).

@@ -29,8 +29,9 @@ NNLS_FLAGS = os.environ.get("PNX_NNLS_FLAGS", "").split()  # e.g. -DPNX_NNLS_GBA
 # measured on, and bench.py only replays counters whose stamp matches the sources it is running
 SOURCE_GROUPS = {
     "curvefit": ["pnx_curvefit_kernel.hpp", "pnx_curvefit_inst.hip"],
+    "curvefit_f32": ["pnx_curvefit_f32_kernel.hpp", "pnx_curvefit_f32.hip", "pnx_model_t.hpp"],
     "nnls": ["pnx_nnls.hip", "pnx_nnls.hpp", "pnx_nnls_dev.hpp", "pnx_nnls_qr.hip", "pnx_nnls_blk.hip", "pnx_nnls_blk_kernel.hpp"],
-    "sweep": ["pnx_sweep.hip"],
+    "sweep": ["pnx_sweep.hip", "pnx_model_t.hpp"],
     "predict": ["pnx_predict.hip", "pnx_predict.hpp"],
     # the host boundary (streamed path, chunk ring, deferred NNLS hand-over, peak tables): host-mode / PCIe-inclusive figures and
     # the host-path fuzz summaries are stamped with this id, so that they are not replayed as current after pnx_api.hip changes
@@ -58,7 +59,8 @@ def _units():
     units = [("pnx_api.o", "pnx_api.hip", []), ("pnx_nnls.o", "pnx_nnls.hip", NNLS_FLAGS), ("pnx_nnls_qr.o", "pnx_nnls_qr.hip", NNLS_FLAGS),
              ("pnx_nnls_blk.o", "pnx_nnls_blk.hip", NNLS_FLAGS),
              ("pnx_sweep.o", "pnx_sweep.hip", []), ("pnx_spectrum.o", "pnx_spectrum.hip", []),
-             ("pnx_resize.o", "pnx_resize.hip", []), ("pnx_predict.o", "pnx_predict.hip", [])]
+             ("pnx_resize.o", "pnx_resize.hip", []), ("pnx_predict.o", "pnx_predict.hip", []),
+             ("pnx_curvefit_f32.o", "pnx_curvefit_f32.hip", CURVEFIT_FLAGS)]
     for m in range(N_MODELS):
         units.append((f"pnx_curvefit_m{m}.o", "pnx_curvefit_inst.hip", [f"-DPNX_MODEL={m}", *CURVEFIT_FLAGS]))
     return [u for u in units if os.path.exists(os.path.join(CSRC, u[1]))]

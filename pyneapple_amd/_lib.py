@@ -26,7 +26,7 @@ ABI_SYMBOLS = [
     "pnx_resize2d_f64", "pnx_ideal_bounds_f64", "pnx_nnls_spectrum_peaks_f64", "pnx_nnls_solve_peaks_f64", "pnx_scatter_maps_f32",
     "pnx_mask_select_f64", "pnx_gather_rows_f64", "pnx_scatter_rows_t_f64", "pnx_row_ss_tot_f64", "pnx_upload", "pnx_download",
     "pnx_label_sums_f64", "pnx_release_staging", "pnx_queue_order_f64",
-    "pnx_nnls_fit_stats_f64", "pnx_nnls_solve_peaks_stats_f64", "pnx_curvefit_predict_f64",
+    "pnx_nnls_fit_stats_f64", "pnx_nnls_solve_peaks_stats_f64", "pnx_curvefit_predict_f64", "pnx_curvefit_fast_f32",
 ]
 
 
@@ -108,6 +108,8 @@ def load():
                                            dp, C.c_int, C.c_int, vp]
     lib.pnx_curvefit_batch_f32.restype = C.c_int
     lib.pnx_curvefit_batch_f32.argtypes = lib.pnx_curvefit_batch_f64.argtypes  # all data pointers are void*
+    lib.pnx_curvefit_fast_f32.restype = C.c_int
+    lib.pnx_curvefit_fast_f32.argtypes = lib.pnx_curvefit_batch_f64.argtypes
     lib.pnx_nnls_plan_create.restype = C.c_int
     lib.pnx_nnls_plan_create.argtypes = [C.POINTER(vp), C.c_int, C.c_int, dp, dp, C.c_int, C.c_int]
     lib.pnx_nnls_plan_destroy.restype = C.c_int

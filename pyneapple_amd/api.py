@@ -59,6 +59,12 @@ def make_opts(model, n_b, fixed_idx=(), per_voxel=False, fixed_per_voxel=False, 
     return o
 
 
+def _precision(precision):
+    if precision not in ("float64", "float32"):
+        raise ValueError(f"precision must be 'float64' or 'float32', got {precision!r}")
+    return precision == "float32"
+
+
 def _out(out, key, shape, dtype):
     """A caller-provided result array (`out[key]`: C-contiguous, right shape and dtype -- e.g. a row range of a larger array
     that several device shards fill) or a fresh one."""
@@ -71,17 +77,30 @@ def _out(out, key, shape, dtype):
 
 
 def curvefit(model, b, y, p0, lo, hi, *, fixed_idx=(), fixed_vals=None, max_nfev=250, ftol=1e-8, xtol=1e-8,
-             gtol=1e-8, jac="fd", want_pcov=True, device=0, t1_mode=0, tr=0.0, tm=0.0, out=None, sigma=None,
-             absolute_sigma=False):
+             gtol=1e-8, jac=None, want_pcov=True, device=0, t1_mode=0, tr=0.0, tm=0.0, out=None, sigma=None,
+             absolute_sigma=False, precision="float64"):
     """Batched bounded NLLS on host (numpy) arrays.  Shapes as in include/pnx.h.
 
     A float32 signal array selects the fp32-storage entry point (pnx_curvefit_batch_f32: every data array float32 in
     and out, fp64 arithmetic on the device); anything else goes through pnx_curvefit_batch_f64.
     Returns dict(popt (n_free, n_vox), pcov (n_vox, n_free, n_free) | None, status int8, nfev int32, cost).
     `out`: optional dict of preallocated result arrays ("pcov", "status", "nfev", "cost") to write into.
+    jac: "fd" or "analytic"; None = "fd" (SciPy's 2-point differences), and "analytic" with precision="float32".
+    precision="float32": fp32 ARITHMETIC (pnx_curvefit_fast_f32, a separate kernel): every array crosses the ABI as float32
+    whatever dtype the signal has, analytic Jacobian only, all parameters free, no T1 factor, no sigma.  The results are
+    float32-quality minima, not SciPy-parity results (include/pnx.h).
     """
+    fast = _precision(precision)
+    if fast:
+        if jac == "fd":
+            raise ValueError("precision='float32' fits with the analytic Jacobian: SciPy's 2-point step is below fp32 resolution")
+        if len(fixed_idx) or t1_mode or sigma is not None:
+            raise ValueError("precision='float32' is built for all parameters free, without the T1 / STEAM factor and without sigma")
+        jac = "analytic"
+    elif jac is None:
+        jac = "fd"
     _lib.require_device()
-    dt = np.float32 if getattr(y, "dtype", None) == np.float32 else np.float64
+    dt = np.float32 if fast or getattr(y, "dtype", None) == np.float32 else np.float64
     b = np.ascontiguousarray(b, dt)
     y = np.ascontiguousarray(np.atleast_2d(y), dt)
     n_vox, n_b = y.shape
@@ -108,7 +127,7 @@ def curvefit(model, b, y, p0, lo, hi, *, fixed_idx=(), fixed_vals=None, max_nfev
     status = _out(out, "status", (n_vox,), np.int8)
     nfev = _out(out, "nfev", (n_vox,), np.int32)
     cost = _out(out, "cost", (n_vox,), dt)
-    fn = load().pnx_curvefit_batch_f32 if dt is np.float32 else load().pnx_curvefit_batch_f64
+    fn = load().pnx_curvefit_fast_f32 if fast else load().pnx_curvefit_batch_f32 if dt is np.float32 else load().pnx_curvefit_batch_f64
     check(fn(C.byref(o), n_vox, ptr(b), ptr(y), ptr(p0), ptr(lo), ptr(hi), ptr(fv),
                                         ptr(popt), ptr(pcov), ptr(status), ptr(nfev), ptr(cost), MEM_HOST, device, None))
     return dict(popt=popt, pcov=pcov, status=status, nfev=nfev, cost=cost)
@@ -119,17 +138,23 @@ def release_staging(device=0):
     check(load().pnx_release_staging(int(device)))
 
 
-def curvefit_device(opts, n_vox, b, y, p0, lo, hi, fixed, popt, pcov, status, nfev, cost, device, stream=None, order=None):
+def curvefit_device(opts, n_vox, b, y, p0, lo, hi, fixed, popt, pcov, status, nfev, cost, device, stream=None, order=None,
+                    precision="float64"):
     """Enqueue a batched fit on HBM-resident torch tensors (asynchronous; caller synchronises).  float32 tensors
     select the fp32-storage entry point.  `order`: optional int32 device tensor, a permutation of the voxel indices in which
-    the kernel's queue hands the voxels out (longest fits first hides the straggler tail; results do not depend on it)."""
+    the kernel's queue hands the voxels out (longest fits first hides the straggler tail; results do not depend on it).
+    precision="float32": fp32 arithmetic (pnx_curvefit_fast_f32); the tensors must be float32 and `opts` made with
+    jac="analytic" -- everything the fp32 kernel is not built for is refused by the library."""
+    fast = _precision(precision)
     f32 = "float32" in str(getattr(y, "dtype", ""))
+    if fast and not f32:
+        raise ValueError("precision='float32' takes float32 tensors")
     b = np.ascontiguousarray(b, np.float32 if f32 else np.float64)
     if not getattr(opts, "per_voxel_p0_bounds", 0):
         p0, lo, hi = (np.ascontiguousarray(a, b.dtype) for a in (p0, lo, hi))
     if isinstance(fixed, np.ndarray):
         fixed = np.ascontiguousarray(fixed, b.dtype)
-    fn = load().pnx_curvefit_batch_f32 if f32 else load().pnx_curvefit_batch_f64
+    fn = load().pnx_curvefit_fast_f32 if fast else load().pnx_curvefit_batch_f32 if f32 else load().pnx_curvefit_batch_f64
     if order is not None and (tuple(order.shape) != (int(n_vox),) or "int32" not in str(order.dtype)):
         raise ValueError("order must be an int32 device tensor of n_vox entries")
     opts.queue_order = ptr(order)  # explicit per call (None clears what an earlier call with these opts set)

@@ -16,6 +16,7 @@
 #include <thread>
 #include <vector>
 
+#include "pnx_curvefit_f32_kernel.hpp"
 #include "pnx_curvefit_kernel.hpp"
 #include "pnx_host_pipeline.hpp"
 #include "pnx_internal.hpp"
@@ -858,6 +859,97 @@ static int curvefit_batch(const pnx_curvefit_opts *o, int64_t n_vox, const T *b,
     const size_t chunk = (size_t)dev_env_int("PNX_HOST_CHUNK", F32 ? 1 << 20 : 3 << 18, 1024, 1 << 26);
     return chunk_ring(A, nv, chunk, dev_env_int("PNX_HOST_SLOTS", 3, 2, 8), dev_env_int("PNX_HOST_KSTREAMS", 2, 1, 4), hg.touchers(), device,
                       (hipStream_t)stream, [&](size_t c, const DevSet &D, hipStream_t st) { return curvefit_on(o, A, sh, D, c, dev, st); });
+}
+
+// ---- fp32 arithmetic: pnx_curvefit_fast_f32 (kernel: pnx_curvefit_f32_kernel.hpp, launch: pnx_curvefit_f32.hip) ---------
+extern "C" int pnx_launch_curvefit_f32(int model, const pnx::f32::CurvefitF32Args *args, int cus, void *stream);
+
+// the fit of n_vox voxels on float device buffers; shared p0 / bounds come from the host arrays p0 / lo / hi
+static int curvefit_f32_device(const pnx_curvefit_opts *o, int64_t n_vox, const float *b, const float *y_d, const float *p0, const float *lo,
+                               const float *hi, float *popt_d, float *pcov_d, int8_t *status_d, int32_t *nfev_d, float *cost_d,
+                               DeviceInfo *dev, hipStream_t stream) {
+    f32::CurvefitF32Args a;
+    memset(&a, 0, sizeof(a));
+    a.y = y_d;
+    a.popt = popt_d;
+    a.pcov = pcov_d;
+    a.status = status_d;
+    a.nfev = nfev_d;
+    a.cost = cost_d;
+    a.n_vox = n_vox;
+    a.n_b = o->n_b;
+    a.per_voxel = o->per_voxel_p0_bounds;
+    a.max_nfev = o->max_nfev > 0 ? o->max_nfev : 100 * o->n_free;  // least_squares: max_nfev=None -> 100*n
+    // tolerances below fp32 resolution cannot be honoured: the floors of include/pnx.h (measured: DESIGN.md 4.1b)
+    a.ftol = (float)std::max(o->ftol, 4.0 * (double)f32::kEpsF);
+    a.xtol = (float)std::max(o->xtol, (double)f32::kEpsF);
+    a.gtol = (float)o->gtol;  // no floor: see include/pnx.h
+    for (int i = 0; i < o->n_b; ++i) a.b[i] = b[i];
+    if (o->per_voxel_p0_bounds) {
+        a.p0 = p0;
+        a.lo = lo;
+        a.hi = hi;
+    } else {
+        for (int k = 0; k < o->n_free; ++k) {
+            a.p0s[k] = p0[k];
+            a.los[k] = lo[k];
+            a.his[k] = hi[k];
+        }
+    }
+    a.queue = next_queue(dev);
+    PNX_HIP(hipMemsetAsync(a.queue, 0, sizeof(unsigned long long), stream));
+    return pnx_launch_curvefit_f32(o->model, &a, dev->cus, (void *)stream);
+}
+
+extern "C" int pnx_curvefit_fast_f32(const pnx_curvefit_opts *o, int64_t n_vox, const float *b, const float *y, const float *p0,
+                                     const float *lo, const float *hi, const float *fixed, float *popt, float *pcov, int8_t *status,
+                                     int32_t *nfev, float *cost, int mem, int device, void *stream) {
+    int rc = check_curvefit_opts(o);
+    if (rc) return rc;
+    // what the fp32 kernel is not built for: refused by name, never served by the fp64 kernel behind the caller's back
+    if (o->jac_mode == PNX_JAC_FD)
+        return set_error(PNX_ERR_UNSUPPORTED, "fp32 arithmetic: SciPy's 2-point step (1.5e-8) is below fp32 resolution; pass PNX_JAC_ANALYTIC");
+    if (o->n_fixed || fixed) return set_error(PNX_ERR_UNSUPPORTED, "fp32 arithmetic: fixed parameters are not built (use pnx_curvefit_batch_f32)");
+    if (o->t1_mode) return set_error(PNX_ERR_UNSUPPORTED, "fp32 arithmetic: the T1 / STEAM factor is not built (use pnx_curvefit_batch_f32)");
+    if (o->sigma) return set_error(PNX_ERR_UNSUPPORTED, "fp32 arithmetic: sigma is not built (use pnx_curvefit_batch_f32)");
+    if (o->queue_order) return set_error(PNX_ERR_UNSUPPORTED, "fp32 arithmetic: queue_order is not built (use pnx_curvefit_batch_f32)");
+    if (n_vox < 0) return set_error(PNX_ERR_INVALID, "n_vox < 0");
+    if (!b || !p0 || !lo || !hi || !popt || (n_vox && !y)) return set_error(PNX_ERR_INVALID, "NULL data pointer");
+    if (mem != PNX_MEM_HOST && mem != PNX_MEM_DEVICE) return set_error(PNX_ERR_INVALID, "mem=%d", mem);
+    if (n_vox == 0) return PNX_OK;
+    DeviceInfo *dev;
+    rc = get_device(device, &dev);
+    if (rc) return rc;
+    PNX_HIP(hipSetDevice(device));
+    const int n = o->n_free;
+    const size_t nv = (size_t)n_vox;
+    const bool pv = o->per_voxel_p0_bounds != 0;
+    if (mem == PNX_MEM_DEVICE) {
+        if (pcov && (!status || !cost))
+            return set_error(PNX_ERR_INVALID, "device mode: pcov needs the status and cost outputs too (the covariance "
+                                              "epilogue kernel reads them)");
+        return curvefit_f32_device(o, n_vox, b, y, p0, lo, hi, popt, pcov, status, nfev, cost, dev, (hipStream_t)stream);
+    }
+    // host arrays: the chunk ring on float buffers (nothing is widened: the kernel reads and writes float)
+    ArrayTable A;  // CF_* order without the fixed maps' content; per-voxel p0 / bounds and popt are parameter-major
+    A.add(y, sizeof(float), o->n_b, false);
+    A.add(pv ? p0 : nullptr, sizeof(float), n, false).pmajor = true;
+    A.add(pv ? lo : nullptr, sizeof(float), n, false).pmajor = true;
+    A.add(pv ? hi : nullptr, sizeof(float), n, false).pmajor = true;
+    A.add(nullptr, sizeof(float), 0, false).pmajor = true;
+    A.add(popt, sizeof(float), n, true).pmajor = true;
+    A.add(pcov, sizeof(float), (size_t)n * n, true);
+    A.add(status, 1, 1, true).always = pcov != nullptr;  // the covariance epilogue reads status and cost
+    A.add(nfev, sizeof(int32_t), 1, true);
+    A.add(cost, sizeof(float), 1, true).always = pcov != nullptr;
+    HostCallGuard hg;
+    const size_t chunk = (size_t)dev_env_int("PNX_HOST_CHUNK", 1 << 20, 1024, 1 << 26);
+    return chunk_ring(A, nv, chunk, dev_env_int("PNX_HOST_SLOTS", 3, 2, 8), dev_env_int("PNX_HOST_KSTREAMS", 2, 1, 4), hg.touchers(), device,
+                      (hipStream_t)stream, [&](size_t c, const DevSet &D, hipStream_t st) {
+                          auto f = [&](int k) { return (float *)D.dev[k]; };
+                          return curvefit_f32_device(o, (int64_t)c, b, f(CF_Y), pv ? f(CF_P0) : p0, pv ? f(CF_LO) : lo, pv ? f(CF_HI) : hi,
+                                                     f(CF_POPT), f(CF_PCOV), (int8_t *)D.dev[CF_STAT], (int32_t *)D.dev[CF_NFEV], f(CF_COST), dev, st);
+                      });
 }
 
 extern "C" {

@@ -91,6 +91,10 @@ class HipIDEALFitter(HipFitterBase):
         if interpolation_method not in _INTERPOLATION_METHODS:
             raise ValueError(
                 f"Invalid interpolation method: {interpolation_method}. Must be one of {_INTERPOLATION_METHODS}.")
+        if getattr(solver, "precision", "float64") != "float64":
+            # this fitter builds the options of its device-resident levels itself (fp64 arithmetic): refuse instead of fitting in
+            # fp64 behind a solver that asked for fp32
+            raise ValueError("HipIDEALFitter fits in fp64 arithmetic; it cannot take a solver with precision='float32'")
         super().__init__(solver=solver, **fitter_kwargs)
         self.dim_steps = None if dim_steps is None else np.asarray(dim_steps)
         self.step_tol = step_tol

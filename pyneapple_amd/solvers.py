@@ -116,17 +116,28 @@ class HipCurveFitSolver(CurveFitBase):
             fixed maps cross the ABI as float32 and results come back as float32 (pnx_curvefit_batch_f32); the
             arithmetic stays fp64 -- for float32 images this is what the reference computes, without the float64
             host copy.
+        precision: "float64" (default) or "float32": fp32 ARITHMETIC on a separate kernel (pnx_curvefit_fast_f32).  Implies
+            float32 arrays across the ABI and the analytic Jacobian; results are float32-quality minima, not SciPy-parity
+            results.  Not built there, hence a ValueError: jacobian="fd", fixed parameters, a T1 model, sigma.
     """
 
     def __init__(self, model: Any, max_iter: int, tol: float, p0: dict[str, float],
                  bounds: dict[str, tuple[float, float]], verbose: bool = False, method: str = "trf",
                  multi_threading: bool = False, use_jacobian: bool = True, **solver_kwargs):
-        self.jacobian_mode = str(solver_kwargs.pop("jacobian", "fd"))
         self.device = int(solver_kwargs.pop("device", 0))
         self.n_gpus = int(solver_kwargs.pop("n_gpus", 1))
-        self.io_dtype = _io_dtype(solver_kwargs.pop("io_dtype", "float64"))
+        self.precision = solver_kwargs.pop("precision", "float64")
+        fast = api._precision(self.precision)
+        explicit_jac = "jacobian" in solver_kwargs
+        self.jacobian_mode = str(solver_kwargs.pop("jacobian", "analytic" if fast else "fd"))
+        self.io_dtype = _io_dtype(solver_kwargs.pop("io_dtype", "float32" if fast else "float64"))
         if self.jacobian_mode not in ("fd", "analytic"):
             raise ValueError("jacobian must be 'fd' or 'analytic'")
+        if fast:
+            if explicit_jac and self.jacobian_mode == "fd":
+                raise ValueError("precision='float32' fits with the analytic Jacobian (SciPy's 2-point step is below fp32 "
+                                 "resolution); jacobian='fd' cannot be honoured")
+            self.io_dtype = np.float32  # fp32 arithmetic reads and writes float32 arrays
         # The reference forwards every remaining key into scipy.optimize.curve_fit (curvefit.py:295-306).  The kernel
         # implements least_squares' xtol / gtol; anything else would change SciPy's result and there is no CPU path to
         # honour it, so it is refused instead of being dropped silently (keys at their SciPy default are accepted).
@@ -143,6 +154,8 @@ class HipCurveFitSolver(CurveFitBase):
                 raise ValueError("HipCurveFitSolver implements a scalar or 1-D sigma (one standard deviation per b-value); "
                                  "a 2-D sigma is not implemented")
             self.sigma = self.sigma.reshape(-1)
+            if fast:
+                raise ValueError("precision='float32' is not built with sigma; use precision='float64'")
         for key, default in _CURVE_FIT_DEFAULTS.items():
             if key in solver_kwargs:
                 v = solver_kwargs.pop(key)
@@ -152,7 +165,7 @@ class HipCurveFitSolver(CurveFitBase):
         unknown = set(solver_kwargs) - {"n_pools"}
         if unknown:
             raise ValueError(f"HipCurveFitSolver got solver arguments it cannot honour: {sorted(unknown)} "
-                             "(supported: sigma, absolute_sigma, xtol, gtol, jacobian, device, n_gpus, io_dtype, n_pools)")
+                             "(supported: sigma, absolute_sigma, xtol, gtol, jacobian, device, n_gpus, io_dtype, precision, n_pools)")
         if method != "trf":
             raise ValueError(f"HipCurveFitSolver implements method='trf' only (got {method!r}); "
                              "use the reference CurveFitSolver for 'dogbox' / 'lm'.")
@@ -181,6 +194,11 @@ class HipCurveFitSolver(CurveFitBase):
                     "bounds must be a dict with parameter names as keys and (lower, upper) tuples as values.")
         self._kernel_model = kernel_model_key(model)  # fail early and loudly for unsupported models
         self._kernel_t1 = kernel_t1(model)
+        if fast:
+            if self._kernel_t1["t1_mode"]:
+                raise ValueError("precision='float32' is not built with the T1 / STEAM factor; use precision='float64'")
+            if getattr(model, "fixed_params", None):
+                raise ValueError("precision='float32' is not built with fixed parameters; use precision='float64'")
 
     # ------------------------------------------------------------------ p0 / bounds (curvefit.py:319-392)
     def _prepare_p0_bounds(self, p0, bounds, n_pixels):
@@ -291,6 +309,8 @@ class HipCurveFitSolver(CurveFitBase):
         fixed = pixel_fixed_params if pixel_fixed_params else (getattr(self.model, "fixed_params", None) or None)
         free_names = list(self.model.param_names)
         fixed_idx, fixed_vals, jac = [], None, self.jacobian_mode
+        if fixed and self.precision == "float32":
+            raise ValueError("precision='float32' is not built with fixed parameters (pixel_fixed_params); use precision='float64'")
         if fixed:
             free_idx = [i for i, n in enumerate(all_names) if n not in fixed]
             fixed_idx = [i for i, n in enumerate(all_names) if n in fixed]
@@ -330,6 +350,8 @@ class HipCurveFitSolver(CurveFitBase):
         n_vox = ydata.shape[0]
         kw = dict(max_nfev=int(self.max_iter), ftol=float(self.tol), xtol=self.xtol, gtol=self.gtol, jac=jac,
                   fixed_idx=fixed_idx, sigma=self.sigma, absolute_sigma=self.absolute_sigma, **self._kernel_t1)
+        if self.precision == "float32":
+            kw["precision"] = "float32"
         n_dev = max(1, min(self.n_gpus, n_vox))
         if n_dev == 1:
             return api.curvefit(self._kernel_model, xdata, ydata, p0, lo, hi, fixed_vals=fixed_vals,
