@@ -218,6 +218,36 @@ PNX_API int pnx_curvefit_fast_f32(const pnx_curvefit_opts *opts, int64_t n_vox, 
                           int8_t *status, int32_t *nfev, float *cost, int mem, int device, void *stream);
 
 /*
+ * The bounded fit with the volume-fraction constraint f1 + f2 <= 1 (the reference's ConstrainedCurveFitSolver, solvers/
+ * constrained_curvefit.py):  minimise 0.5 ||model(p) - y||^2  subject to  lo <= p <= hi  and  f1 + f2 <= 1,  for the two reduced
+ * tri-exponential layouts PNX_MODEL_TRI_REDUCED [f1, D1, f2, D2, D3] and PNX_MODEL_TRI_S0 [f1, D1, f2, D2, D3, S0] -- the models the
+ * reference admits the constraint for; any other model is PNX_ERR_INVALID.  Not the reference's SLSQP iteration: the constrained
+ * PROBLEM is solved by two box-bounded TRF fits and certified:
+ *   1. pnx_curvefit_batch_f64's fit of every voxel.  A result with f1 + f2 <= 1 is a KKT point of the constrained problem with
+ *      multiplier 0: it is returned as it is, covariance included (face = 0, lambda = 0), bit-identical to the box-only call.
+ *   2. A voxel with status > 0 and f1 + f2 > 1 is fitted again on the face f1 + f2 = 1, which is the bi-exponential model
+ *      (f3 = 0, D3 drops out): start f1 / (f1 + f2), D1, D2 (, S0), clipped into the bounds of f1 intersected with 1 - those of
+ *      f2, [max(lo_f1, 1 - hi_f2), min(hi_f1, 1 - lo_f2)]; same Jacobian mode and tolerances; one evaluation limit per launch,
+ *      max(1, max_nfev - the smallest phase-1 count among the launch's violators).
+ *   3. Its result is written back as f1, D1, f2 = 1 - f1, D2, the phase-1 D3 (unidentifiable on the face), (S0); cost is
+ *      evaluated there; nfev is the sum of both fits; status is the second fit's; pcov is NaN (J^T J is singular on the face, the
+ *      reference's _estimate_covariance returns NaN for a singular matrix).  lambda = -(g_f1 + g_f2) / 2 from the gradient
+ *      g = J^T r of the FULL model at that point is the multiplier of the constraint: face = 1 when lambda >= 0 (a KKT point of
+ *      the constrained problem), 2 when lambda < 0 -- NOT certified: the box-only minimum was infeasible, yet the face point
+ *      wants to move inwards.  A second fit that fails (empty intersection of the bounds: status -1) returns the usual sentinel
+ *      popt = p0, NaN pcov, its status, with lambda = NaN and face = 2.
+ * Arguments of pnx_curvefit_batch_f64, then lambda (n_vox) double and face (n_vox) int8, either may be NULL.  Host and device
+ * memory.  PNX_MEM_DEVICE: the call synchronises `stream` ONCE, behind the first fit, to read the number of violators (it sizes
+ * the second fit's scratch); when there are none nothing else runs, otherwise the rest is enqueued and the call returns.
+ * PNX_MEM_HOST: the chunk ring, both fits per chunk (not the single streamed kernel of pnx_curvefit_batch_f64).
+ * Not built, PNX_ERR_UNSUPPORTED with a message: fixed parameters (fixed must be NULL), the T1 / STEAM factor, sigma, queue_order.
+ */
+PNX_API int pnx_curvefit_simplex_f64(const pnx_curvefit_opts *opts, int64_t n_vox, const double *b, const double *y,
+                             const double *p0, const double *lo, const double *hi, const double *fixed, double *popt,
+                             double *pcov, int8_t *status, int32_t *nfev, double *cost, double *lambda, int8_t *face,
+                             int mem, int device, void *stream);
+
+/*
  * NNLS plan: everything that is shared by all voxels of one fit -- the regularised design matrix
  * A = [basis; reg] (nnls_solver.py:61-73) -- is uploaded and factored into its Gram form once.
  *   basis (n_meas, n_bins) row-major host;  reg (n_reg, n_bins) row-major host or NULL (n_reg = 0).

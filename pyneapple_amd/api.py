@@ -133,6 +133,66 @@ def curvefit(model, b, y, p0, lo, hi, *, fixed_idx=(), fixed_vals=None, max_nfev
     return dict(popt=popt, pcov=pcov, status=status, nfev=nfev, cost=cost)
 
 
+CONSTRAINED_MODELS = ("tri_reduced", "tri_s0")  # the layouts with exactly two fractions and f3 = 1 - f1 - f2
+
+
+def _constrained_refusals(model, fixed_idx=(), fixed_vals=None, t1_mode=0, sigma=None, precision="float64"):
+    if model not in CONSTRAINED_MODELS:
+        raise ValueError(f"the constraint f1 + f2 <= 1 is defined for the models {CONSTRAINED_MODELS}, not for {model!r}")
+    if len(fixed_idx) or fixed_vals is not None or t1_mode or sigma is not None:
+        raise ValueError("the constrained fit is built for all parameters free, without the T1 / STEAM factor and without sigma")
+    if precision != "float64":
+        raise ValueError("the constrained fit is built for precision='float64' only")
+
+
+def curvefit_constrained(model, b, y, p0, lo, hi, *, fixed_idx=(), fixed_vals=None, max_nfev=250, ftol=1e-8, xtol=1e-8,
+                         gtol=1e-8, jac=None, want_pcov=True, device=0, t1_mode=0, tr=0.0, tm=0.0, out=None, sigma=None,
+                         absolute_sigma=False, precision="float64"):
+    """`curvefit` with the constraint f1 + f2 <= 1 (pnx_curvefit_simplex_f64; method and outputs: include/pnx.h), float64 host
+    arrays, model "tri_reduced" or "tri_s0".  The signature is `curvefit`'s; what the constrained fit is not built for (fixed
+    parameters, T1, sigma, precision="float32") raises ValueError.  Returns `curvefit`'s dict plus "lambda" (n_vox,) float64,
+    the multiplier of the constraint (0 for an interior voxel), and "face" (n_vox,) int8: 0 interior -- the voxel's entries are
+    those of `curvefit` --, 1 on the face f1 + f2 = 1 with lambda >= 0, 2 on the face and not certified.
+    `out` may also hold "lambda" and "face"."""
+    _constrained_refusals(model, fixed_idx, fixed_vals, t1_mode, sigma, precision)
+    _lib.require_device()
+    dt = np.float64
+    b = np.ascontiguousarray(b, dt)
+    y = np.ascontiguousarray(np.atleast_2d(y), dt)
+    n_vox, n_b = y.shape
+    if b.shape != (n_b,):
+        raise ValueError(f"b has shape {b.shape}, expected ({n_b},)")
+    p0, lo, hi = (np.ascontiguousarray(a, dt) for a in (p0, lo, hi))
+    per_voxel = p0.ndim == 2
+    o = make_opts(model, n_b, (), per_voxel, False, max_nfev, ftol, xtol, gtol, jac or "fd", absolute_sigma=absolute_sigma)
+    n = o.n_free
+    want = (n, n_vox) if per_voxel else (n,)
+    if p0.shape != want or lo.shape != want or hi.shape != want:
+        raise ValueError(f"p0/lo/hi must have shape {want}")
+    popt = np.empty((n, n_vox), dt)
+    pcov = _out(out, "pcov", (n_vox, n, n), dt) if want_pcov else None
+    status = _out(out, "status", (n_vox,), np.int8)
+    nfev = _out(out, "nfev", (n_vox,), np.int32)
+    cost = _out(out, "cost", (n_vox,), dt)
+    lam = _out(out, "lambda", (n_vox,), dt)
+    face = _out(out, "face", (n_vox,), np.int8)
+    check(load().pnx_curvefit_simplex_f64(C.byref(o), n_vox, ptr(b), ptr(y), ptr(p0), ptr(lo), ptr(hi), None, ptr(popt), ptr(pcov),
+                                          ptr(status), ptr(nfev), ptr(cost), ptr(lam), ptr(face), MEM_HOST, device, None))
+    return {"popt": popt, "pcov": pcov, "status": status, "nfev": nfev, "cost": cost, "lambda": lam, "face": face}
+
+
+def curvefit_constrained_device(opts, n_vox, b, y, p0, lo, hi, popt, pcov, status, nfev, cost, lam, face, device, stream=None):
+    """The constrained fit on HBM-resident float64 torch tensors (pnx_curvefit_simplex_f64, PNX_MEM_DEVICE).  Unlike
+    `curvefit_device` the call synchronises the stream once, behind the first fit, to read the number of violators; the second
+    fit and the merge are enqueued.  `lam` (float64) / `face` (int8): device tensors of n_vox entries, or None."""
+    b = np.ascontiguousarray(b, np.float64)
+    if not getattr(opts, "per_voxel_p0_bounds", 0):
+        p0, lo, hi = (np.ascontiguousarray(a, np.float64) for a in (p0, lo, hi))
+    check(load().pnx_curvefit_simplex_f64(C.byref(opts), int(n_vox), ptr(b), ptr(y), ptr(p0), ptr(lo), ptr(hi), None, ptr(popt),
+                                          ptr(pcov), ptr(status), ptr(nfev), ptr(cost), ptr(lam), ptr(face), MEM_DEVICE, int(device),
+                                          stream))
+
+
 def release_staging(device=0):
     """Free the device staging slab / pinned block / streams a streamed host-array curve fit keeps for the next call."""
     check(load().pnx_release_staging(int(device)))

@@ -22,6 +22,7 @@
 #include "pnx_internal.hpp"
 #include "pnx_nnls.hpp"
 #include "pnx_predict.hpp"
+#include "pnx_simplex.hpp"
 
 namespace pnx {
 
@@ -859,6 +860,135 @@ static int curvefit_batch(const pnx_curvefit_opts *o, int64_t n_vox, const T *b,
     const size_t chunk = (size_t)dev_env_int("PNX_HOST_CHUNK", F32 ? 1 << 20 : 3 << 18, 1024, 1 << 26);
     return chunk_ring(A, nv, chunk, dev_env_int("PNX_HOST_SLOTS", 3, 2, 8), dev_env_int("PNX_HOST_KSTREAMS", 2, 1, 4), hg.touchers(), device,
                       (hipStream_t)stream, [&](size_t c, const DevSet &D, hipStream_t st) { return curvefit_on(o, A, sh, D, c, dev, st); });
+}
+
+// ---- constrained curve fit, f1 + f2 <= 1: pnx_curvefit_simplex_f64 (streaming kernels: pnx_simplex.hip) -----------------
+// Two box-bounded fits and a certificate on the device buffers of n_vox voxels.  p0 / lo / hi: (n_free,) host
+// arrays, or (n_free, n_vox) device arrays when o->per_voxel_p0_bounds.  status, nfev and cost may be null (scratch then);
+// lambda, face and pcov may be null.  Synchronises `st` once, to read the number of violators; nothing else waits.
+static int simplex_on(const pnx_curvefit_opts *o, int64_t n_vox, const double *b, const double *y_d, const double *p0, const double *lo,
+                      const double *hi, double *popt_d, double *pcov_d, int8_t *status_d, int32_t *nfev_d, double *cost_d,
+                      double *lambda_d, int8_t *face_d, DeviceInfo *dev, hipStream_t st) {
+    const size_t nv = (size_t)n_vox;
+    int rc;
+    AsyncBuf scratch;  // outputs the caller did not ask for, the violator flags and their compacted indices
+    int8_t *status = status_d;
+    int32_t *nfev = nfev_d;
+    double *cost = cost_d;
+    unsigned char *flags = nullptr;
+    int64_t *idx = nullptr;
+    for (int pass = 0; pass < 2; ++pass) {
+        Carver cv;
+        cv.base = (char *)scratch.p;
+        idx = (int64_t *)cv.take(nv * sizeof(int64_t));
+        if (!cost_d) cost = (double *)cv.take(nv * sizeof(double));
+        if (!nfev_d) nfev = (int32_t *)cv.take(nv * sizeof(int32_t));
+        if (!status_d) status = (int8_t *)cv.take(nv);
+        flags = (unsigned char *)cv.take(nv);
+        if (pass == 0 && (rc = scratch.alloc(cv.off, st))) return rc;
+    }
+    // phase 1: the box-bounded fit of every voxel, covariance included -- the unchanged launch path
+    if ((rc = curvefit_device(o, n_vox, b, y_d, p0, lo, hi, nullptr, popt_d, pcov_d, status, nfev, cost, dev, st))) return rc;
+    int64_t m = 0;
+    int min_nfev = 0;
+    if ((rc = simplex_select(popt_d, n_vox, status, nfev, flags, idx, lambda_d, face_d, &m, &min_nfev, st))) return rc;
+    if (m == 0) return PNX_OK;  // every box-only minimum is feasible: nothing else runs
+    // phase 2: the violators on the face f1 + f2 = 1, i.e. the bi-exponential model with per-voxel start values and bounds
+    const bool s0 = o->model == PNX_MODEL_TRI_S0;
+    pnx_curvefit_opts o2 = *o;
+    o2.model = s0 ? PNX_MODEL_BI_S0 : PNX_MODEL_BI_REDUCED;
+    o2.n_free = s0 ? 4 : 3;
+    for (int k = 0; k < o2.n_free; ++k) o2.free_idx[k] = k;
+    o2.per_voxel_p0_bounds = 1;
+    // the kernel takes ONE evaluation limit per launch: what the cheapest violator of this launch has left of max_nfev, at least 1
+    const int limit = o->max_nfev > 0 ? o->max_nfev : 100 * o->n_free;
+    o2.max_nfev = std::max(1, limit - min_nfev);
+    const int n2 = o2.n_free;
+    const size_t mm = (size_t)m;
+    AsyncBuf face_buf;
+    double *y2 = nullptr, *p02 = nullptr, *lo2 = nullptr, *hi2 = nullptr, *popt2 = nullptr, *cost2 = nullptr;
+    int32_t *nfev2 = nullptr;
+    int8_t *status2 = nullptr;
+    for (int pass = 0; pass < 2; ++pass) {
+        Carver cv;
+        cv.base = (char *)face_buf.p;
+        y2 = (double *)cv.take(mm * o->n_b * sizeof(double));
+        p02 = (double *)cv.take(mm * n2 * sizeof(double));
+        lo2 = (double *)cv.take(mm * n2 * sizeof(double));
+        hi2 = (double *)cv.take(mm * n2 * sizeof(double));
+        popt2 = (double *)cv.take(mm * n2 * sizeof(double));
+        cost2 = (double *)cv.take(mm * sizeof(double));
+        nfev2 = (int32_t *)cv.take(mm * sizeof(int32_t));
+        status2 = (int8_t *)cv.take(mm);
+        if (pass == 0 && (rc = face_buf.alloc(cv.off, st))) return rc;
+    }
+    if ((rc = simplex_gather(o->model, o->n_b, y_d, popt_d, n_vox, idx, m, o->per_voxel_p0_bounds, lo, hi, y2, p02, lo2, hi2, st))) return rc;
+    if ((rc = curvefit_device(&o2, m, b, y2, p02, lo2, hi2, nullptr, popt2, nullptr, status2, nfev2, cost2, dev, st))) return rc;
+    return simplex_merge(o->model, o->n_b, b, m, idx, y2, popt2, status2, nfev2, cost2, o->per_voxel_p0_bounds, p0, n_vox, popt_d, pcov_d,
+                         status, nfev, cost, lambda_d, face_d, st);  // the AsyncBuf destructors enqueue the frees behind it
+}
+
+extern "C" int pnx_curvefit_simplex_f64(const pnx_curvefit_opts *o, int64_t n_vox, const double *b, const double *y, const double *p0,
+                                        const double *lo, const double *hi, const double *fixed, double *popt, double *pcov,
+                                        int8_t *status, int32_t *nfev, double *cost, double *lambda, int8_t *face, int mem, int device,
+                                        void *stream) {
+    if (!o) return set_error(PNX_ERR_INVALID, "opts is NULL");
+    if (o->model != PNX_MODEL_TRI_REDUCED && o->model != PNX_MODEL_TRI_S0)
+        return set_error(PNX_ERR_INVALID, "the constraint f1 + f2 <= 1 is defined for the reduced tri-exponential models "
+                                          "(PNX_MODEL_TRI_REDUCED, PNX_MODEL_TRI_S0), not for model %d", o->model);
+    int rc = check_curvefit_opts(o);
+    if (rc) return rc;
+    // what the constrained fit is not built for: refused by name, never served by the box-only fit behind the caller's back
+    if (o->n_fixed || fixed) return set_error(PNX_ERR_UNSUPPORTED, "constrained fit: fixed parameters are not built (the face problem would need its own set)");
+    if (o->t1_mode) return set_error(PNX_ERR_UNSUPPORTED, "constrained fit: the T1 / STEAM factor is not built");
+    if (o->sigma) return set_error(PNX_ERR_UNSUPPORTED, "constrained fit: sigma is not built");
+    if (o->queue_order) return set_error(PNX_ERR_UNSUPPORTED, "constrained fit: queue_order is not built");
+    if (n_vox < 0) return set_error(PNX_ERR_INVALID, "n_vox < 0");
+    if (!b || !p0 || !lo || !hi || !popt || (n_vox && !y)) return set_error(PNX_ERR_INVALID, "NULL data pointer");
+    if (mem != PNX_MEM_HOST && mem != PNX_MEM_DEVICE) return set_error(PNX_ERR_INVALID, "mem=%d", mem);
+    if (n_vox == 0) return PNX_OK;
+    DeviceInfo *dev;
+    if ((rc = get_device(device, &dev))) return rc;
+    PNX_HIP(hipSetDevice(device));
+    const int n = o->n_free;
+    const bool pv = o->per_voxel_p0_bounds != 0;
+    if (mem == PNX_MEM_DEVICE) {
+        if (pcov && (!status || !cost))
+            return set_error(PNX_ERR_INVALID, "device mode: pcov needs the status and cost outputs too (the covariance "
+                                              "epilogue kernel reads them)");
+        return simplex_on(o, n_vox, b, y, p0, lo, hi, popt, pcov, status, nfev, cost, lambda, face, dev, (hipStream_t)stream);
+    }
+    // host arrays: the chunk ring, both phases per chunk (the streamed single-kernel launch has no place for a second fit)
+    CurvefitShared sh;
+    for (int i = 0; i < o->n_b; ++i) sh.b[i] = b[i];
+    if (!pv)
+        for (int k = 0; k < n; ++k) {
+            sh.p0[k] = p0[k];
+            sh.lo[k] = lo[k];
+            sh.hi[k] = hi[k];
+        }
+    enum { SX_LAMBDA = CF_COST + 1, SX_FACE };
+    ArrayTable A;  // CF_* order, then the two outputs of the certificate
+    A.add(y, sizeof(double), o->n_b, false);
+    A.add(pv ? p0 : nullptr, sizeof(double), n, false).pmajor = true;
+    A.add(pv ? lo : nullptr, sizeof(double), n, false).pmajor = true;
+    A.add(pv ? hi : nullptr, sizeof(double), n, false).pmajor = true;
+    A.add(nullptr, sizeof(double), 0, false).pmajor = true;
+    A.add(popt, sizeof(double), n, true).pmajor = true;
+    A.add(pcov, sizeof(double), (size_t)n * n, true);
+    A.add(status, 1, 1, true).always = true;  // the classification reads status, the merge adds to nfev
+    A.add(nfev, sizeof(int32_t), 1, true).always = true;
+    A.add(cost, sizeof(double), 1, true).always = pcov != nullptr;
+    A.add(lambda, sizeof(double), 1, true);
+    A.add(face, 1, 1, true);
+    HostCallGuard hg;
+    const size_t chunk = (size_t)dev_env_int("PNX_HOST_CHUNK", 3 << 18, 1024, 1 << 26);
+    return chunk_ring(A, (size_t)n_vox, chunk, dev_env_int("PNX_HOST_SLOTS", 3, 2, 8), dev_env_int("PNX_HOST_KSTREAMS", 2, 1, 4), hg.touchers(),
+                      device, (hipStream_t)stream, [&](size_t c, const DevSet &D, hipStream_t st) {
+                          return simplex_on(o, (int64_t)c, sh.b, D.d(CF_Y), per_voxel_or(A, D, CF_P0, sh.p0), per_voxel_or(A, D, CF_LO, sh.lo),
+                                            per_voxel_or(A, D, CF_HI, sh.hi), D.d(CF_POPT), D.d(CF_PCOV), (int8_t *)D.dev[CF_STAT],
+                                            (int32_t *)D.dev[CF_NFEV], D.d(CF_COST), D.d(SX_LAMBDA), (int8_t *)D.dev[SX_FACE], dev, st);
+                      });
 }
 
 // ---- fp32 arithmetic: pnx_curvefit_fast_f32 (kernel: pnx_curvefit_f32_kernel.hpp, launch: pnx_curvefit_f32.hip) ---------

@@ -5,7 +5,11 @@ and `HipNNLSSolver` mirrors `pyneapple.solvers.NNLSSolver` (src/pyneapple/solver
 constructor arguments, same `fit()` signature, same fitted state (`params_`, `diagnostics_`,
 `pixel_results_`), same error behaviour -- only `_fit_data` runs all voxels at once through the C ABI.
 
-Registered under the `pyneapple.solvers` entry-point group (pyproject.toml) as `hip_curvefit` / `hip_nnls`;
+`HipConstrainedCurveFitSolver` mirrors `ConstrainedCurveFitSolver` (solvers/constrained_curvefit.py) in its constructor and
+its constraint sum(f_i) <= 1, not in its algorithm (pnx_curvefit_simplex_f64).
+
+Registered under the `pyneapple.solvers` entry-point group (pyproject.toml) as `hip_curvefit` / `hip_nnls` /
+`hip_constrained_curvefit`;
 extra scalar keys of `[Fitting.solver]` arrive as keyword arguments (io/toml.py:328-338): `device`,
 `n_gpus`, `jacobian`.
 """
@@ -346,6 +350,12 @@ class HipCurveFitSolver(CurveFitBase):
         self.diagnostics_ = {"pcov": (pcov[0] if n_pixels == 1 else pcov) if pcov is not None else None, "n_pixels": n_pixels,
                              "status": status, "nfev": res["nfev"], "cost": res["cost"]}
 
+    _extra_outputs: dict = {}  # further per-voxel result arrays of a subclass's batch call: key -> dtype
+
+    def _batch_fit(self, *args, **kw):
+        """The array-level call of one shard (a subclass swaps in another one with api.curvefit's signature)."""
+        return api.curvefit(*args, **kw)
+
     def _run(self, xdata, ydata, p0, lo, hi, per_voxel, fixed_idx, fixed_vals, jac):
         n_vox = ydata.shape[0]
         kw = dict(max_nfev=int(self.max_iter), ftol=float(self.tol), xtol=self.xtol, gtol=self.gtol, jac=jac,
@@ -354,15 +364,15 @@ class HipCurveFitSolver(CurveFitBase):
             kw["precision"] = "float32"
         n_dev = max(1, min(self.n_gpus, n_vox))
         if n_dev == 1:
-            return api.curvefit(self._kernel_model, xdata, ydata, p0, lo, hi, fixed_vals=fixed_vals,
-                                device=self.device, **kw)
+            return self._batch_fit(self._kernel_model, xdata, ydata, p0, lo, hi, fixed_vals=fixed_vals,
+                                   device=self.device, **kw)
         parts = _split(n_vox, n_dev)
         # the shards write their voxel-major results straight into row ranges of the full arrays (pcov is 200 B per triexp voxel:
         # concatenating it afterwards would cost more than the fit); popt is parameter-major and is joined afterwards
         n = p0.shape[0]
         dt = ydata.dtype
         full = {"pcov": np.empty((n_vox, n, n), dt), "status": np.empty(n_vox, np.int8), "nfev": np.empty(n_vox, np.int32),
-                "cost": np.empty(n_vox, dt)}
+                "cost": np.empty(n_vox, dt), **{key: np.empty(n_vox, d) for key, d in self._extra_outputs.items()}}
 
         def work(k):
             a, b = parts[k]
@@ -374,12 +384,68 @@ class HipCurveFitSolver(CurveFitBase):
                   np.ascontiguousarray(hi[:, sl])) if per_voxel else (p0, lo, hi)
             dev_k = _shard_device(self.device, k)
             with pinned_to_gpu(dev_k):  # this thread and the call's helper threads stay on the NUMA node of their GPU
-                return api.curvefit(self._kernel_model, xdata, ydata[sl], *pv, fixed_vals=fv,
-                                    device=dev_k, out={key: v[sl] for key, v in full.items()}, **kw)["popt"]
+                return self._batch_fit(self._kernel_model, xdata, ydata[sl], *pv, fixed_vals=fv,
+                                       device=dev_k, out={key: v[sl] for key, v in full.items()}, **kw)["popt"]
 
         with ThreadPoolExecutor(len(parts)) as ex:  # ctypes releases the GIL during the call
             popts = list(ex.map(work, range(len(parts))))
         return dict(full, popt=np.concatenate(popts, axis=1))
+
+
+class HipConstrainedCurveFitSolver(HipCurveFitSolver):
+    """`HipCurveFitSolver` with the volume-fraction constraint sum(f_i) <= 1 of the reference's ConstrainedCurveFitSolver
+    (solvers/constrained_curvefit.py:23-119), same constructor contract: `p0` and `bounds` come first, `fraction_constraint=True`
+    needs a `fit_reduced` model with at least two fraction parameters (names starting with "f") -- the reduced tri-exponential
+    models [f1, D1, f2, D2, D3 (, S0)] --, `fraction_constraint=False` behaves as the parent, `method` is accepted and ignored.
+
+    The constrained PROBLEM is solved, not the reference's SLSQP iteration (pnx_curvefit_simplex_f64): the parent's bounded fit;
+    voxels whose result has f1 + f2 > 1 are fitted again on the face f1 + f2 = 1 (the bi-exponential model) and certified by
+    the multiplier of the constraint.  `diagnostics_` gains "lambda" (0 for an interior voxel) and "face" (0 interior: the
+    parent's result bit for bit; 1 face, lambda >= 0; 2 face, not certified); pcov of a face voxel is NaN.
+    Not built with the constraint, hence a ValueError: fixed parameters (model or per pixel), a T1 model, sigma,
+    precision / io_dtype "float32".  Extra keyword arguments as the parent's."""
+
+    def __init__(self, model: Any, p0: dict[str, float], bounds: dict[str, tuple[float, float]], max_iter: int = 250,
+                 tol: float = 1e-8, fraction_constraint: bool = True, verbose: bool = False, method: str = "SLSQP",
+                 multi_threading: bool = False, use_jacobian: bool = True, **solver_kwargs):
+        if fraction_constraint and not getattr(model, "fit_reduced", False):  # constrained_curvefit.py:72-79
+            raise ValueError("fraction_constraint=True requires fit_reduced=True. In reduced mode the signal is normalised to S0=1 "
+                             "before fitting, so the hard constraint sum(f_i) <= 1 is physically meaningful. Use fit_reduced=True "
+                             "(or fit_s0=True) with the constrained solver.")
+        super().__init__(model=model, max_iter=max_iter, tol=tol, p0=p0, bounds=bounds, verbose=verbose, method="trf",
+                         multi_threading=multi_threading, use_jacobian=use_jacobian, **solver_kwargs)
+        self.method = "SLSQP"  # the reference's attribute value (constrained_curvefit.py:96); no SLSQP runs here
+        self.fraction_constraint = bool(fraction_constraint)
+        self._fraction_names = [n for n in self.model.param_names if n.startswith("f")] if fraction_constraint else []
+        self._fraction_indices = [self.model.param_names.index(n) for n in self._fraction_names]
+        if not fraction_constraint:
+            return
+        if len(self._fraction_names) < 2:
+            raise ValueError(f"fraction_constraint=True requires at least 2 fraction parameters. Found: {self._fraction_names}")
+        if self._kernel_model not in api.CONSTRAINED_MODELS:
+            raise ValueError(f"the constrained fit is built for the models {api.CONSTRAINED_MODELS}, not {self._kernel_model!r}")
+        if self.precision != "float64" or self.io_dtype is not np.float64:
+            raise ValueError("the constrained fit is built for precision='float64' and io_dtype='float64' only")
+        if self.sigma is not None:
+            raise ValueError("the constrained fit is not built with sigma")
+        if self._kernel_t1["t1_mode"]:
+            raise ValueError("the constrained fit is not built with the T1 / STEAM factor")
+        if getattr(model, "fixed_params", None):
+            raise ValueError("the constrained fit is not built with fixed parameters")
+        self._extra_outputs = {"lambda": np.float64, "face": np.int8}
+
+    def _batch_fit(self, *args, **kw):
+        return api.curvefit_constrained(*args, **kw) if self.fraction_constraint else api.curvefit(*args, **kw)
+
+    def fit(self, xdata, ydata, p0=None, bounds=None, pixel_fixed_params=None, **fit_kwargs):
+        if self.fraction_constraint and (pixel_fixed_params or getattr(self.model, "fixed_params", None)):
+            raise ValueError("the constrained fit is not built with fixed parameters (pixel_fixed_params)")
+        return super().fit(xdata, ydata, p0=p0, bounds=bounds, pixel_fixed_params=pixel_fixed_params, **fit_kwargs)
+
+    def _pack(self, res, n_pixels, free_names):
+        super()._pack(res, n_pixels, free_names)
+        for key in self._extra_outputs:
+            self.diagnostics_[key] = res[key]
 
 
 class HipNNLSSolver(NNLSBase):
