@@ -404,11 +404,21 @@ PNX_API int pnx_scatter_maps_f32(const double *values, const int64_t *linear_ind
  *   level's start values and bounds, parameter-major (n_params, n_px): p0 = clip(map, lo, hi),
  *   lower = clip(p0 (1 - tol), lo, hi), upper = clip(p0 (1 + tol), lo, hi)  (ideal.py:167-198).  Device pointers;
  *   lo / hi / tol (n_params,) on the host.
+ * pnx_ideal_bounds_simplex_f64: the same for a level fitted under f1 + f2 <= 1 (pnx_curvefit_simplex_f64); i_f1 / i_f2 are the
+ *   rows of the two fractions.  Interpolating a feasible map overshoots, and a window around a start with f1 + f2 > 1 can hold
+ *   no feasible point (the face problem's intersected bounds are then empty: status -1).  Per voxel, in fp64 as written:
+ *   p = clip(map, lo, hi); if e = f1 + f2 - 1 > 0: f1 -= e / 2, f2 -= e / 2, both clipped to their bounds again; then p0 /
+ *   lower / upper from p as above.  A voxel with f1 + f2 <= 1 after the first clip gets pnx_ideal_bounds_f64's output bit for
+ *   bit.  PNX_ERR_INVALID before any device work: n_params outside 1 .. 8, i_f1 or i_f2 outside [0, n_params), i_f1 == i_f2.
+ *   Both calls only enqueue; the small arguments travel by value.
  */
 PNX_API int pnx_resize2d_f64(const double *in, int X, int Y, int64_t C, double *out, int TX, int TY, int method, int mem,
                      int device, void *stream);
 PNX_API int pnx_ideal_bounds_f64(const double *map, int64_t n_px, int n_params, const double *lo_host, const double *hi_host,
                          const double *tol_host, double *p0, double *lower, double *upper, int device, void *stream);
+PNX_API int pnx_ideal_bounds_simplex_f64(const double *map, int64_t n_px, int n_params, const double *lo_host, const double *hi_host,
+                                 const double *tol_host, int i_f1, int i_f2, double *p0, double *lower, double *upper,
+                                 int device, void *stream);
 
 /*
  * IDEAL level plumbing between the resize and the fit (fitters/ideal.py:199-254), device pointers:

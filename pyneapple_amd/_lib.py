@@ -27,7 +27,7 @@ ABI_SYMBOLS = [
     "pnx_mask_select_f64", "pnx_gather_rows_f64", "pnx_scatter_rows_t_f64", "pnx_row_ss_tot_f64", "pnx_upload", "pnx_download",
     "pnx_label_sums_f64", "pnx_release_staging", "pnx_queue_order_f64",
     "pnx_nnls_fit_stats_f64", "pnx_nnls_solve_peaks_stats_f64", "pnx_curvefit_predict_f64", "pnx_curvefit_fast_f32",
-    "pnx_curvefit_simplex_f64",
+    "pnx_curvefit_simplex_f64", "pnx_ideal_bounds_simplex_f64",
 ]
 
 
@@ -124,6 +124,8 @@ def load():
     lib.pnx_resize2d_f64.argtypes = [vp, C.c_int, C.c_int, C.c_int64, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]
     lib.pnx_ideal_bounds_f64.restype = C.c_int
     lib.pnx_ideal_bounds_f64.argtypes = [vp, C.c_int64, C.c_int, dp, dp, dp, vp, vp, vp, C.c_int, vp]
+    lib.pnx_ideal_bounds_simplex_f64.restype = C.c_int  # pnx_ideal_bounds_f64's arguments, i_f1 and i_f2 behind tol
+    lib.pnx_ideal_bounds_simplex_f64.argtypes = [vp, C.c_int64, C.c_int, dp, dp, dp, C.c_int, C.c_int, vp, vp, vp, C.c_int, vp]
     lib.pnx_nnls_solve_f32.restype = C.c_int
     lib.pnx_nnls_solve_f32.argtypes = lib.pnx_nnls_solve_f64.argtypes
     lib.pnx_nnls_aty_f64.restype = C.c_int

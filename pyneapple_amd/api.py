@@ -530,6 +530,14 @@ def ideal_bounds_device(param_map, n_px, lo, hi, tol, p0, lower, upper, device, 
                                       ptr(upper), int(device), stream))
 
 
+def ideal_bounds_simplex_device(param_map, n_px, lo, hi, tol, i_f1, i_f2, p0, lower, upper, device, stream=None):
+    """`ideal_bounds_device` for a level fitted under f1 + f2 <= 1 (pnx_ideal_bounds_simplex_f64): the clipped start values of
+    the fraction rows i_f1 / i_f2 are moved onto the face where their sum exceeds 1, before the windows are built."""
+    lo, hi, tol = (np.ascontiguousarray(a, np.float64) for a in (lo, hi, tol))
+    check(load().pnx_ideal_bounds_simplex_f64(ptr(param_map), int(n_px), int(lo.size), ptr(lo), ptr(hi), ptr(tol), int(i_f1), int(i_f2),
+                                              ptr(p0), ptr(lower), ptr(upper), int(device), stream))
+
+
 def mask_select_device(mask, threshold, idx, device, stream=None) -> int:
     """idx[:k] = C-order indices of mask > threshold (float64 tensor, any shape); returns k (synchronises the stream)."""
     k = C.c_int64(0)

@@ -105,6 +105,40 @@ __global__ void ideal_bounds_kernel(const double *__restrict__ map, long long n_
     }
 }
 
+struct SimplexRows {  // the two fraction rows of the constraint f1 + f2 <= 1 and their global bounds, by value
+    int i1, i2;
+    double lo1, hi1, lo2, hi2;
+};
+
+// ideal_bounds_kernel for a level fitted under f1 + f2 <= 1 (pnx_curvefit_simplex_f64): cubic interpolation of a feasible
+// parent map overshoots, and a window [p (1 - tol), p (1 + tol)] around a start with f1 + f2 > 1 can miss the face f1 + f2 = 1
+// altogether -- the face problem's intersected bounds are then empty.  So the clipped fractions are moved onto the face along
+// its normal (e / 2 off each) and clipped again before the windows are built.  One lane per voxel (the two rows are coupled),
+// stores parameter-major and coalesced as above; a voxel with f1 + f2 <= 1 takes exactly the arithmetic of ideal_bounds_kernel.
+__global__ void ideal_bounds_simplex_kernel(const double *__restrict__ map, long long n_px, int n_params, const BoundsArgs B,
+                                            const SimplexRows S, double *__restrict__ p0, double *__restrict__ lower,
+                                            double *__restrict__ upper) {
+#pragma clang fp contract(off)  // the roundings of the numpy statement (ideal.py project_fractions), operation by operation
+    for (long long v = (long long)blockIdx.x * blockDim.x + threadIdx.x; v < n_px; v += (long long)gridDim.x * blockDim.x) {
+        const double *row = map + v * n_params;
+        double f1 = fmin(fmax(row[S.i1], S.lo1), S.hi1);
+        double f2 = fmin(fmax(row[S.i2], S.lo2), S.hi2);
+        const double e = f1 + f2 - 1.0;
+        if (e > 0) {
+            f1 = fmin(fmax(f1 - e / 2, S.lo1), S.hi1);
+            f2 = fmin(fmax(f2 - e / 2, S.lo2), S.hi2);
+        }
+        for (int k = 0; k < n_params; ++k) {
+            const double l = B.lo[k], h = B.hi[k], t = B.tol[k];
+            const double p = k == S.i1 ? f1 : k == S.i2 ? f2 : fmin(fmax(row[k], l), h);
+            const long long o = (long long)k * n_px + v;
+            p0[o] = p;
+            lower[o] = fmin(fmax(p * (1 - t), l), h);
+            upper[o] = fmin(fmax(p * (1 + t), l), h);
+        }
+    }
+}
+
 // ---- level plumbing between the resize and the fit (IDEALFitter.fit, fitters/ideal.py:199-254): which voxels of the level
 // are fitted, their signal rows and start values gathered, the estimates scattered back into the level's map.
 struct MaskAbove {  // idx -> mask[idx] > thr   (ideal.py:199: `_segmentation_interp[..., 0] > self.segmentation_threshold`)
@@ -216,6 +250,33 @@ int pnx_ideal_bounds_f64(const double *map, int64_t n_px, int n_params, const do
     size_t blocks = ((size_t)n_px * n_params + 255) / 256;
     if (blocks > 65536) blocks = 65536;
     hipLaunchKernelGGL(ideal_bounds_kernel, dim3((unsigned)blocks), dim3(256), 0, st, map, (long long)n_px, n_params, B, p0,
+                       lower, upper);
+    RS_HIP(hipGetLastError());
+    return PNX_OK;
+}
+
+int pnx_ideal_bounds_simplex_f64(const double *map, int64_t n_px, int n_params, const double *lo_host, const double *hi_host,
+                                 const double *tol_host, int i_f1, int i_f2, double *p0, double *lower, double *upper, int device,
+                                 void *stream) {
+    if (!map || !lo_host || !hi_host || !tol_host || !p0 || !lower || !upper) return set_error(PNX_ERR_INVALID, "NULL pointer");
+    if (n_params < 1 || n_params > PNX_MAX_PARAMS) return set_error(PNX_ERR_INVALID, "n_params=%d: 1 .. %d", n_params, PNX_MAX_PARAMS);
+    if (n_px < 0) return set_error(PNX_ERR_INVALID, "n_px < 0");
+    if (i_f1 < 0 || i_f1 >= n_params) return set_error(PNX_ERR_INVALID, "i_f1=%d outside [0, n_params=%d)", i_f1, n_params);
+    if (i_f2 < 0 || i_f2 >= n_params) return set_error(PNX_ERR_INVALID, "i_f2=%d outside [0, n_params=%d)", i_f2, n_params);
+    if (i_f1 == i_f2) return set_error(PNX_ERR_INVALID, "i_f1 == i_f2 (%d): the constraint needs two fraction rows", i_f1);
+    if (n_px == 0) return PNX_OK;
+    RS_HIP(hipSetDevice(device));
+    hipStream_t st = (hipStream_t)stream;
+    BoundsArgs B;
+    for (int k = 0; k < PNX_MAX_PARAMS; ++k) {
+        B.lo[k] = k < n_params ? lo_host[k] : 0.0;
+        B.hi[k] = k < n_params ? hi_host[k] : 0.0;
+        B.tol[k] = k < n_params ? tol_host[k] : 0.0;
+    }
+    const SimplexRows S{i_f1, i_f2, lo_host[i_f1], hi_host[i_f1], lo_host[i_f2], hi_host[i_f2]};
+    size_t blocks = ((size_t)n_px + 255) / 256;
+    if (blocks > 65536) blocks = 65536;
+    hipLaunchKernelGGL(ideal_bounds_simplex_kernel, dim3((unsigned)blocks), dim3(256), 0, st, map, (long long)n_px, n_params, B, S, p0,
                        lower, upper);
     RS_HIP(hipGetLastError());
     return PNX_OK;

@@ -72,6 +72,31 @@ def resize2d(array: np.ndarray, target_shape, method: str = "cubic") -> np.ndarr
     return np.ascontiguousarray(np.swapaxes(out, 0, 1))   # (tx, ty, ...)
 
 
+def project_fractions(p0: np.ndarray, lo, hi, i_f1: int, i_f2: int) -> np.ndarray:
+    """Start values of a level fitted under f1 + f2 <= 1, parameter axis last, already clipped to the bounds: where the two
+    fractions sum to more than 1 (cubic interpolation of a feasible map overshoots) each gives up half the excess and is clipped
+    to its bounds again.  A window p (1 -/+ tol) around an infeasible start can hold no feasible point at all; around the
+    projected one it does.  The numpy statement of pnx_ideal_bounds_simplex_f64's step, operation by operation."""
+    p0 = np.array(p0, dtype=np.float64)
+    f1, f2 = p0[..., i_f1], p0[..., i_f2]
+    e = f1 + f2 - 1.0
+    over = e > 0
+    p0[..., i_f1] = np.where(over, np.clip(f1 - e / 2, lo[i_f1], hi[i_f1]), f1)
+    p0[..., i_f2] = np.where(over, np.clip(f2 - e / 2, lo[i_f2], hi[i_f2]), f2)
+    return p0
+
+
+def _fraction_rows(solver):
+    """(i_f1, i_f2) when `solver` fits under the constraint f1 + f2 <= 1 (HipConstrainedCurveFitSolver with
+    fraction_constraint=True), else None."""
+    if not getattr(solver, "fraction_constraint", False):
+        return None
+    rows = [int(i) for i in getattr(solver, "_fraction_indices", ())]
+    if len(rows) != 2:
+        raise ValueError(f"HipIDEALFitter: the constrained solver must name exactly two fraction parameters, got rows {rows}")
+    return rows[0], rows[1]
+
+
 class HipIDEALFitter(HipFitterBase):
     """IDEAL pyramid around a `HipCurveFitSolver` (any solver with the CurveFitSolver interface works).
 
@@ -82,7 +107,14 @@ class HipIDEALFitter(HipFitterBase):
     and assigned as attributes before `fit`, which raises a ValueError naming them otherwise.
     After `fit`: `step_params` (one (X, Y, Z, n_params) map per level), `fitted_params_`, `pixel_indices`,
     `image_shape`, `results_` (FitResult of the last level), `fit_time`, `level_stats_` (device path: per level the mean
-    cost at the level's start values -- one pass of the residual sweep kernel, pnx_sweep_f64 -- and at the estimates).
+    cost at the level's start values -- one pass of the residual sweep kernel, pnx_sweep_f64, which is unweighted and therefore
+    left out when the solver has a sigma -- and at the estimates).
+    The solver's constraint and weights hold at every level on both paths: a `HipConstrainedCurveFitSolver` fits every level
+    under f1 + f2 <= 1 (the resized start values are projected onto the simplex before the level's windows are built,
+    `project_fractions` / pnx_ideal_bounds_simplex_f64; `level_stats_` gains "n_face", "feasible_frac" and "n_bad_bounds" (voxels
+    with status -1), `diagnostics_` of the solver "lambda" and "face" of the last level), a solver with `sigma` / `absolute_sigma` fits every level weighted.
+    For the HIP constrained solver the host path resizes with the device path's kernel (pnx_resize2d_f64 on host arrays): both
+    paths then return the same bytes.
     """
 
     def __init__(self, solver, dim_steps=None, step_tol: dict | None = None, ideal_dims: int = 2,
@@ -170,12 +202,27 @@ class HipIDEALFitter(HipFitterBase):
         lo_vals = np.array([self.solver.bounds[n][0] for n in names], float)
         hi_vals = np.array([self.solver.bounds[n][1] for n in names], float)
         tol_vals = np.array([self.step_tol[n] for n in names], float)
+        frac = _fraction_rows(self.solver)
         if self._use_device_path():
             return self._fit_device(xdata, image, segmentation, dim_steps, names, p0_vals, lo_vals, hi_vals, tol_vals, t0,
                                     fit_kwargs)
         self.step_params = []
         self.stage_times_ = []  # per level: seconds spent resizing / masking, in solver.fit, in map assembly
         method = self.interpolation_method
+        resize = lambda a, shape: resize2d(a, shape, method)
+        if frac is not None and hasattr(self.solver, "_kernel_model"):
+            # The constrained fit of a voxel whose D3 sits on its bound turns the 5e-16 between numpy's and the kernel's summation
+            # order into 5e-7, and the next level into percents of D3 (tests/test_gpu_ideal_solver.py): for the HIP constrained
+            # solver the signal and the maps are resized by the device loop's kernel (pnx_resize2d_f64, host arrays in and out),
+            # so that both loops hand the solver the same bytes and the answer does not depend on the loop that ran
+            from . import api
+
+            dev_i = int(getattr(self.solver, "device", 0))
+
+            def resize(a, shape):
+                if tuple(int(v) for v in shape[:2]) == tuple(a.shape[:2]):
+                    return a
+                return api.resize2d(np.ascontiguousarray(a, np.float64), shape, method, dev_i)
         for step_index, step in enumerate(dim_steps):
             t_a = time.perf_counter()
             shape = tuple(int(s) for s in step)
@@ -184,10 +231,12 @@ class HipIDEALFitter(HipFitterBase):
                 lower = np.broadcast_to(lo_vals, (*shape, n_params)).copy()
                 upper = np.broadcast_to(hi_vals, (*shape, n_params)).copy()
             else:
-                p0 = np.clip(resize2d(self.step_params[-1], shape, method), lo_vals, hi_vals)
+                p0 = np.clip(resize(self.step_params[-1], shape), lo_vals, hi_vals)
+                if frac is not None:  # the device path's pnx_ideal_bounds_simplex_f64: both paths solve the same problem
+                    p0 = project_fractions(p0, lo_vals, hi_vals, *frac)
                 lower = np.clip(p0 * (1 - tol_vals), lo_vals, hi_vals)
                 upper = np.clip(p0 * (1 + tol_vals), lo_vals, hi_vals)
-            img = resize2d(image, shape, method)
+            img = resize(image, shape)
             mask = resize2d(seg4, shape, method)[..., 0] > self.segmentation_threshold
             if not mask.any():  # ideal.py:199-209: ROI too sparse at this level -> fit everything
                 mask = np.ones(shape, dtype=bool)
@@ -228,7 +277,8 @@ class HipIDEALFitter(HipFitterBase):
     def _fit_device(self, xdata, image, segmentation, dim_steps, names, p0_vals, lo_vals, hi_vals, tol_vals, t0, fit_kwargs):
         """Same level loop as above with everything between the first upload and the per-level map download in HBM:
         pnx_resize2d_f64 (image, mask, previous maps), pnx_ideal_bounds_f64 (p0 / bounds of the level) and the
-        device-pointer fit (pnx_curvefit_batch_f64, per-voxel p0 / bounds); mask thresholding + compaction, row gathers, the
+        device-pointer fit (pnx_curvefit_batch_f64, per-voxel p0 / bounds) -- pnx_ideal_bounds_simplex_f64 and
+        pnx_curvefit_simplex_f64 for a solver with the constraint f1 + f2 <= 1; mask thresholding + compaction, row gathers, the
         map scatter and SS_tot are HIP kernels too (pnx_mask_select_f64, pnx_gather_rows_f64, pnx_scatter_rows_t_f64,
         pnx_row_ss_tot_f64).  torch allocates, uploads and downloads; the level statistics use its reductions."""
         import torch
@@ -253,6 +303,8 @@ class HipIDEALFitter(HipFitterBase):
         seg_d = torch.from_numpy(np.ascontiguousarray(segmentation, np.float64)).to(dev)
         seg_thr = float(np.float32(self.segmentation_threshold)) if seg_f32 else float(self.segmentation_threshold)
         kw = dict(s._kernel_t1)
+        frac = _fraction_rows(s)
+        sigma = getattr(s, "sigma", None)
         self.step_params, self.stage_times_ = [], []
         prev = None  # (px, py, Z, n) device map of the previous level
         for step_index, step in enumerate(dim_steps):
@@ -294,7 +346,10 @@ class HipIDEALFitter(HipFitterBase):
                     m = mg
                 p0_d = torch.empty((n, n_px), dtype=torch.float64, device=dev)
                 lo_d, hi_d = torch.empty_like(p0_d), torch.empty_like(p0_d)
-                api.ideal_bounds_device(m, n_px, lo_vals, hi_vals, tol_vals, p0_d, lo_d, hi_d, dev_i, stream)
+                if frac is None:
+                    api.ideal_bounds_device(m, n_px, lo_vals, hi_vals, tol_vals, p0_d, lo_d, hi_d, dev_i, stream)
+                else:
+                    api.ideal_bounds_simplex_device(m, n_px, lo_vals, hi_vals, tol_vals, *frac, p0_d, lo_d, hi_d, dev_i, stream)
                 p0_a, lo_a, hi_a = p0_d, lo_d, hi_d
             else:
                 p0_a, lo_a, hi_a = p0_vals, lo_vals, hi_vals
@@ -306,10 +361,12 @@ class HipIDEALFitter(HipFitterBase):
             pcov = torch.empty((n_px, n, n), dtype=torch.float64, device=dev) if last else None
             opts = api.make_opts(s._kernel_model, N, [], per_voxel, False, int(s.max_iter), float(s.tol),
                                  float(getattr(s, "xtol", 1e-8)), float(getattr(s, "gtol", 1e-8)),
-                                 s.jacobian_mode, kw["t1_mode"], kw["tr"], kw["tm"])
+                                 s.jacobian_mode, kw["t1_mode"], kw["tr"], kw["tm"], sigma=sigma,
+                                 absolute_sigma=getattr(s, "absolute_sigma", False))
             t_b = time.perf_counter()
             cost0 = None
-            if per_voxel and kw["t1_mode"] == 0:
+            # (the sweep is unweighted: with a sigma its cost is not the fit's, and the comparison below would mean nothing)
+            if per_voxel and kw["t1_mode"] == 0 and sigma is None:
                 # cost at the level's start values: one pass of the HBM-streaming residual sweep (pnx_sweep_f64) over
                 # the same signal rows and the parameter-major p0 array the fit is about to start from
                 cost0 = torch.empty(n_px, dtype=torch.float64, device=dev)
@@ -317,10 +374,22 @@ class HipIDEALFitter(HipFitterBase):
                 h0 = torch.empty((n * (n + 1) // 2, n_px), dtype=torch.float64, device=dev)
                 api.sweep_device(s._kernel_model, n_px, xdata, pixels, p0_d, cost0, g0, h0, dev_i, stream)
                 del g0, h0
-            api.curvefit_device(opts, n_px, xdata, pixels, p0_a, lo_a, hi_a, None, popt, pcov, status, nfev, cost,
-                                dev_i, stream)
+            if frac is None:
+                api.curvefit_device(opts, n_px, xdata, pixels, p0_a, lo_a, hi_a, None, popt, pcov, status, nfev, cost,
+                                    dev_i, stream)
+            else:
+                lam = torch.empty(n_px, dtype=torch.float64, device=dev)
+                face = torch.empty(n_px, dtype=torch.int8, device=dev)
+                api.curvefit_constrained_device(opts, n_px, xdata, pixels, p0_a, lo_a, hi_a, popt, pcov, status, nfev, cost,
+                                                lam, face, dev_i, stream)
             stats = {"shape": shape, "n_pixels": n_px, "converged_frac": float((status > 0).double().mean()),
                      "cost_mean": float(cost.mean())}
+            if frac is not None:
+                ok = status > 0
+                stats["n_face"] = int((face != 0).sum())
+                stats["n_bad_bounds"] = int((status == -1).sum())  # empty per-voxel window, or empty intersection on the face
+                # share of the converged voxels inside the simplex, the fp64 sum as written (a face voxel's f2 is 1 - f1)
+                stats["feasible_frac"] = float(((popt[frac[0]] + popt[frac[1]]) <= 1.0)[ok].double().mean()) if bool(ok.any()) else 1.0
             if cost0 is not None:
                 ok = status > 0
                 stats["cost_p0_mean"] = float(cost0.mean())
@@ -339,6 +408,8 @@ class HipIDEALFitter(HipFitterBase):
             self.stage_times_.append((round(t_b - t_a, 3), round(t_c - t_b, 3), round(time.perf_counter() - t_c, 3)))
         res = {"popt": api.download(popt, dev_i, stream), "pcov": api.download(pcov, dev_i, stream),
                "status": status.cpu().numpy(), "nfev": nfev.cpu().numpy(), "cost": api.download(cost, dev_i, stream)}
+        if frac is not None:  # what solver.fit() of the last level leaves in diagnostics_
+            res["lambda"], res["face"] = api.download(lam, dev_i, stream), face.cpu().numpy()
         ss_d = torch.empty(n_px, dtype=torch.float64, device=dev)
         api.row_ss_tot_device(pixels, n_px, N, ss_d, dev_i, stream)  # SS_tot of the fitted rows, reduced in HBM
         ss_tot = ss_d.cpu().numpy()
