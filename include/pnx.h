@@ -387,6 +387,33 @@ PNX_API int pnx_curvefit_predict_f64(const pnx_curvefit_opts *opts, int64_t n_vo
                              const double *fixed, const double *y, double *pred, double *ss_res, int mem, int device,
                              void *stream);
 /*
+ * Per-voxel start values for the curve fit from a dictionary search.  The reference starts every voxel of a
+ * volume from one p0; here every voxel is matched against n_atoms candidate parameter vectors ("atoms") and starts from the best:
+ *   s_g = model(b; atom_g, fixed), evaluated by pnx_curvefit_predict_f64's kernel (the fit's own arithmetic: all seven layouts,
+ *     shared fixed parameters, the T1 / STEAM factor); with opts->sigma rows and signals are multiplied by 1 / sigma_i, as the fit does;
+ *   cost_g(v) = 0.5 (||y_v||^2 - 2 y_v . s_g + ||s_g||^2);  best[v] = the argmin over g, the lowest index among equal costs;
+ *   p0_out[:, v] = atoms[:, best[v]], copied;  cost[v] = the cost of the chosen atom.
+ * The product y . s_g runs on the fp64 matrix cores and never reaches memory: a voxel costs its signal row in and p0 / best / cost
+ * out.  The cost is evaluated in the expanded form above: it carries the rounding of two dot products of n_b terms, at most
+ * 4 n_b 2^-52 (||y||^2 + max_g ||s_g||^2), so two atoms whose costs differ by less than that may swap.
+ * project_amplitude != 0: for the layouts with a free linear amplitude S0 (PNX_MODEL_MONO, PNX_MODEL_BI_S0, PNX_MODEL_TRI_S0;
+ *   PNX_ERR_INVALID otherwise) the dictionary is built with S0 = 1 whatever the atoms' S0 row holds, and per voxel and atom
+ *   a = clip(y . s_g / ||s_g||^2, lo_S0, hi_S0) (lo_S0 for an all-zero row),  cost_g = 0.5 (||y||^2 - 2 a y . s_g + a^2 ||s_g||^2);
+ *   the chosen a is written into the S0 row of p0_out.  A small dictionary then serves signals of any amplitude.
+ * A voxel with a non-finite (weighted) signal gets best = -1, cost = NaN and p0_out = atoms[:, 0]; the fit behind it reports its
+ * usual status for it.  Its neighbours are not affected.
+ *   opts: model, n_b, n_free, n_fixed, free_idx, fixed_idx, t1_mode, tr, tm, sigma are read;
+ *   b (n_b,) host; y (n_vox, n_b) host|device; atoms (n_free, n_atoms) host, parameter-major like p0, 1 <= n_atoms <= 4096;
+ *   fixed (n_fixed,) host or NULL; lo, hi (n_free,) host: every atom must lie inside them (the fit refuses a start value outside
+ *   its bounds), PNX_ERR_INVALID names the first that does not;
+ *   p0_out (n_free, n_vox), best (n_vox) int32 or NULL, cost (n_vox) or NULL: out, host|device as `mem`.
+ * PNX_MEM_DEVICE only enqueues (the dictionary lives in a stream-ordered buffer); PNX_MEM_HOST goes through the chunk ring.
+ * Not built, PNX_ERR_UNSUPPORTED with a message before any device work: per_voxel_p0_bounds, fixed_per_voxel, queue_order.
+ */
+PNX_API int pnx_curvefit_grid_start_f64(const pnx_curvefit_opts *opts, int64_t n_vox, const double *b, const double *y, int n_atoms,
+                                const double *atoms, const double *fixed, const double *lo, const double *hi, int project_amplitude,
+                                double *p0_out, int32_t *best, double *cost, int mem, int device, void *stream);
+/*
  * float32 parameter maps (io/nifti.py:279-312 reconstruct_maps): out (n_spatial, k) zero filled, then
  * out[linear_index[i], :] = (float) values[i, :] for the n_px fitted voxels (linear_index = C-order index into the
  * (X, Y, Z) grid).  values (n_px, k) float64, linear_index (n_px) int64, out float32: host|device as `mem`.

@@ -27,7 +27,7 @@ ABI_SYMBOLS = [
     "pnx_mask_select_f64", "pnx_gather_rows_f64", "pnx_scatter_rows_t_f64", "pnx_row_ss_tot_f64", "pnx_upload", "pnx_download",
     "pnx_label_sums_f64", "pnx_release_staging", "pnx_queue_order_f64",
     "pnx_nnls_fit_stats_f64", "pnx_nnls_solve_peaks_stats_f64", "pnx_curvefit_predict_f64", "pnx_curvefit_fast_f32",
-    "pnx_curvefit_simplex_f64", "pnx_ideal_bounds_simplex_f64",
+    "pnx_curvefit_simplex_f64", "pnx_ideal_bounds_simplex_f64", "pnx_curvefit_grid_start_f64",
 ]
 
 
@@ -114,6 +114,9 @@ def load():
     lib.pnx_curvefit_simplex_f64.restype = C.c_int  # pnx_curvefit_batch_f64's arguments, then lambda and face in front of mem
     lib.pnx_curvefit_simplex_f64.argtypes = [C.POINTER(CurvefitOpts), C.c_int64, dp, dp, dp, dp, dp, dp, dp, dp, vp, vp,
                                              dp, dp, vp, C.c_int, C.c_int, vp]
+    lib.pnx_curvefit_grid_start_f64.restype = C.c_int  # opts, n_vox, b, y, n_atoms, atoms, fixed, lo, hi, project, p0_out, best, cost
+    lib.pnx_curvefit_grid_start_f64.argtypes = [C.POINTER(CurvefitOpts), C.c_int64, dp, dp, C.c_int, dp, dp, dp, dp, C.c_int, dp, vp, dp,
+                                                C.c_int, C.c_int, vp]
     lib.pnx_nnls_plan_create.restype = C.c_int
     lib.pnx_nnls_plan_create.argtypes = [C.POINTER(vp), C.c_int, C.c_int, dp, dp, C.c_int, C.c_int]
     lib.pnx_nnls_plan_destroy.restype = C.c_int

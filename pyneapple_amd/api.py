@@ -225,6 +225,60 @@ def curvefit_device(opts, n_vox, b, y, p0, lo, hi, fixed, popt, pcov, status, nf
         opts.queue_order = None
 
 
+GRID_MAX_ATOMS = 4096  # kGridMaxAtoms of csrc/pnx_grid_args.hpp
+PROJECT_MODELS = ("mono", "bi_s0", "tri_s0")  # the layouts with a linear amplitude S0
+
+
+def grid_start(model, b, y, atoms, lo, hi, *, fixed_idx=(), fixed_vals=None, sigma=None, project_amplitude=False, t1_mode=0,
+               tr=0., tm=0., device=0, out=None):
+    """Per-voxel start values from a dictionary search on host (numpy) arrays (pnx_curvefit_grid_start_f64; method: include/pnx.h).
+
+    atoms (n_free, n_atoms <= 4096) parameter-major like p0, every column a candidate start inside the shared bounds lo / hi
+    (n_free,); fixed_idx / fixed_vals (n_fixed,) and sigma as `curvefit` takes them (shared values only).  project_amplitude: fit
+    the linear amplitude S0 per voxel and atom (clipped to its bounds) instead of taking it from the atoms; models "mono",
+    "bi_s0", "tri_s0".  Returns dict(p0 (n_free, n_vox) -- ready for `curvefit(..., p0=p0, lo tiled, hi tiled)` --, best (n_vox,)
+    int32 index of the chosen atom, -1 for a non-finite signal, cost (n_vox,) 0.5 ||(y - s_best) / sigma||^2).
+    `out`: optional dict of preallocated result arrays ("p0", "best", "cost")."""
+    _lib.require_device()
+    b = np.ascontiguousarray(b, np.float64)
+    y = np.ascontiguousarray(np.atleast_2d(y), np.float64)
+    n_vox, n_b = y.shape
+    if b.shape != (n_b,):
+        raise ValueError(f"b has shape {b.shape}, expected ({n_b},)")
+    atoms, lo, hi = (np.ascontiguousarray(a, np.float64) for a in (atoms, lo, hi))
+    fv = None
+    if len(fixed_idx):
+        fv = np.ascontiguousarray(fixed_vals, np.float64)
+        if fv.ndim != 1:
+            raise ValueError("grid_start takes shared fixed values (n_fixed,): per-voxel fixed maps are not built")
+    o = make_opts(model, n_b, fixed_idx, jac="analytic", t1_mode=t1_mode, tr=tr, tm=tm, sigma=sigma)
+    n = o.n_free
+    if atoms.ndim != 2 or atoms.shape[0] != n or lo.shape != (n,) or hi.shape != (n,):
+        raise ValueError(f"atoms must have shape ({n}, n_atoms), lo / hi ({n},)")
+    if fv is not None and fv.shape != (o.n_fixed,):
+        raise ValueError("fixed_vals has the wrong shape")
+    p0 = _out(out, "p0", (n, n_vox), np.float64)
+    best = _out(out, "best", (n_vox,), np.int32)
+    cost = _out(out, "cost", (n_vox,), np.float64)
+    check(load().pnx_curvefit_grid_start_f64(C.byref(o), n_vox, ptr(b), ptr(y), int(atoms.shape[1]), ptr(atoms), ptr(fv), ptr(lo), ptr(hi),
+                                             int(bool(project_amplitude)), ptr(p0), ptr(best), ptr(cost), MEM_HOST, int(device), None))
+    return dict(p0=p0, best=best, cost=cost)
+
+
+def grid_start_device(opts, n_vox, b, y, atoms, fixed, lo, hi, project_amplitude, p0, best, cost, device, stream=None):
+    """Enqueue the dictionary search on HBM-resident float64 torch tensors (asynchronous; caller synchronises): y (n_vox, n_b),
+    p0 (n_free, n_vox), best (n_vox,) int32 or None, cost (n_vox,) or None on the device; b, atoms (n_free, n_atoms), shared fixed
+    values, lo, hi are host arrays.  `opts` from make_opts (model, fixed positions, T1, sigma)."""
+    b, atoms, lo, hi = (np.ascontiguousarray(a, np.float64) for a in (b, atoms, lo, hi))
+    if fixed is not None:
+        fixed = np.ascontiguousarray(fixed, np.float64)
+    if atoms.ndim != 2:
+        raise ValueError("atoms must have shape (n_free, n_atoms)")
+    check(load().pnx_curvefit_grid_start_f64(C.byref(opts), int(n_vox), ptr(b), ptr(y), int(atoms.shape[1]), ptr(atoms), ptr(fixed), ptr(lo),
+                                             ptr(hi), int(bool(project_amplitude)), ptr(p0), ptr(best), ptr(cost), MEM_DEVICE, int(device),
+                                             stream))
+
+
 class NnlsPlan:
     """Shared part of one NNLS fit: A = [basis; reg] uploaded and reduced to its Gram form once."""
 

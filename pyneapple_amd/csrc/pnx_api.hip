@@ -18,6 +18,8 @@
 
 #include "pnx_curvefit_f32_kernel.hpp"
 #include "pnx_curvefit_kernel.hpp"
+#include "pnx_grid.hpp"
+#include "pnx_grid_args.hpp"
 #include "pnx_host_pipeline.hpp"
 #include "pnx_internal.hpp"
 #include "pnx_nnls.hpp"
@@ -1149,6 +1151,45 @@ int pnx_curvefit_predict_f64(const pnx_curvefit_opts *o, int64_t n_vox, int n_x,
                       [&](size_t n, const DevSet &D, hipStream_t s) {
                           return model_predict_device(&c, (int64_t)n, n_x, x, D.d(PR_P), fpv ? D.d(PR_FX) : fixed, D.d(PR_Y), D.d(PR_PRED),
                                                       D.d(PR_SS), s);
+                      });
+}
+
+// ---- per-voxel start values from a dictionary search (kernels: pnx_grid.hip, argument checks: pnx_grid_args.hpp) ------------
+int pnx_curvefit_grid_start_f64(const pnx_curvefit_opts *o, int64_t n_vox, const double *b, const double *y, int n_atoms,
+                                const double *atoms, const double *fixed, const double *lo, const double *hi, int project_amplitude,
+                                double *p0_out, int32_t *best, double *cost, int mem, int device, void *stream) {
+    if (!o) return set_error(PNX_ERR_INVALID, "opts is NULL");
+    // the fields the search reads, checked as the fit checks them: jac_mode and the tolerances are not looked at
+    pnx_curvefit_opts c = *o;
+    c.jac_mode = PNX_JAC_ANALYTIC;
+    c.ftol = c.xtol = c.gtol = 0.0;
+    int rc = check_curvefit_opts(&c);
+    if (rc) return rc;
+    int s0_row = -1;
+    if ((rc = grid_check_args(&c, n_vox, b, y, n_atoms, atoms, fixed, lo, hi, project_amplitude, p0_out, mem, &s0_row))) return rc;
+    if (n_vox == 0) return PNX_OK;
+    DeviceInfo *dev;
+    if ((rc = get_device(device, &dev))) return rc;
+    PNX_HIP(hipSetDevice(device));
+    hipStream_t st = (hipStream_t)stream;
+    AsyncBuf dict_buf;  // the dictionary: built once per call, stream-ordered, freed behind the work that reads it
+    GridDict D;
+    if ((rc = dict_buf.alloc(grid_dict_bytes(c.n_free, n_atoms, c.n_b), st))) return rc;
+    if ((rc = grid_dict_build(&c, b, n_atoms, atoms, fixed, lo, hi, s0_row, dict_buf.p, &D, st))) return rc;
+    if (mem == PNX_MEM_DEVICE) return grid_match_device(D, n_vox, y, p0_out, best, cost, dev->cus, st);
+    // host arrays: the chunk ring; its streams read the dictionary, so it is complete before the first chunk starts
+    PNX_HIP(hipStreamSynchronize(st));
+    enum { GS_Y, GS_P0, GS_BEST, GS_COST };
+    ArrayTable A;
+    A.add(y, sizeof(double), c.n_b, false);
+    A.add(p0_out, sizeof(double), c.n_free, true).pmajor = true;
+    A.add(best, sizeof(int32_t), 1, true);
+    A.add(cost, sizeof(double), 1, true);
+    HostCallGuard hg;
+    const size_t chunk = (size_t)dev_env_int("PNX_HOST_CHUNK", 3 << 18, 1024, 1 << 26);
+    return chunk_ring(A, (size_t)n_vox, chunk, dev_env_int("PNX_HOST_SLOTS", 3, 2, 8), dev_env_int("PNX_HOST_KSTREAMS", 2, 1, 4), hg.touchers(),
+                      device, st, [&](size_t n, const DevSet &S, hipStream_t s) {
+                          return grid_match_device(D, (int64_t)n, S.d(GS_Y), S.d(GS_P0), (int32_t *)S.dev[GS_BEST], S.d(GS_COST), dev->cus, s);
                       });
 }
 

@@ -123,6 +123,15 @@ class HipCurveFitSolver(CurveFitBase):
         precision: "float64" (default) or "float32": fp32 ARITHMETIC on a separate kernel (pnx_curvefit_fast_f32).  Implies
             float32 arrays across the ABI and the analytic Jacobian; results are float32-quality minima, not SciPy-parity
             results.  Not built there, hence a ValueError: jacobian="fd", fixed parameters, a T1 model, sigma.
+        p0_grid: None (default: every voxel starts from `p0`, as in the reference) or a dict from parameter name to a sequence
+            of candidate values (TOML: arrays under [Fitting.solver.p0_grid]).  The candidates ("atoms") are the Cartesian
+            product of the sequences in `model.param_names` order, the last parameter varying fastest; a parameter the dict
+            does not name takes its scalar `p0`.  Each voxel then starts from the atom whose model signal is closest to its
+            own (pnx_curvefit_grid_start_f64) unless `fit()` is given an explicit `p0`; `diagnostics_` gains "p0_atom" (int32
+            index of the atom, -1 for a non-finite signal) and "p0_cost".  At most 4096 atoms, every value inside `bounds`.
+            Not built with it, hence a ValueError: precision / io_dtype "float32", per-pixel fixed parameters, per-voxel bounds.
+        p0_grid_project: fit the amplitude S0 per voxel and atom, clipped to its bounds, instead of taking it from the atoms
+            (so S0 needs no entry in p0_grid).  Default: True exactly when the model has a free S0.
     """
 
     def __init__(self, model: Any, max_iter: int, tol: float, p0: dict[str, float],
@@ -145,6 +154,8 @@ class HipCurveFitSolver(CurveFitBase):
         # The reference forwards every remaining key into scipy.optimize.curve_fit (curvefit.py:295-306).  The kernel
         # implements least_squares' xtol / gtol; anything else would change SciPy's result and there is no CPU path to
         # honour it, so it is refused instead of being dropped silently (keys at their SciPy default are accepted).
+        p0_grid = solver_kwargs.pop("p0_grid", None)
+        p0_grid_project = solver_kwargs.pop("p0_grid_project", None)
         self.xtol = float(solver_kwargs.pop("xtol", 1e-8))
         self.gtol = float(solver_kwargs.pop("gtol", 1e-8))
         # sigma / absolute_sigma: the two curve_fit arguments the reference's docstring names (curvefit.py:33).  A scalar or 1-D
@@ -169,7 +180,8 @@ class HipCurveFitSolver(CurveFitBase):
         unknown = set(solver_kwargs) - {"n_pools"}
         if unknown:
             raise ValueError(f"HipCurveFitSolver got solver arguments it cannot honour: {sorted(unknown)} "
-                             "(supported: sigma, absolute_sigma, xtol, gtol, jacobian, device, n_gpus, io_dtype, precision, n_pools)")
+                             "(supported: sigma, absolute_sigma, xtol, gtol, jacobian, device, n_gpus, io_dtype, precision, p0_grid, "
+                             "p0_grid_project, n_pools)")
         if method != "trf":
             raise ValueError(f"HipCurveFitSolver implements method='trf' only (got {method!r}); "
                              "use the reference CurveFitSolver for 'dogbox' / 'lm'.")
@@ -203,6 +215,47 @@ class HipCurveFitSolver(CurveFitBase):
                 raise ValueError("precision='float32' is not built with the T1 / STEAM factor; use precision='float64'")
             if getattr(model, "fixed_params", None):
                 raise ValueError("precision='float32' is not built with fixed parameters; use precision='float64'")
+        self._set_p0_grid(p0_grid, p0_grid_project)
+
+    # ------------------------------------------------------------------ p0_grid: the atoms of the dictionary search
+    def _set_p0_grid(self, p0_grid, project):
+        """Validates `p0_grid` / `p0_grid_project` and builds the atoms (n_free, n_atoms); nothing is set up without p0_grid."""
+        self.p0_grid, self.p0_grid_project, self._p0_atoms = None, False, None
+        if p0_grid is None:
+            if project:
+                raise ValueError("p0_grid_project=True needs a p0_grid")
+            return
+        import itertools
+
+        if self.precision == "float32" or self.io_dtype is not np.float64:
+            raise ValueError("p0_grid is built for precision='float64' and io_dtype='float64': the dictionary search reads and "
+                             "writes float64 arrays")
+        names = list(self.model.param_names)
+        if not isinstance(p0_grid, dict):
+            raise ValueError("p0_grid must be a dict from parameter name to a sequence of candidate values")
+        unknown = [n for n in p0_grid if n not in names]
+        if unknown:
+            raise ValueError(f"p0_grid names parameters the model does not fit: {unknown} (free parameters: {names})")
+        has_s0 = "S0" in names and self._kernel_model in api.PROJECT_MODELS
+        if project is None:
+            project = has_s0
+        if project and not has_s0:
+            raise ValueError(f"p0_grid_project=True needs a model with a free amplitude S0 {api.PROJECT_MODELS}, not {self._kernel_model!r}")
+        axes = []
+        for n in names:
+            vals = np.atleast_1d(np.asarray(p0_grid[n], float)) if n in p0_grid else np.array([float(self.p0[n])])
+            lo, hi = self.bounds[n]
+            if vals.ndim != 1 or vals.size < 1:
+                raise ValueError(f"p0_grid[{n!r}] must be a non-empty 1-D sequence of values")
+            if not ((vals >= lo) & (vals <= hi)).all():
+                raise ValueError(f"p0_grid[{n!r}] holds a value outside the bounds ({lo}, {hi}) of {n}")
+            axes.append(vals)
+        n_atoms = int(np.prod([a.size for a in axes], dtype=np.int64))
+        if n_atoms > api.GRID_MAX_ATOMS:
+            raise ValueError(f"p0_grid spans {n_atoms} atoms, more than the {api.GRID_MAX_ATOMS} the dictionary search takes")
+        self.p0_grid = {n: list(map(float, np.atleast_1d(v))) for n, v in p0_grid.items()}
+        self.p0_grid_project = bool(project)
+        self._p0_atoms = np.ascontiguousarray(np.array(list(itertools.product(*axes)), float).T)  # (n_free, n_atoms)
 
     # ------------------------------------------------------------------ p0 / bounds (curvefit.py:319-392)
     def _prepare_p0_bounds(self, p0, bounds, n_pixels):
@@ -333,8 +386,14 @@ class HipCurveFitSolver(CurveFitBase):
                 fixed_vals = np.array([float(fixed[all_names[i]]) for i in fixed_idx])
             jac = "analytic"  # the reference passes model.jacobian_with_fixed here (curvefit.py:279-281)
 
+        grid = self._p0_atoms is not None and p0 is None  # an explicit p0 wins (IDEAL and Segmented pass their own)
+        if grid:
+            if pixel_fixed_params:
+                raise ValueError("p0_grid is not built with per-pixel fixed parameters (the dictionary would differ from voxel to voxel)")
+            if per_voxel:
+                raise ValueError("p0_grid works with shared bounds: one dictionary serves the whole call")
         res = self._run(xdata, np.ascontiguousarray(ydata, self.io_dtype), p0_a, lo_a, hi_a, per_voxel, fixed_idx,
-                        fixed_vals, jac)
+                        fixed_vals, jac, grid)
         self._pack(res, n_pixels, free_names)
         return self
 
@@ -349,6 +408,9 @@ class HipCurveFitSolver(CurveFitBase):
         self.params_ = {name: [float(popt[i, 0])] if n_pixels == 1 else popt[i] for i, name in enumerate(free_names)}
         self.diagnostics_ = {"pcov": (pcov[0] if n_pixels == 1 else pcov) if pcov is not None else None, "n_pixels": n_pixels,
                              "status": status, "nfev": res["nfev"], "cost": res["cost"]}
+        for key in ("p0_atom", "p0_cost"):  # a fit that started from the dictionary search (p0_grid)
+            if key in res:
+                self.diagnostics_[key] = res[key]
 
     _extra_outputs: dict = {}  # further per-voxel result arrays of a subclass's batch call: key -> dtype
 
@@ -356,7 +418,18 @@ class HipCurveFitSolver(CurveFitBase):
         """The array-level call of one shard (a subclass swaps in another one with api.curvefit's signature)."""
         return api.curvefit(*args, **kw)
 
-    def _run(self, xdata, ydata, p0, lo, hi, per_voxel, fixed_idx, fixed_vals, jac):
+    def _grid_fit(self, xdata, ydata, lo, hi, fixed_vals, device, kw, out=None):
+        """One shard with p0_grid: the dictionary search, then the fit from its per-voxel start values under the shared bounds."""
+        out = out or {}
+        gs = api.grid_start(self._kernel_model, xdata, ydata, self._p0_atoms, lo, hi, fixed_idx=kw["fixed_idx"], fixed_vals=fixed_vals,
+                            sigma=self.sigma, project_amplitude=self.p0_grid_project, device=device, **self._kernel_t1,
+                            out={"best": out.get("p0_atom"), "cost": out.get("p0_cost")})
+        tile = lambda a: np.ascontiguousarray(np.repeat(a[:, None], ydata.shape[0], axis=1))
+        res = self._batch_fit(self._kernel_model, xdata, ydata, gs["p0"], tile(lo), tile(hi), fixed_vals=fixed_vals, device=device,
+                              out=out or None, **kw)
+        return dict(res, p0_atom=gs["best"], p0_cost=gs["cost"])
+
+    def _run(self, xdata, ydata, p0, lo, hi, per_voxel, fixed_idx, fixed_vals, jac, grid=False):
         n_vox = ydata.shape[0]
         kw = dict(max_nfev=int(self.max_iter), ftol=float(self.tol), xtol=self.xtol, gtol=self.gtol, jac=jac,
                   fixed_idx=fixed_idx, sigma=self.sigma, absolute_sigma=self.absolute_sigma, **self._kernel_t1)
@@ -364,6 +437,8 @@ class HipCurveFitSolver(CurveFitBase):
             kw["precision"] = "float32"
         n_dev = max(1, min(self.n_gpus, n_vox))
         if n_dev == 1:
+            if grid:
+                return self._grid_fit(xdata, ydata, lo, hi, fixed_vals, self.device, kw)
             return self._batch_fit(self._kernel_model, xdata, ydata, p0, lo, hi, fixed_vals=fixed_vals,
                                    device=self.device, **kw)
         parts = _split(n_vox, n_dev)
@@ -373,6 +448,8 @@ class HipCurveFitSolver(CurveFitBase):
         dt = ydata.dtype
         full = {"pcov": np.empty((n_vox, n, n), dt), "status": np.empty(n_vox, np.int8), "nfev": np.empty(n_vox, np.int32),
                 "cost": np.empty(n_vox, dt), **{key: np.empty(n_vox, d) for key, d in self._extra_outputs.items()}}
+        if grid:
+            full.update(p0_atom=np.empty(n_vox, np.int32), p0_cost=np.empty(n_vox, np.float64))
 
         def work(k):
             a, b = parts[k]
@@ -384,6 +461,8 @@ class HipCurveFitSolver(CurveFitBase):
                   np.ascontiguousarray(hi[:, sl])) if per_voxel else (p0, lo, hi)
             dev_k = _shard_device(self.device, k)
             with pinned_to_gpu(dev_k):  # this thread and the call's helper threads stay on the NUMA node of their GPU
+                if grid:
+                    return self._grid_fit(xdata, ydata[sl], lo, hi, fv, dev_k, kw, out={key: v[sl] for key, v in full.items()})["popt"]
                 return self._batch_fit(self._kernel_model, xdata, ydata[sl], *pv, fixed_vals=fv,
                                        device=dev_k, out={key: v[sl] for key, v in full.items()}, **kw)["popt"]
 
@@ -408,6 +487,9 @@ class HipConstrainedCurveFitSolver(HipCurveFitSolver):
     def __init__(self, model: Any, p0: dict[str, float], bounds: dict[str, tuple[float, float]], max_iter: int = 250,
                  tol: float = 1e-8, fraction_constraint: bool = True, verbose: bool = False, method: str = "SLSQP",
                  multi_threading: bool = False, use_jacobian: bool = True, **solver_kwargs):
+        if solver_kwargs.get("p0_grid") is not None or solver_kwargs.get("p0_grid_project") is not None:
+            raise ValueError("p0_grid is not built for HipConstrainedCurveFitSolver: the dictionary knows nothing of the constraint "
+                             "f1 + f2 <= 1 and the constrained fit takes one shared start; use HipCurveFitSolver")
         if fraction_constraint and not getattr(model, "fit_reduced", False):  # constrained_curvefit.py:72-79
             raise ValueError("fraction_constraint=True requires fit_reduced=True. In reduced mode the signal is normalised to S0=1 "
                              "before fitting, so the hard constraint sum(f_i) <= 1 is physically meaningful. Use fit_reduced=True "
