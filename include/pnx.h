@@ -414,6 +414,42 @@ PNX_API int pnx_curvefit_grid_start_f64(const pnx_curvefit_opts *opts, int64_t n
                                 const double *atoms, const double *fixed, const double *lo, const double *hi, int project_amplitude,
                                 double *p0_out, int32_t *best, double *cost, int mem, int device, void *stream);
 /*
+ * Log-linear mono-exponential fit, ln S = ln S0 - b D by (weighted) linear least squares per voxel: the ADC
+ * map, step 1 of a segmented IVIM fit, a cheap source of S0 / D start values.  A closed form over one pass of the data: a voxel
+ * costs its signal row in and its results out.  Per voxel, in fp64, in the order written:
+ *   use[i]: the caller's 0/1 mask over the b-values (NULL = all).  A non-finite y_i with use[i]: status -2, every output NaN
+ *     (n_used 0), the curve fit's convention; the voxel's neighbours are not affected.
+ *   U = { i : use[i] and y_i > 0 }, n_used = |U|: a non-positive sample has no logarithm and is left out, not clamped.
+ *   l_i = log(y_i);  w_i = 1 (weighting 0) or y_i^2 (weighting 1, the usual weights of log-transformed data).
+ *   bm = sum w b / sum w;  lm = sum w l / sum w;  Sbb = sum w (b - bm)^2;  D = -sum w (b - bm)(l - lm) / Sbb;  a = lm + D bm;
+ *   S0 = exp(a) -- the centred form, never the raw 2 x 2 normal matrix.
+ *   n_reweight (0 .. 8) further passes repeat the fit over the same U with w_i = exp(a - b_i D)^2 of the previous estimate.
+ *   status 0, parameters / pcov / ss_res NaN: n_used < 2, Sbb == 0 in any pass, or a non-finite a or D (weights that overflow);
+ *   status 1 otherwise.
+ *   pcov of (S0, D): for n_used >= 3, s^2 = sum w r^2 / (n_used - 2) with r_i = l_i - (a - b_i D) and the last pass's weights,
+ *     var a = s^2 (1 / sum w + bm^2 / Sbb), cov(a, D) = s^2 bm / Sbb, var D = s^2 / Sbb (s^2 (X^T W X)^-1 from the centred sums),
+ *     mapped to (S0, D) by the delta method: [[S0^2 var a, S0 cov], [S0 cov, var D]].  n_used == 2: NaN, status stays 1.
+ *   clip != 0: S0 and D are clipped into [lo[0], hi[0]] and [lo[1], hi[1]] after the fit; a voxel that was moved gets status 2;
+ *     pcov stays as computed.
+ *   ss_res = sum over use[i] of (S0 exp(-b_i D) - y_i)^2: the SIGNAL-domain residual at the returned (clipped) point over every
+ *     masked-in sample, the non-positive ones included, so that R^2 follows from pnx_row_ss_tot_f64 as for the other solvers.
+ *   b (n_b,) host; use (n_b,) uint8 host or NULL; lo, hi (2,) host when clip (not read otherwise);
+ *   y (n_vox, n_b) in; params (2, n_vox) parameter-major [S0, D]; pcov (n_vox, 2, 2) or NULL; status (n_vox) int8 or NULL;
+ *   n_used (n_vox) int32 or NULL; ss_res (n_vox) or NULL: host|device as `mem`.
+ * pnx_loglinear_f32: fp32 storage of b, lo, hi, y, params, pcov and ss_res, the same fp64 arithmetic (as pnx_curvefit_batch_f32;
+ *   the kernel reads and writes float, nothing is staged).
+ * PNX_MEM_DEVICE only enqueues; PNX_MEM_HOST goes through the chunk ring.  PNX_ERR_INVALID with a message that names the
+ * argument, before any device work: n_b outside 2 .. PNX_MAX_BVALUES, a NULL b / y / params, a non-finite b, weighting not 0 / 1,
+ * n_reweight outside 0 .. 8, a mask that leaves fewer than 2 b-values or fewer than 2 distinct ones, clip with NULL bounds or
+ * lo >= hi, mem not host / device.
+ */
+PNX_API int pnx_loglinear_f64(int64_t n_vox, int n_b, const double *b_host, const uint8_t *use_host, int weighting, int n_reweight,
+                      int clip, const double *lo_host, const double *hi_host, const double *y, double *params, double *pcov,
+                      int8_t *status, int32_t *n_used, double *ss_res, int mem, int device, void *stream);
+PNX_API int pnx_loglinear_f32(int64_t n_vox, int n_b, const float *b_host, const uint8_t *use_host, int weighting, int n_reweight,
+                      int clip, const float *lo_host, const float *hi_host, const float *y, float *params, float *pcov,
+                      int8_t *status, int32_t *n_used, float *ss_res, int mem, int device, void *stream);
+/*
  * float32 parameter maps (io/nifti.py:279-312 reconstruct_maps): out (n_spatial, k) zero filled, then
  * out[linear_index[i], :] = (float) values[i, :] for the n_px fitted voxels (linear_index = C-order index into the
  * (X, Y, Z) grid).  values (n_px, k) float64, linear_index (n_px) int64, out float32: host|device as `mem`.

@@ -28,6 +28,7 @@ ABI_SYMBOLS = [
     "pnx_label_sums_f64", "pnx_release_staging", "pnx_queue_order_f64",
     "pnx_nnls_fit_stats_f64", "pnx_nnls_solve_peaks_stats_f64", "pnx_curvefit_predict_f64", "pnx_curvefit_fast_f32",
     "pnx_curvefit_simplex_f64", "pnx_ideal_bounds_simplex_f64", "pnx_curvefit_grid_start_f64",
+    "pnx_loglinear_f64", "pnx_loglinear_f32",
 ]
 
 
@@ -117,6 +118,11 @@ def load():
     lib.pnx_curvefit_grid_start_f64.restype = C.c_int  # opts, n_vox, b, y, n_atoms, atoms, fixed, lo, hi, project, p0_out, best, cost
     lib.pnx_curvefit_grid_start_f64.argtypes = [C.POINTER(CurvefitOpts), C.c_int64, dp, dp, C.c_int, dp, dp, dp, dp, C.c_int, dp, vp, dp,
                                                 C.c_int, C.c_int, vp]
+    lib.pnx_loglinear_f64.restype = C.c_int  # n_vox, n_b, b, use, weighting, n_reweight, clip, lo, hi, y, params, pcov, status, n_used, ss_res
+    lib.pnx_loglinear_f64.argtypes = [C.c_int64, C.c_int, dp, vp, C.c_int, C.c_int, C.c_int, dp, dp, dp, dp, dp, vp, vp, dp,
+                                      C.c_int, C.c_int, vp]
+    lib.pnx_loglinear_f32.restype = C.c_int
+    lib.pnx_loglinear_f32.argtypes = lib.pnx_loglinear_f64.argtypes  # all data pointers are void*
     lib.pnx_nnls_plan_create.restype = C.c_int
     lib.pnx_nnls_plan_create.argtypes = [C.POINTER(vp), C.c_int, C.c_int, dp, dp, C.c_int, C.c_int]
     lib.pnx_nnls_plan_destroy.restype = C.c_int

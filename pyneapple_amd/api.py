@@ -279,6 +279,69 @@ def grid_start_device(opts, n_vox, b, y, atoms, fixed, lo, hi, project_amplitude
                                              stream))
 
 
+LOGLINEAR_WEIGHTING = {"none": 0, "signal2": 1}  # w = 1 / w = y^2 (include/pnx.h)
+LOGLINEAR_MAX_REWEIGHT = 8  # kLogLinMaxReweight of csrc/pnx_loglin_args.hpp
+
+
+def _loglinear_args(b, n_b, dt, bvalue_mask, weighting, clip):
+    """The small host arguments of pnx_loglinear_f64 / _f32 in the storage type `dt`: b, the uint8 mask or None, the weighting
+    code, lo / hi (2,) or None."""
+    b = np.ascontiguousarray(b, dt)
+    if b.shape != (n_b,):
+        raise ValueError(f"b has shape {b.shape}, expected ({n_b},)")
+    use = None
+    if bvalue_mask is not None:
+        use = np.ascontiguousarray(np.asarray(bvalue_mask) != 0, np.uint8)
+        if use.shape != (n_b,):
+            raise ValueError(f"bvalue_mask has shape {use.shape}, expected ({n_b},)")
+    if weighting not in LOGLINEAR_WEIGHTING:
+        raise ValueError(f"weighting must be one of {sorted(LOGLINEAR_WEIGHTING)}, got {weighting!r}")
+    lo = hi = None
+    if clip is not None:
+        lo, hi = (np.ascontiguousarray(a, dt) for a in clip)
+        if lo.shape != (2,) or hi.shape != (2,):
+            raise ValueError("clip must be (lo, hi) with two entries each: the bounds of S0 and D")
+    return b, use, LOGLINEAR_WEIGHTING[weighting], lo, hi
+
+
+def loglinear(b, y, *, bvalue_mask=None, weighting="signal2", n_reweight=0, clip=None, want_pcov=True, device=0, out=None):
+    """Log-linear mono-exponential fit ln S = ln S0 - b D per voxel on host (numpy) arrays (pnx_loglinear_f64; method, status
+    codes and outputs: include/pnx.h).  A float32 signal selects the fp32-storage entry point (pnx_loglinear_f32: every data
+    array float32 in and out, fp64 arithmetic on the device).
+
+    bvalue_mask (n_b,) bool or None: the b-values that take part (one mask for the call); weighting "signal2" (w = y^2) or "none";
+    n_reweight 0 .. 8 further passes with w = exp(a - b D)^2; clip: None or (lo, hi), two entries each for S0 and D.
+    Returns dict(params (2, n_vox) [S0, D], pcov (n_vox, 2, 2) | None, status int8, n_used int32, ss_res).
+    `out`: optional dict of preallocated result arrays ("params", "pcov", "status", "n_used", "ss_res")."""
+    _lib.require_device()
+    dt = np.float32 if getattr(y, "dtype", None) == np.float32 else np.float64
+    y = np.ascontiguousarray(np.atleast_2d(y), dt)
+    n_vox, n_b = y.shape
+    b, use, wcode, lo, hi = _loglinear_args(b, n_b, dt, bvalue_mask, weighting, clip)
+    params = _out(out, "params", (2, n_vox), dt)
+    pcov = _out(out, "pcov", (n_vox, 2, 2), dt) if want_pcov else None
+    status = _out(out, "status", (n_vox,), np.int8)
+    n_used = _out(out, "n_used", (n_vox,), np.int32)
+    ss_res = _out(out, "ss_res", (n_vox,), dt)
+    fn = load().pnx_loglinear_f32 if dt is np.float32 else load().pnx_loglinear_f64
+    check(fn(n_vox, n_b, ptr(b), ptr(use), wcode, int(n_reweight), int(clip is not None), ptr(lo), ptr(hi), ptr(y), ptr(params),
+             ptr(pcov), ptr(status), ptr(n_used), ptr(ss_res), MEM_HOST, int(device), None))
+    return dict(params=params, pcov=pcov, status=status, n_used=n_used, ss_res=ss_res)
+
+
+def loglinear_device(b, y, params, pcov, status, n_used, ss_res, device, *, bvalue_mask=None, weighting="signal2", n_reweight=0,
+                     clip=None, stream=None):
+    """Enqueue the log-linear fit on HBM-resident torch tensors (asynchronous; caller synchronises): y (n_vox, n_b), params
+    (2, n_vox), and -- each may be None -- pcov (n_vox, 2, 2), status int8, n_used int32, ss_res (n_vox,).  float32 tensors select
+    pnx_loglinear_f32.  b, bvalue_mask and the clip bounds are host arrays, as `loglinear` takes them."""
+    f32 = "float32" in str(getattr(y, "dtype", ""))
+    n_vox, n_b = (int(s) for s in y.shape)
+    b, use, wcode, lo, hi = _loglinear_args(b, n_b, np.float32 if f32 else np.float64, bvalue_mask, weighting, clip)
+    fn = load().pnx_loglinear_f32 if f32 else load().pnx_loglinear_f64
+    check(fn(n_vox, n_b, ptr(b), ptr(use), wcode, int(n_reweight), int(clip is not None), ptr(lo), ptr(hi), ptr(y), ptr(params),
+             ptr(pcov), ptr(status), ptr(n_used), ptr(ss_res), MEM_DEVICE, int(device), stream))
+
+
 class NnlsPlan:
     """Shared part of one NNLS fit: A = [basis; reg] uploaded and reduced to its Gram form once."""
 

@@ -22,6 +22,7 @@
 #include "pnx_grid_args.hpp"
 #include "pnx_host_pipeline.hpp"
 #include "pnx_internal.hpp"
+#include "pnx_loglin.hpp"
 #include "pnx_nnls.hpp"
 #include "pnx_predict.hpp"
 #include "pnx_simplex.hpp"
@@ -1084,6 +1085,38 @@ extern "C" int pnx_curvefit_fast_f32(const pnx_curvefit_opts *o, int64_t n_vox, 
                       });
 }
 
+// ---- log-linear mono-exponential fit: pnx_loglinear_f64 / _f32 (kernel: pnx_loglin.hip, argument checks: pnx_loglin_args.hpp) ---
+// T = double or float: the storage type on both sides of the kernel, which reads and writes it directly (nothing is widened).
+template <typename T>
+static int loglinear(int64_t n_vox, int n_b, const T *b, const uint8_t *use, int weighting, int n_reweight, int clip, const T *lo,
+                     const T *hi, const T *y, T *params, T *pcov, int8_t *status, int32_t *n_used, T *ss_res, int mem, int device,
+                     void *stream) {
+    LogLinOpts o;
+    int rc = loglin_check_args<T>(n_vox, n_b, b, use, weighting, n_reweight, clip, lo, hi, y, params, mem, &o);
+    if (rc) return rc;
+    if (n_vox == 0) return PNX_OK;
+    DeviceInfo *dev;
+    if ((rc = get_device(device, &dev))) return rc;
+    PNX_HIP(hipSetDevice(device));
+    hipStream_t st = (hipStream_t)stream;
+    if (mem == PNX_MEM_DEVICE) return loglinear_device<T>(o, n_vox, y, params, pcov, status, n_used, ss_res, st);
+    enum { LL_Y, LL_P, LL_PCOV, LL_STAT, LL_NUSED, LL_SS };
+    ArrayTable A;  // the parameters are parameter-major, as popt of the curve fit
+    A.add(y, sizeof(T), (size_t)n_b, false);
+    A.add(params, sizeof(T), 2, true).pmajor = true;
+    A.add(pcov, sizeof(T), 4, true);
+    A.add(status, 1, 1, true);
+    A.add(n_used, sizeof(int32_t), 1, true);
+    A.add(ss_res, sizeof(T), 1, true);
+    HostCallGuard hg;
+    const size_t chunk = (size_t)dev_env_int("PNX_HOST_CHUNK", sizeof(T) == 4 ? 1 << 20 : 3 << 18, 1024, 1 << 26);
+    return chunk_ring(A, (size_t)n_vox, chunk, dev_env_int("PNX_HOST_SLOTS", 3, 2, 8), dev_env_int("PNX_HOST_KSTREAMS", 2, 1, 4), hg.touchers(),
+                      device, st, [&](size_t n, const DevSet &D, hipStream_t s) {
+                          return loglinear_device<T>(o, (int64_t)n, (const T *)D.dev[LL_Y], (T *)D.dev[LL_P], (T *)D.dev[LL_PCOV],
+                                                     (int8_t *)D.dev[LL_STAT], (int32_t *)D.dev[LL_NUSED], (T *)D.dev[LL_SS], s);
+                      });
+}
+
 extern "C" {
 int pnx_release_staging(int device) {
     if (device < 0 || device >= 64) return set_error(PNX_ERR_INVALID, "device %d out of range", device);
@@ -1191,6 +1224,20 @@ int pnx_curvefit_grid_start_f64(const pnx_curvefit_opts *o, int64_t n_vox, const
                       device, st, [&](size_t n, const DevSet &S, hipStream_t s) {
                           return grid_match_device(D, (int64_t)n, S.d(GS_Y), S.d(GS_P0), (int32_t *)S.dev[GS_BEST], S.d(GS_COST), dev->cus, s);
                       });
+}
+
+int pnx_loglinear_f64(int64_t n_vox, int n_b, const double *b_host, const uint8_t *use_host, int weighting, int n_reweight, int clip,
+                      const double *lo_host, const double *hi_host, const double *y, double *params, double *pcov, int8_t *status,
+                      int32_t *n_used, double *ss_res, int mem, int device, void *stream) {
+    return loglinear<double>(n_vox, n_b, b_host, use_host, weighting, n_reweight, clip, lo_host, hi_host, y, params, pcov, status, n_used,
+                             ss_res, mem, device, stream);
+}
+
+int pnx_loglinear_f32(int64_t n_vox, int n_b, const float *b_host, const uint8_t *use_host, int weighting, int n_reweight, int clip,
+                      const float *lo_host, const float *hi_host, const float *y, float *params, float *pcov, int8_t *status,
+                      int32_t *n_used, float *ss_res, int mem, int device, void *stream) {
+    return loglinear<float>(n_vox, n_b, b_host, use_host, weighting, n_reweight, clip, lo_host, hi_host, y, params, pcov, status, n_used,
+                            ss_res, mem, device, stream);
 }
 
 // ------------------------------------------------------------------------------------------- NNLS

@@ -53,14 +53,14 @@ except Exception:
             return float(np.nanmean(self.r_squared))
 
 
-def _ss_tot(signals: np.ndarray, workers: int = 8) -> np.ndarray:
+def _ss_tot(signals: np.ndarray, workers: int = 8, cols=None) -> np.ndarray:
     """sum_i (y_i - mean(y))^2 per row; row blocks on a few threads (numpy releases the GIL) -- 134 M elements for the
-    C3 volume take 0.35 s on one thread."""
+    C3 volume take 0.35 s on one thread.  cols: boolean mask over the columns that count (a fit on a b-value subset)."""
     n = signals.shape[0]
     out = np.empty(n)
 
     def block(a, e):
-        blk = signals[a:e]
+        blk = signals[a:e] if cols is None else signals[a:e][:, cols]
         d = blk - blk.mean(axis=1, keepdims=True)
         np.einsum("ij,ij->i", d, d, out=out[a:e])
 
@@ -160,9 +160,14 @@ class HipFitterBase(_FitterBase):
                                f"Call _extract_pixel_data() before predict() or get_fitted_params().")
 
     # fitters/base.py:188-274, array level ---------------------------------------------------------
-    def _assemble(self, xdata, pixels, fit_time, ss_tot=None):
+    def _assemble(self, xdata, pixels, fit_time, ss_tot=None, cols=None):
         """FitResult of the solver's current state.  `pixels` (n_px, N) are the fitted signals; `ss_tot` may be passed when
-        it was already reduced elsewhere (the device-resident IDEAL pyramid reduces it in HBM)."""
+        it was already reduced elsewhere (the device-resident IDEAL pyramid reduces it in HBM).  cols: boolean mask over the
+        measurements the solver fitted (a solver with `supports_bvalue_mask`): both sums of R^2 run over those only."""
+        if cols is not None:
+            cols = np.asarray(cols, bool)
+            if cols.all():
+                cols = None
         s = self.solver
         d = getattr(s, "diagnostics_", None) or {}
         n_px = pixels.shape[0]
@@ -173,7 +178,8 @@ class HipFitterBase(_FitterBase):
             prs = getattr(s, "pixel_results_", None)
             success = np.array([pr.success for pr in prs], dtype=bool) if prs is not None and len(prs) == n_px \
                 else np.ones(n_px, dtype=bool)
-            ss_res = np.sum((pixels - self.predict_pixels(xdata)) ** 2, axis=1)
+            diff = pixels - self.predict_pixels(xdata)
+            ss_res = np.sum((diff if cols is None else diff[:, cols]) ** 2, axis=1)
             pc = d.get("pcov")
             covariance = None if pc is None else np.asarray(pc).reshape(n_px, *np.asarray(pc).shape[-2:])
             res = d.get("residual")
@@ -194,10 +200,15 @@ class HipFitterBase(_FitterBase):
         else:
             status = np.asarray(d["status"])
             success = status > 0
-            ss_res = 2.0 * np.atleast_1d(d["cost"]).astype(np.float64)  # cost = 0.5 * sum(res^2) at the returned x
+            if "cost" in d:
+                ss_res = 2.0 * np.atleast_1d(d["cost"]).astype(np.float64)  # cost = 0.5 * sum(res^2) at the returned x
+            else:  # a solver that reports the signal-domain residual itself (HipLogLinearSolver)
+                ss_res = np.atleast_1d(d["ss_res"]).astype(np.float64)
             bad = ~success
+            xfit = xdata if cols is None else xdata[cols]
             if bad.any() and self.device_stats:  # failed voxels return p0: the predict kernel's residual there
-                ss_res[bad] = self._curvefit_predict(xdata, np.nonzero(bad)[0], y=pixels[bad], want_pred=False)["ss_res"]
+                ybad = pixels[bad] if cols is None else np.ascontiguousarray(pixels[bad][:, cols])
+                ss_res[bad] = self._curvefit_predict(xfit, np.nonzero(bad)[0], y=ybad, want_pred=False)["ss_res"]
             elif bad.any():  # failed voxels return p0: evaluate the model there (a handful of voxels)
                 names = list(self.fitted_params_.keys())
                 arr = np.stack([np.atleast_1d(self.fitted_params_[n]) for n in names])[:, bad]
@@ -208,12 +219,14 @@ class HipFitterBase(_FitterBase):
                     vals.update(fixed)
                     vals.update({n: np.asarray(v)[i] for n, v in (self._pixel_fixed or {}).items()})
                     try:
-                        pred = s.model.forward(xdata, *[vals[n] for n in all_names])
-                        ss_res[i] = np.sum((pixels[i] - pred) ** 2)
+                        pred = s.model.forward(xfit, *[vals[n] for n in all_names])
+                        ss_res[i] = np.sum(((pixels[i] if cols is None else pixels[i][cols]) - pred) ** 2)
                     except Exception:
                         ss_res[i] = np.nan
             covariance = np.asarray(d["pcov"]).reshape(n_px, *np.asarray(d["pcov"]).shape[-2:])
             residuals = None
+        if ss_tot is None and cols is not None:
+            ss_tot = _ss_tot(pixels, cols=cols)
         msgs = None
         if not success.all() and getattr(s, "pixel_results_", None) is not None and len(s.pixel_results_) == n_px:
             view = s.pixel_results_
@@ -381,5 +394,7 @@ class HipPixelWiseFitter(HipFitterBase):
         else:
             self.solver.fit(xdata, pixels, **fit_kwargs)
         self.fitted_params_ = dict(self.solver.params_)
-        self.results_ = self._assemble(xdata, pixels, time.perf_counter() - t0)
+        # a solver that fits a b-value subset of the whole rows (bvalue_mask): R^2 over that subset
+        cols = fit_kwargs.get("bvalue_mask") if getattr(self.solver, "supports_bvalue_mask", False) else None
+        self.results_ = self._assemble(xdata, pixels, time.perf_counter() - t0, cols=cols)
         return self

@@ -82,7 +82,11 @@ class HipSegmentedFitter(HipFitterBase):
         self.image_shape = image.shape
         # step 1: the simple model on the b-value subset
         one = HipPixelWiseFitter(self.step1_solver)
-        one.fit(xdata[keep], image if keep.all() else image[..., keep], segmentation, **fit_kwargs)
+        if getattr(self.step1_solver, "supports_bvalue_mask", False):
+            # the solver reads the subset out of the whole rows on the device: no strided host copy of the image
+            one.fit(xdata, image, segmentation, bvalue_mask=keep, **fit_kwargs)
+        else:
+            one.fit(xdata[keep], image if keep.all() else image[..., keep], segmentation, **fit_kwargs)
         self.step1_params_ = dict(one.get_fitted_params())
         self.step1_result_ = one.results_
         # step 2: same mask, same voxel order -> the step-1 columns ARE the per-voxel fixed columns.  The pixel-wise fitter

@@ -8,8 +8,11 @@ constructor arguments, same `fit()` signature, same fitted state (`params_`, `di
 `HipConstrainedCurveFitSolver` mirrors `ConstrainedCurveFitSolver` (solvers/constrained_curvefit.py) in its constructor and
 its constraint sum(f_i) <= 1, not in its algorithm (pnx_curvefit_simplex_f64).
 
+`HipLogLinearSolver` has no counterpart in the reference: the linearised mono-exponential fit as a closed form
+(pnx_loglinear_f64), with the reference's solver contract.
+
 Registered under the `pyneapple.solvers` entry-point group (pyproject.toml) as `hip_curvefit` / `hip_nnls` /
-`hip_constrained_curvefit`;
+`hip_constrained_curvefit` / `hip_loglinear`;
 extra scalar keys of `[Fitting.solver]` arrive as keyword arguments (io/toml.py:328-338): `device`,
 `n_gpus`, `jacobian`.
 """
@@ -528,6 +531,88 @@ class HipConstrainedCurveFitSolver(HipCurveFitSolver):
         super()._pack(res, n_pixels, free_names)
         for key in self._extra_outputs:
             self.diagnostics_[key] = res[key]
+
+
+_LOGLINEAR_MESSAGES = {0: "Fewer than two usable (positive) samples at distinct b-values: no line to fit.",
+                       -2: "array must not contain infs or NaNs"}
+
+
+class HipLogLinearSolver(RefBaseSolver):
+    """Linearised mono-exponential fit ln S = ln S0 - b D by (weighted) linear least squares per voxel (pnx_loglinear_f64,
+    include/pnx.h): the ADC map, step 1 of a segmented IVIM fit, a cheap source of S0 / D start values.  Registered as
+    `hip_loglinear`.
+
+    model: the plain mono-exponential layout ([S0, D], nothing fixed, no T1 / STEAM factor).  `max_iter` and `tol` are accepted
+    because the TOML loader always passes them; a closed form has no use for either.  Keyword arguments:
+        p0: None or {"S0": .., "D": ..}: what a voxel that could not be fitted (status <= 0) reports as its parameters, the
+            reference's failure convention (NaN without p0).
+        bounds: None or {"S0": (lo, hi), "D": (lo, hi)}; read only with clip=True.
+        weighting: "signal2" (default, w = y^2: the usual weights of log-transformed data) or "none".
+        n_reweight: 0 .. 8 further passes with the weights of the estimate before (iteratively re-weighted LLS).
+        clip: clip S0 and D into `bounds` after the fit (status 2 for a voxel that was moved).
+        device, io_dtype ("float32": float32 arrays across the ABI, fp64 arithmetic) as HipCurveFitSolver's.
+    Any other keyword (the reference's solver arguments: method, multi_threading, ...) is accepted and ignored.
+    fit(xdata, ydata, bvalue_mask=None): `bvalue_mask` (n_b,) bool restricts the fit to a subset of the b-values without slicing
+    the signal array.  After fit: params_ {"S0", "D"}, diagnostics_ {"pcov", "n_pixels", "status", "n_used", "ss_res"} (ss_res in
+    the signal domain over the masked-in samples), pixel_results_."""
+
+    supports_bvalue_mask = True
+
+    def __init__(self, model: Any, max_iter: int = 250, tol: float = 1e-8, p0: dict[str, float] | None = None,
+                 bounds: dict[str, tuple[float, float]] | None = None, weighting: str = "signal2", n_reweight: int = 0,
+                 clip: bool = False, device: int = 0, io_dtype: str = "float64", **ignored_reference_kwargs):
+        RefBaseSolver.__init__(self, model=model, max_iter=max_iter, tol=tol, verbose=bool(ignored_reference_kwargs.pop("verbose", False)))
+        names = list(getattr(model, "_all_param_names", []))
+        if names != ["S0", "D"] or getattr(model, "fixed_params", None) or kernel_t1(model)["t1_mode"]:
+            raise ValueError(f"HipLogLinearSolver fits the plain mono-exponential model [S0, D] (nothing fixed, no T1 / STEAM factor), "
+                             f"not {type(model).__name__} with parameters {names} and fixed {dict(getattr(model, 'fixed_params', None) or {})}")
+        if weighting not in api.LOGLINEAR_WEIGHTING:
+            raise ValueError(f"weighting must be one of {sorted(api.LOGLINEAR_WEIGHTING)}, got {weighting!r}")
+        if not 0 <= int(n_reweight) <= api.LOGLINEAR_MAX_REWEIGHT:
+            raise ValueError(f"n_reweight must lie in 0 .. {api.LOGLINEAR_MAX_REWEIGHT}, got {n_reweight}")
+        for name, d in (("p0", p0), ("bounds", bounds)):
+            if d is not None:
+                _validate_parameter_names(d, names)
+        if clip and bounds is None:
+            raise ValueError("clip=True needs bounds: {'S0': (lo, hi), 'D': (lo, hi)}")
+        self.p0 = p0
+        self.bounds = bounds
+        self.weighting = weighting
+        self.n_reweight = int(n_reweight)
+        self.clip = bool(clip)
+        self.device = int(device)
+        self.io_dtype = _io_dtype(io_dtype)
+        self.solver_kwargs = ignored_reference_kwargs
+
+    def fit(self, xdata: np.ndarray, ydata: np.ndarray, bvalue_mask=None, pixel_fixed_params=None, **fit_kwargs) -> "HipLogLinearSolver":
+        if pixel_fixed_params:
+            raise ValueError("HipLogLinearSolver fits both parameters of the line: pixel_fixed_params cannot be honoured")
+        self._reset_state()
+        xdata = np.asarray(xdata)
+        ydata = np.asarray(ydata)
+        _validate_data_shapes(xdata, ydata)
+        if ydata.ndim == 1:
+            ydata = ydata[np.newaxis, :]
+        if ydata.ndim > 2:
+            raise ValueError(f"ydata must be 1D or 2D array, but got shape {ydata.shape}.")
+        n_pixels = ydata.shape[0]
+        clip = None
+        if self.clip:
+            clip = ([self.bounds["S0"][0], self.bounds["D"][0]], [self.bounds["S0"][1], self.bounds["D"][1]])
+        res = api.loglinear(xdata, np.ascontiguousarray(ydata, self.io_dtype), bvalue_mask=bvalue_mask, weighting=self.weighting,
+                            n_reweight=self.n_reweight, clip=clip, device=self.device)
+        params, pcov, status = res["params"], res["pcov"], res["status"]
+        success = status > 0
+        if self.p0 is not None and not success.all():  # the reference's failure convention: p0, NaN covariance (already NaN)
+            params[0, ~success] = float(self.p0["S0"])
+            params[1, ~success] = float(self.p0["D"])
+        self.pixel_results_ = PixelResultsView(
+            params.T, pcov, success,
+            lambda i, st=status: None if st[i] > 0 else _LOGLINEAR_MESSAGES.get(int(st[i]), "fit failed"))
+        self.params_ = {name: [float(params[i, 0])] if n_pixels == 1 else params[i] for i, name in enumerate(("S0", "D"))}
+        self.diagnostics_ = {"pcov": pcov[0] if n_pixels == 1 else pcov, "n_pixels": n_pixels, "status": status,
+                             "n_used": res["n_used"], "ss_res": res["ss_res"]}
+        return self
 
 
 class HipNNLSSolver(NNLSBase):
