@@ -450,6 +450,50 @@ PNX_API int pnx_loglinear_f32(int64_t n_vox, int n_b, const float *b_host, const
                       int clip, const float *lo_host, const float *hi_host, const float *y, float *params, float *pcov,
                       int8_t *status, int32_t *n_used, float *ss_res, int mem, int device, void *stream);
 /*
+ * Exponential peeling ("curve stripping", the fully segmented IVIM estimate) of the mono-, bi- and tri-exponential layouts
+ * (DESIGN.md 4.1f): the slowest compartment is fitted log-linearly on the high b-values and subtracted, the next faster one is
+ * fitted on what is left of the lower b-values, and once more for a third.  A closed form: the clinical estimator where a
+ * non-linear fit is too noisy, and a per-voxel start value for the non-linear fit.  K = the number of exponentials of `model`
+ * (1 for PNX_MODEL_MONO, 2 for the bi-, 3 for the tri-exponential layouts; all seven are served).  No T1 / STEAM factor, nothing
+ * fixed.  Per voxel, in fp64, in the order written:
+ *   use: a (K, n_b) 0/1 mask.  Row k is the set of b-values of stage k; stage 0 is the SLOWEST compartment and is fitted first.
+ *     M = the union of the rows.  A non-finite y_i with i in M: status -2, every output NaN (n_used 0); the voxel's neighbours
+ *     are not affected.  A non-finite sample outside M is ignored.
+ *   r(0) = y.  For k = 0 .. K-1:
+ *     U_k = { i : use[k][i] and r(k)_i > 0 }, n_used[k] = |U_k|: a non-positive residual is left out, not clamped.
+ *     l_i = log r(k)_i;  w_i = 1 (weighting 0) or (r(k)_i)^2 (weighting 1).
+ *     The centred weighted line of pnx_loglinear_f64 over U_k: bm = sum w b / sum w;  lm = sum w l / sum w;
+ *     Sbb = sum w (b - bm)^2;  D_k = -sum w (b - bm)(l - lm) / Sbb;  a_k = lm + D_k bm;  A_k = exp(a_k).
+ *     The stage fails when n_used[k] < 2, Sbb == 0, or any of a_k, D_k, A_k is non-finite: status 0, parameters and ss_res NaN,
+ *     n_used of the stages not reached 0.
+ *     Otherwise r(k+1)_i = r(k)_i - A_k exp(-b_i D_k) for EVERY i.
+ *   Stage k is component K - k of the layout (component 1 is the fastest).  With S = sum A_k:
+ *     mono [S0, D]: [A_0, D_0];  bi reduced [f1, D1, D2]: [A_1 / S, D_1, D_0];  bi S0: the reduced layout, then S;
+ *     bi full [f1, D1, f2, D2]: [A_1, D_1, A_0, D_0] (amplitudes);  tri reduced [f1, D1, f2, D2, D3]:
+ *     [A_2 / S, D_2, A_1 / S, D_1, D_0];  tri S0: the reduced layout, then S;  tri full: [A_2, D_2, A_1, D_1, A_0, D_0].
+ *   clip != 0: every parameter is clipped into [lo[j], hi[j]] after the mapping (comparisons that keep a NaN, as
+ *     pnx_loglinear_f64); a voxel that was moved gets status 2, a complete voxel that was not moved status 1.
+ *   fallback (n_params,) or NULL: when given, a voxel with status 0 or -2 returns this vector instead of NaN (its ss_res stays
+ *     NaN), which makes `params` usable as a device-resident per-voxel p0 of pnx_curvefit_batch_f64.
+ *   ss_res = sum over i in M of (model(b_i; returned parameters) - y_i)^2: the SIGNAL-domain residual at the returned (clipped)
+ *     point over every masked-in sample, so that R^2 follows from pnx_row_ss_tot_f64 as for the other solvers.
+ *   No covariance and no re-weighting passes: peeling has no honest closed-form covariance, so none is invented.
+ *   b (n_b,) host; use (K, n_b) uint8 host; lo, hi (n_params,) host when clip (not read otherwise); fallback (n_params,) host or
+ *   NULL; y (n_vox, n_b) in; params (n_params, n_vox) parameter-major; status (n_vox) int8 or NULL; n_used (K, n_vox) int32 or
+ *   NULL; ss_res (n_vox) or NULL: host|device as `mem`.
+ * pnx_peel_f32: fp32 storage of b, lo, hi, fallback, y, params and ss_res, the same fp64 arithmetic.
+ * PNX_MEM_DEVICE only enqueues; PNX_MEM_HOST goes through the chunk ring.  PNX_ERR_INVALID with a message that names the
+ * argument, before any device work: an unknown model, n_b outside 2K .. PNX_MAX_BVALUES, a NULL b / use / y / params, a
+ * non-finite b, weighting not 0 / 1, a mask row with fewer than 2 b-values or fewer than 2 distinct ones, clip with NULL bounds
+ * or lo >= hi, mem not host / device.
+ */
+PNX_API int pnx_peel_f64(int model, int64_t n_vox, int n_b, const double *b_host, const uint8_t *use_host, int weighting, int clip,
+                 const double *lo_host, const double *hi_host, const double *fallback_host, const double *y, double *params,
+                 int8_t *status, int32_t *n_used, double *ss_res, int mem, int device, void *stream);
+PNX_API int pnx_peel_f32(int model, int64_t n_vox, int n_b, const float *b_host, const uint8_t *use_host, int weighting, int clip,
+                 const float *lo_host, const float *hi_host, const float *fallback_host, const float *y, float *params, int8_t *status,
+                 int32_t *n_used, float *ss_res, int mem, int device, void *stream);
+/*
  * float32 parameter maps (io/nifti.py:279-312 reconstruct_maps): out (n_spatial, k) zero filled, then
  * out[linear_index[i], :] = (float) values[i, :] for the n_px fitted voxels (linear_index = C-order index into the
  * (X, Y, Z) grid).  values (n_px, k) float64, linear_index (n_px) int64, out float32: host|device as `mem`.

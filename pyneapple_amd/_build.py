@@ -36,6 +36,7 @@ SOURCE_GROUPS = {
     "simplex": ["pnx_simplex.hip", "pnx_simplex.hpp"],
     "grid": ["pnx_grid.hip", "pnx_grid.hpp", "pnx_grid_args.hpp"],
     "loglin": ["pnx_loglin.hip", "pnx_loglin.hpp", "pnx_loglin_args.hpp"],
+    "peel": ["pnx_peel.hip", "pnx_peel.hpp", "pnx_peel_args.hpp"],
     # the host boundary (streamed path, chunk ring, deferred NNLS hand-over, peak tables): host-mode / PCIe-inclusive figures and
     # the host-path fuzz summaries are stamped with this id, so that they are not replayed as current after pnx_api.hip changes
     # (round 4: the orchestration of both host paths moved into pnx_host_pipeline.hpp; the peak analysis the rings call is pnx_spectrum.hip)
@@ -64,7 +65,7 @@ def _units():
              ("pnx_sweep.o", "pnx_sweep.hip", []), ("pnx_spectrum.o", "pnx_spectrum.hip", []),
              ("pnx_resize.o", "pnx_resize.hip", []), ("pnx_predict.o", "pnx_predict.hip", []),
              ("pnx_simplex.o", "pnx_simplex.hip", []), ("pnx_grid.o", "pnx_grid.hip", []),
-             ("pnx_loglin.o", "pnx_loglin.hip", []),
+             ("pnx_loglin.o", "pnx_loglin.hip", []), ("pnx_peel.o", "pnx_peel.hip", []),
              ("pnx_curvefit_f32.o", "pnx_curvefit_f32.hip", CURVEFIT_FLAGS)]
     for m in range(N_MODELS):
         units.append((f"pnx_curvefit_m{m}.o", "pnx_curvefit_inst.hip", [f"-DPNX_MODEL={m}", *CURVEFIT_FLAGS]))
@@ -110,6 +111,8 @@ def _stale(unit, force: bool) -> bool:
         deps = [d for d in deps if "pnx_grid" not in os.path.basename(d)]  # the dictionary search's headers: its unit and the ABI's
     if src not in ("pnx_api.hip", "pnx_loglin.hip"):
         deps = [d for d in deps if "pnx_loglin" not in os.path.basename(d)]  # the log-linear fit's headers: likewise
+    if src not in ("pnx_api.hip", "pnx_peel.hip"):
+        deps = [d for d in deps if "pnx_peel" not in os.path.basename(d)]  # the peeling fit's headers: likewise
     return max(os.path.getmtime(d) for d in deps) > os.path.getmtime(o)
 
 

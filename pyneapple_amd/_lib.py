@@ -28,7 +28,7 @@ ABI_SYMBOLS = [
     "pnx_label_sums_f64", "pnx_release_staging", "pnx_queue_order_f64",
     "pnx_nnls_fit_stats_f64", "pnx_nnls_solve_peaks_stats_f64", "pnx_curvefit_predict_f64", "pnx_curvefit_fast_f32",
     "pnx_curvefit_simplex_f64", "pnx_ideal_bounds_simplex_f64", "pnx_curvefit_grid_start_f64",
-    "pnx_loglinear_f64", "pnx_loglinear_f32",
+    "pnx_loglinear_f64", "pnx_loglinear_f32", "pnx_peel_f64", "pnx_peel_f32",
 ]
 
 
@@ -123,6 +123,11 @@ def load():
                                       C.c_int, C.c_int, vp]
     lib.pnx_loglinear_f32.restype = C.c_int
     lib.pnx_loglinear_f32.argtypes = lib.pnx_loglinear_f64.argtypes  # all data pointers are void*
+    lib.pnx_peel_f64.restype = C.c_int  # model, n_vox, n_b, b, use, weighting, clip, lo, hi, fallback, y, params, status, n_used, ss_res
+    lib.pnx_peel_f64.argtypes = [C.c_int, C.c_int64, C.c_int, dp, vp, C.c_int, C.c_int, dp, dp, dp, dp, dp, vp, vp, dp,
+                                 C.c_int, C.c_int, vp]
+    lib.pnx_peel_f32.restype = C.c_int
+    lib.pnx_peel_f32.argtypes = lib.pnx_peel_f64.argtypes  # all data pointers are void*
     lib.pnx_nnls_plan_create.restype = C.c_int
     lib.pnx_nnls_plan_create.argtypes = [C.POINTER(vp), C.c_int, C.c_int, dp, dp, C.c_int, C.c_int]
     lib.pnx_nnls_plan_destroy.restype = C.c_int

@@ -342,6 +342,90 @@ def loglinear_device(b, y, params, pcov, status, n_used, ss_res, device, *, bval
              ptr(pcov), ptr(status), ptr(n_used), ptr(ss_res), MEM_DEVICE, int(device), stream))
 
 
+PEEL_STAGES = {"mono": 1, "bi_reduced": 2, "bi_s0": 2, "bi_full": 2, "tri_reduced": 3, "tri_s0": 3, "tri_full": 3}  # exponentials
+
+
+def peel_masks(b, model, b_thresholds):
+    """The (K, n_b) uint8 stage masks of `peel` from K - 1 ascending thresholds [t_1 < ... < t_{K-1}]: stage 0 (the slowest
+    compartment, fitted first) takes b >= t_{K-1}, a middle stage k (K = 3 only) t_{K-1-k} <= b < t_{K-k}, the last stage
+    b < t_1.  K = 1: every b-value."""
+    K = PEEL_STAGES[model]
+    b = np.asarray(b, float)
+    t = np.atleast_1d(np.asarray([] if b_thresholds is None else b_thresholds, float))
+    if t.shape != (K - 1,) or not (np.diff(t) > 0).all() or not np.isfinite(t).all():
+        raise ValueError(f"b_thresholds must hold {K - 1} ascending values for {model!r}, got {b_thresholds!r}")
+    edges = np.concatenate([[-np.inf], t, [np.inf]])  # stage k: edges[K-1-k] <= b < edges[K-k]
+    return np.ascontiguousarray(np.stack([(b >= edges[K - 1 - k]) & (b < edges[K - k]) for k in range(K)]), np.uint8)
+
+
+def _peel_args(b, n_b, dt, model, masks, b_thresholds, weighting, clip, fallback):
+    """The small host arguments of pnx_peel_f64 / _f32 in the storage type `dt`: b, the (K, n_b) uint8 masks, the weighting code,
+    lo / hi (n_params,) or None, fallback (n_params,) or None."""
+    if model not in PEEL_STAGES:
+        raise ValueError(f"model must be one of {sorted(PEEL_STAGES)}, got {model!r}")
+    K, n = PEEL_STAGES[model], len(MODEL_PARAM_NAMES[model])
+    b = np.ascontiguousarray(b, dt)
+    if b.shape != (n_b,):
+        raise ValueError(f"b has shape {b.shape}, expected ({n_b},)")
+    if (masks is None) == (b_thresholds is None) and not (K == 1 and masks is None):
+        raise ValueError("peel takes either masks (K, n_b) or b_thresholds (K - 1 ascending values)")
+    if masks is None:
+        use = peel_masks(b, model, b_thresholds)
+    else:
+        use = np.ascontiguousarray(np.atleast_2d(np.asarray(masks)) != 0, np.uint8)
+        if use.shape != (K, n_b):
+            raise ValueError(f"masks has shape {use.shape}, expected ({K}, {n_b})")
+    if weighting not in LOGLINEAR_WEIGHTING:
+        raise ValueError(f"weighting must be one of {sorted(LOGLINEAR_WEIGHTING)}, got {weighting!r}")
+    lo = hi = None
+    if clip is not None:
+        lo, hi = (np.ascontiguousarray(a, dt) for a in clip)
+        if lo.shape != (n,) or hi.shape != (n,):
+            raise ValueError(f"clip must be (lo, hi) with {n} entries each: the bounds of {MODEL_PARAM_NAMES[model]}")
+    if fallback is not None:
+        fallback = np.ascontiguousarray(fallback, dt)
+        if fallback.shape != (n,):
+            raise ValueError(f"fallback must have {n} entries: {MODEL_PARAM_NAMES[model]}")
+    return b, use, LOGLINEAR_WEIGHTING[weighting], lo, hi, fallback
+
+
+def peel(b, y, model, *, masks=None, b_thresholds=None, weighting="signal2", clip=None, fallback=None, device=0, out=None):
+    """Exponential peeling of a mono-, bi- or tri-exponential layout per voxel on host (numpy) arrays (pnx_peel_f64; method, status
+    codes and outputs: include/pnx.h).  A float32 signal selects the fp32-storage entry point (pnx_peel_f32).
+
+    model: a key of MODEL_IDS; masks (K, n_b) 0/1, row k the b-values of stage k (stage 0 = the slowest compartment), or
+    b_thresholds, K - 1 ascending values (`peel_masks`); weighting "signal2" (w = r^2) or "none"; clip: None or (lo, hi) with one
+    entry per parameter; fallback: None or the vector a voxel that could not be fitted returns instead of NaN.
+    Returns dict(params (n_params, n_vox), status int8, n_used (K, n_vox) int32, ss_res).
+    `out`: optional dict of preallocated result arrays ("params", "status", "n_used", "ss_res")."""
+    _lib.require_device()
+    dt = np.float32 if getattr(y, "dtype", None) == np.float32 else np.float64
+    y = np.ascontiguousarray(np.atleast_2d(y), dt)
+    n_vox, n_b = y.shape
+    b, use, wcode, lo, hi, fb = _peel_args(b, n_b, dt, model, masks, b_thresholds, weighting, clip, fallback)
+    params = _out(out, "params", (len(MODEL_PARAM_NAMES[model]), n_vox), dt)
+    status = _out(out, "status", (n_vox,), np.int8)
+    n_used = _out(out, "n_used", (PEEL_STAGES[model], n_vox), np.int32)
+    ss_res = _out(out, "ss_res", (n_vox,), dt)
+    fn = load().pnx_peel_f32 if dt is np.float32 else load().pnx_peel_f64
+    check(fn(MODEL_IDS[model], n_vox, n_b, ptr(b), ptr(use), wcode, int(clip is not None), ptr(lo), ptr(hi), ptr(fb), ptr(y), ptr(params),
+             ptr(status), ptr(n_used), ptr(ss_res), MEM_HOST, int(device), None))
+    return dict(params=params, status=status, n_used=n_used, ss_res=ss_res)
+
+
+def peel_device(b, y, model, params, status, n_used, ss_res, device, *, masks=None, b_thresholds=None, weighting="signal2", clip=None,
+                fallback=None, stream=None):
+    """Enqueue the peeling fit on HBM-resident torch tensors (asynchronous; caller synchronises): y (n_vox, n_b), params
+    (n_params, n_vox), and -- each may be None -- status int8, n_used (K, n_vox) int32, ss_res (n_vox,).  float32 tensors select
+    pnx_peel_f32.  b, the masks or thresholds, the clip bounds and the fallback are host arrays, as `peel` takes them."""
+    f32 = "float32" in str(getattr(y, "dtype", ""))
+    n_vox, n_b = (int(s) for s in y.shape)
+    b, use, wcode, lo, hi, fb = _peel_args(b, n_b, np.float32 if f32 else np.float64, model, masks, b_thresholds, weighting, clip, fallback)
+    fn = load().pnx_peel_f32 if f32 else load().pnx_peel_f64
+    check(fn(MODEL_IDS[model], n_vox, n_b, ptr(b), ptr(use), wcode, int(clip is not None), ptr(lo), ptr(hi), ptr(fb), ptr(y), ptr(params),
+             ptr(status), ptr(n_used), ptr(ss_res), MEM_DEVICE, int(device), stream))
+
+
 class NnlsPlan:
     """Shared part of one NNLS fit: A = [basis; reg] uploaded and reduced to its Gram form once."""
 

@@ -24,6 +24,7 @@
 #include "pnx_internal.hpp"
 #include "pnx_loglin.hpp"
 #include "pnx_nnls.hpp"
+#include "pnx_peel.hpp"
 #include "pnx_predict.hpp"
 #include "pnx_simplex.hpp"
 
@@ -1117,6 +1118,36 @@ static int loglinear(int64_t n_vox, int n_b, const T *b, const uint8_t *use, int
                       });
 }
 
+// ---- exponential peeling: pnx_peel_f64 / _f32 (kernel: pnx_peel.hip, argument checks: pnx_peel_args.hpp) -----------------------
+// T = double or float: the storage type on both sides of the kernel, which reads and writes it directly (nothing is widened).
+template <typename T>
+static int peel(int model, int64_t n_vox, int n_b, const T *b, const uint8_t *use, int weighting, int clip, const T *lo, const T *hi,
+                const T *fallback, const T *y, T *params, int8_t *status, int32_t *n_used, T *ss_res, int mem, int device, void *stream) {
+    PeelOpts o;
+    int rc = peel_check_args<T>(model, n_vox, n_b, b, use, weighting, clip, lo, hi, fallback, y, params, mem, &o);
+    if (rc) return rc;
+    if (n_vox == 0) return PNX_OK;
+    DeviceInfo *dev;
+    if ((rc = get_device(device, &dev))) return rc;
+    PNX_HIP(hipSetDevice(device));
+    hipStream_t st = (hipStream_t)stream;
+    if (mem == PNX_MEM_DEVICE) return peel_device<T>(o, n_vox, y, params, status, n_used, ss_res, st);
+    enum { PL_Y, PL_P, PL_STAT, PL_NUSED, PL_SS };
+    ArrayTable A;  // the parameters and n_used are parameter-major, as popt of the curve fit
+    A.add(y, sizeof(T), (size_t)n_b, false);
+    A.add(params, sizeof(T), (size_t)o.n_params, true).pmajor = true;
+    A.add(status, 1, 1, true);
+    A.add(n_used, sizeof(int32_t), (size_t)o.n_stage, true).pmajor = true;
+    A.add(ss_res, sizeof(T), 1, true);
+    HostCallGuard hg;
+    const size_t chunk = (size_t)dev_env_int("PNX_HOST_CHUNK", sizeof(T) == 4 ? 1 << 20 : 3 << 18, 1024, 1 << 26);
+    return chunk_ring(A, (size_t)n_vox, chunk, dev_env_int("PNX_HOST_SLOTS", 3, 2, 8), dev_env_int("PNX_HOST_KSTREAMS", 2, 1, 4), hg.touchers(),
+                      device, st, [&](size_t n, const DevSet &D, hipStream_t s) {
+                          return peel_device<T>(o, (int64_t)n, (const T *)D.dev[PL_Y], (T *)D.dev[PL_P], (int8_t *)D.dev[PL_STAT],
+                                                (int32_t *)D.dev[PL_NUSED], (T *)D.dev[PL_SS], s);
+                      });
+}
+
 extern "C" {
 int pnx_release_staging(int device) {
     if (device < 0 || device >= 64) return set_error(PNX_ERR_INVALID, "device %d out of range", device);
@@ -1238,6 +1269,20 @@ int pnx_loglinear_f32(int64_t n_vox, int n_b, const float *b_host, const uint8_t
                       int32_t *n_used, float *ss_res, int mem, int device, void *stream) {
     return loglinear<float>(n_vox, n_b, b_host, use_host, weighting, n_reweight, clip, lo_host, hi_host, y, params, pcov, status, n_used,
                             ss_res, mem, device, stream);
+}
+
+int pnx_peel_f64(int model, int64_t n_vox, int n_b, const double *b_host, const uint8_t *use_host, int weighting, int clip,
+                 const double *lo_host, const double *hi_host, const double *fallback_host, const double *y, double *params,
+                 int8_t *status, int32_t *n_used, double *ss_res, int mem, int device, void *stream) {
+    return peel<double>(model, n_vox, n_b, b_host, use_host, weighting, clip, lo_host, hi_host, fallback_host, y, params, status, n_used,
+                        ss_res, mem, device, stream);
+}
+
+int pnx_peel_f32(int model, int64_t n_vox, int n_b, const float *b_host, const uint8_t *use_host, int weighting, int clip,
+                 const float *lo_host, const float *hi_host, const float *fallback_host, const float *y, float *params, int8_t *status,
+                 int32_t *n_used, float *ss_res, int mem, int device, void *stream) {
+    return peel<float>(model, n_vox, n_b, b_host, use_host, weighting, clip, lo_host, hi_host, fallback_host, y, params, status, n_used,
+                       ss_res, mem, device, stream);
 }
 
 // ------------------------------------------------------------------------------------------- NNLS

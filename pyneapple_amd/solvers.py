@@ -9,10 +9,11 @@ constructor arguments, same `fit()` signature, same fitted state (`params_`, `di
 its constraint sum(f_i) <= 1, not in its algorithm (pnx_curvefit_simplex_f64).
 
 `HipLogLinearSolver` has no counterpart in the reference: the linearised mono-exponential fit as a closed form
-(pnx_loglinear_f64), with the reference's solver contract.
+(pnx_loglinear_f64), with the reference's solver contract.  `HipPeelSolver` likewise: exponential peeling of the bi- and
+tri-exponential models (pnx_peel_f64).
 
 Registered under the `pyneapple.solvers` entry-point group (pyproject.toml) as `hip_curvefit` / `hip_nnls` /
-`hip_constrained_curvefit` / `hip_loglinear`;
+`hip_constrained_curvefit` / `hip_loglinear` / `hip_peel`;
 extra scalar keys of `[Fitting.solver]` arrive as keyword arguments (io/toml.py:328-338): `device`,
 `n_gpus`, `jacobian`.
 """
@@ -133,6 +134,11 @@ class HipCurveFitSolver(CurveFitBase):
             own (pnx_curvefit_grid_start_f64) unless `fit()` is given an explicit `p0`; `diagnostics_` gains "p0_atom" (int32
             index of the atom, -1 for a non-finite signal) and "p0_cost".  At most 4096 atoms, every value inside `bounds`.
             Not built with it, hence a ValueError: precision / io_dtype "float32", per-pixel fixed parameters, per-voxel bounds.
+        p0_peel: None (default) or {"b_thresholds": [...], "weighting": "signal2"}: every voxel of
+            `fit()` starts from its exponential-peeling estimate (pnx_peel_f64, api.peel_masks for the thresholds), clipped into
+            `bounds`; a voxel the peel could not fit starts from `p0`.  `diagnostics_` gains "p0_status" (the peel's int8 status).
+            Not built with it, hence a ValueError: together with p0_grid, an explicit per-voxel p0, fixed parameters (model or per
+            pixel), a T1 / STEAM model, per-voxel bounds, precision / io_dtype "float32", HipConstrainedCurveFitSolver.
         p0_grid_project: fit the amplitude S0 per voxel and atom, clipped to its bounds, instead of taking it from the atoms
             (so S0 needs no entry in p0_grid).  Default: True exactly when the model has a free S0.
     """
@@ -159,6 +165,7 @@ class HipCurveFitSolver(CurveFitBase):
         # honour it, so it is refused instead of being dropped silently (keys at their SciPy default are accepted).
         p0_grid = solver_kwargs.pop("p0_grid", None)
         p0_grid_project = solver_kwargs.pop("p0_grid_project", None)
+        p0_peel = solver_kwargs.pop("p0_peel", None)
         self.xtol = float(solver_kwargs.pop("xtol", 1e-8))
         self.gtol = float(solver_kwargs.pop("gtol", 1e-8))
         # sigma / absolute_sigma: the two curve_fit arguments the reference's docstring names (curvefit.py:33).  A scalar or 1-D
@@ -184,7 +191,7 @@ class HipCurveFitSolver(CurveFitBase):
         if unknown:
             raise ValueError(f"HipCurveFitSolver got solver arguments it cannot honour: {sorted(unknown)} "
                              "(supported: sigma, absolute_sigma, xtol, gtol, jacobian, device, n_gpus, io_dtype, precision, p0_grid, "
-                             "p0_grid_project, n_pools)")
+                             "p0_grid_project, p0_peel, n_pools)")
         if method != "trf":
             raise ValueError(f"HipCurveFitSolver implements method='trf' only (got {method!r}); "
                              "use the reference CurveFitSolver for 'dogbox' / 'lm'.")
@@ -219,6 +226,7 @@ class HipCurveFitSolver(CurveFitBase):
             if getattr(model, "fixed_params", None):
                 raise ValueError("precision='float32' is not built with fixed parameters; use precision='float64'")
         self._set_p0_grid(p0_grid, p0_grid_project)
+        self._set_p0_peel(p0_peel)
 
     # ------------------------------------------------------------------ p0_grid: the atoms of the dictionary search
     def _set_p0_grid(self, p0_grid, project):
@@ -259,6 +267,30 @@ class HipCurveFitSolver(CurveFitBase):
         self.p0_grid = {n: list(map(float, np.atleast_1d(v))) for n, v in p0_grid.items()}
         self.p0_grid_project = bool(project)
         self._p0_atoms = np.ascontiguousarray(np.array(list(itertools.product(*axes)), float).T)  # (n_free, n_atoms)
+
+    # ------------------------------------------------------------------ p0_peel: start values from the peeling fit
+    def _set_p0_peel(self, p0_peel):
+        """Validates `p0_peel` ({"b_thresholds": [...], "weighting": "signal2"}); nothing is set up without it."""
+        self.p0_peel = None
+        if p0_peel is None:
+            return
+        if self._p0_atoms is not None:
+            raise ValueError("p0_peel and p0_grid both choose the per-voxel start values; give one of them")
+        if not isinstance(p0_peel, dict) or set(p0_peel) - {"b_thresholds", "weighting"}:
+            raise ValueError("p0_peel must be a dict with the keys 'b_thresholds' and (optionally) 'weighting'")
+        _peel_refusals("p0_peel", self.model)
+        if self.precision == "float32" or self.io_dtype is not np.float64:
+            raise ValueError("p0_peel is built for precision='float64' and io_dtype='float64': its start values are float64 arrays")
+        weighting = p0_peel.get("weighting", "signal2")
+        if weighting not in api.LOGLINEAR_WEIGHTING:
+            raise ValueError(f"p0_peel: weighting must be one of {sorted(api.LOGLINEAR_WEIGHTING)}, got {weighting!r}")
+        thresholds = p0_peel.get("b_thresholds")
+        try:
+            api.peel_masks(np.zeros(1), self._kernel_model, thresholds)  # count and order
+        except ValueError as e:
+            raise ValueError(f"p0_peel: {e}") from None
+        self.p0_peel = {"b_thresholds": None if thresholds is None else [float(t) for t in np.atleast_1d(thresholds)],
+                        "weighting": weighting}
 
     # ------------------------------------------------------------------ p0 / bounds (curvefit.py:319-392)
     def _prepare_p0_bounds(self, p0, bounds, n_pixels):
@@ -395,8 +427,17 @@ class HipCurveFitSolver(CurveFitBase):
                 raise ValueError("p0_grid is not built with per-pixel fixed parameters (the dictionary would differ from voxel to voxel)")
             if per_voxel:
                 raise ValueError("p0_grid works with shared bounds: one dictionary serves the whole call")
+        peel = self.p0_peel is not None
+        if peel:  # the start of every voxel is the peel estimate; a shared p0 (the solver's, or fit()'s) serves the failed voxels
+            if isinstance(p0, np.ndarray) and p0.ndim == 2:
+                raise ValueError("p0_peel chooses the per-voxel start values itself: an explicit per-voxel p0 cannot be honoured")
+            if pixel_fixed_params or fixed:
+                raise ValueError("p0_peel is not built with fixed parameters (pixel_fixed_params): every stage fits its own "
+                                 "amplitude and diffusivity")
+            if per_voxel:
+                raise ValueError("p0_peel works with shared bounds: the peel estimate is clipped into one box for the whole call")
         res = self._run(xdata, np.ascontiguousarray(ydata, self.io_dtype), p0_a, lo_a, hi_a, per_voxel, fixed_idx,
-                        fixed_vals, jac, grid)
+                        fixed_vals, jac, grid, peel)
         self._pack(res, n_pixels, free_names)
         return self
 
@@ -411,7 +452,7 @@ class HipCurveFitSolver(CurveFitBase):
         self.params_ = {name: [float(popt[i, 0])] if n_pixels == 1 else popt[i] for i, name in enumerate(free_names)}
         self.diagnostics_ = {"pcov": (pcov[0] if n_pixels == 1 else pcov) if pcov is not None else None, "n_pixels": n_pixels,
                              "status": status, "nfev": res["nfev"], "cost": res["cost"]}
-        for key in ("p0_atom", "p0_cost"):  # a fit that started from the dictionary search (p0_grid)
+        for key in ("p0_atom", "p0_cost", "p0_status"):  # a fit that started from the dictionary search (p0_grid) / the peel (p0_peel)
             if key in res:
                 self.diagnostics_[key] = res[key]
 
@@ -432,7 +473,19 @@ class HipCurveFitSolver(CurveFitBase):
                               out=out or None, **kw)
         return dict(res, p0_atom=gs["best"], p0_cost=gs["cost"])
 
-    def _run(self, xdata, ydata, p0, lo, hi, per_voxel, fixed_idx, fixed_vals, jac, grid=False):
+    def _peel_fit(self, xdata, ydata, p0, lo, hi, device, kw, out=None):
+        """One shard with p0_peel: the peeling fit clipped into the shared bounds (failed voxels: the shared p0), then the fit from
+        these per-voxel start values.  A start that the clip left exactly on a bound is moved inside by the fit itself, as
+        SciPy's least_squares does (make_strictly_feasible, rstep 1e-10)."""
+        out = out or {}
+        pe = api.peel(xdata, ydata, self._kernel_model, b_thresholds=self.p0_peel["b_thresholds"], weighting=self.p0_peel["weighting"],
+                      clip=(lo, hi), fallback=p0, device=device, out={"status": out.get("p0_status")})
+        tile = lambda a: np.ascontiguousarray(np.repeat(a[:, None], ydata.shape[0], axis=1))
+        res = self._batch_fit(self._kernel_model, xdata, ydata, pe["params"], tile(lo), tile(hi), fixed_vals=None, device=device,
+                              out=out or None, **kw)
+        return dict(res, p0_status=pe["status"])
+
+    def _run(self, xdata, ydata, p0, lo, hi, per_voxel, fixed_idx, fixed_vals, jac, grid=False, peel=False):
         n_vox = ydata.shape[0]
         kw = dict(max_nfev=int(self.max_iter), ftol=float(self.tol), xtol=self.xtol, gtol=self.gtol, jac=jac,
                   fixed_idx=fixed_idx, sigma=self.sigma, absolute_sigma=self.absolute_sigma, **self._kernel_t1)
@@ -442,6 +495,8 @@ class HipCurveFitSolver(CurveFitBase):
         if n_dev == 1:
             if grid:
                 return self._grid_fit(xdata, ydata, lo, hi, fixed_vals, self.device, kw)
+            if peel:
+                return self._peel_fit(xdata, ydata, p0, lo, hi, self.device, kw)
             return self._batch_fit(self._kernel_model, xdata, ydata, p0, lo, hi, fixed_vals=fixed_vals,
                                    device=self.device, **kw)
         parts = _split(n_vox, n_dev)
@@ -453,6 +508,8 @@ class HipCurveFitSolver(CurveFitBase):
                 "cost": np.empty(n_vox, dt), **{key: np.empty(n_vox, d) for key, d in self._extra_outputs.items()}}
         if grid:
             full.update(p0_atom=np.empty(n_vox, np.int32), p0_cost=np.empty(n_vox, np.float64))
+        if peel:
+            full.update(p0_status=np.empty(n_vox, np.int8))
 
         def work(k):
             a, b = parts[k]
@@ -466,6 +523,8 @@ class HipCurveFitSolver(CurveFitBase):
             with pinned_to_gpu(dev_k):  # this thread and the call's helper threads stay on the NUMA node of their GPU
                 if grid:
                     return self._grid_fit(xdata, ydata[sl], lo, hi, fv, dev_k, kw, out={key: v[sl] for key, v in full.items()})["popt"]
+                if peel:
+                    return self._peel_fit(xdata, ydata[sl], p0, lo, hi, dev_k, kw, out={key: v[sl] for key, v in full.items()})["popt"]
                 return self._batch_fit(self._kernel_model, xdata, ydata[sl], *pv, fixed_vals=fv,
                                        device=dev_k, out={key: v[sl] for key, v in full.items()}, **kw)["popt"]
 
@@ -492,6 +551,9 @@ class HipConstrainedCurveFitSolver(HipCurveFitSolver):
                  multi_threading: bool = False, use_jacobian: bool = True, **solver_kwargs):
         if solver_kwargs.get("p0_grid") is not None or solver_kwargs.get("p0_grid_project") is not None:
             raise ValueError("p0_grid is not built for HipConstrainedCurveFitSolver: the dictionary knows nothing of the constraint "
+                             "f1 + f2 <= 1 and the constrained fit takes one shared start; use HipCurveFitSolver")
+        if solver_kwargs.get("p0_peel") is not None:
+            raise ValueError("p0_peel is not built for HipConstrainedCurveFitSolver: the peel estimate knows nothing of the constraint "
                              "f1 + f2 <= 1 and the constrained fit takes one shared start; use HipCurveFitSolver")
         if fraction_constraint and not getattr(model, "fit_reduced", False):  # constrained_curvefit.py:72-79
             raise ValueError("fraction_constraint=True requires fit_reduced=True. In reduced mode the signal is normalised to S0=1 "
@@ -612,6 +674,87 @@ class HipLogLinearSolver(RefBaseSolver):
         self.params_ = {name: [float(params[i, 0])] if n_pixels == 1 else params[i] for i, name in enumerate(("S0", "D"))}
         self.diagnostics_ = {"pcov": pcov[0] if n_pixels == 1 else pcov, "n_pixels": n_pixels, "status": status,
                              "n_used": res["n_used"], "ss_res": res["ss_res"]}
+        return self
+
+
+_PEEL_MESSAGES = {0: "A peeling stage had fewer than two positive residuals at distinct b-values: no line to fit.",
+                  -2: "array must not contain infs or NaNs"}
+
+
+def _peel_refusals(who, model):
+    """What the peeling fit is not built with, refused by name: the T1 / STEAM factor and fixed parameters."""
+    if kernel_t1(model)["t1_mode"]:
+        raise ValueError(f"{who} is not built with the T1 / STEAM factor (fit_t1 / fit_t1_steam)")
+    if getattr(model, "fixed_params", None):
+        raise ValueError(f"{who} is not built with fixed parameters (fixed_params {dict(model.fixed_params)}): every stage fits its own "
+                         "amplitude and diffusivity")
+
+
+class HipPeelSolver(RefBaseSolver):
+    """Exponential peeling ("curve stripping", the fully segmented IVIM estimate) of a mono-, bi- or tri-exponential model per voxel
+    (pnx_peel_f64, include/pnx.h): the slowest compartment is fitted log-linearly on the high b-values and subtracted, the next
+    faster one on what is left of the lower b-values, once more for a third.  Registered as `hip_peel`; no counterpart in the
+    reference, whose solver contract it keeps.
+
+    model: any of the seven layouts, nothing fixed, no T1 / STEAM factor.  `max_iter` and `tol` are accepted because the TOML loader
+    always passes them; a closed form has no use for either.  Keyword arguments:
+        b_thresholds: K - 1 ascending b-values for K exponentials (api.peel_masks): the slowest compartment is fitted on
+            b >= the last threshold, the fastest on b < the first.  Not needed for the mono-exponential model.
+        weighting: "signal2" (default, w = r^2) or "none".
+        bounds: None or {name: (lo, hi)} for every parameter: the result is clipped into them (status 2 for a voxel that was moved).
+        p0: None or {name: value}: what a voxel that could not be fitted (status <= 0) reports as its parameters, the reference's
+            failure convention (NaN without p0).
+        device, io_dtype ("float32": float32 arrays across the ABI, fp64 arithmetic) as HipCurveFitSolver's.
+    Any other keyword (the reference's solver arguments: method, multi_threading, ...) is accepted and ignored.
+    After fit: params_ keyed by the model's names, diagnostics_ {"n_pixels", "status", "n_used" (K, n_pixels), "ss_res"} (ss_res in
+    the signal domain over the b-values of every stage), pixel_results_ (no covariance: peeling has no honest closed form)."""
+
+    def __init__(self, model: Any, max_iter: int = 250, tol: float = 1e-8, p0: dict[str, float] | None = None,
+                 bounds: dict[str, tuple[float, float]] | None = None, b_thresholds=None, weighting: str = "signal2", device: int = 0,
+                 io_dtype: str = "float64", **ignored_reference_kwargs):
+        RefBaseSolver.__init__(self, model=model, max_iter=max_iter, tol=tol, verbose=bool(ignored_reference_kwargs.pop("verbose", False)))
+        _peel_refusals("HipPeelSolver", model)
+        self._kernel_model = kernel_model_key(model)
+        names = api.MODEL_PARAM_NAMES[self._kernel_model]
+        if weighting not in api.LOGLINEAR_WEIGHTING:
+            raise ValueError(f"weighting must be one of {sorted(api.LOGLINEAR_WEIGHTING)}, got {weighting!r}")
+        K = api.PEEL_STAGES[self._kernel_model]
+        if K > 1 and b_thresholds is None:
+            raise ValueError(f"b_thresholds is required: {K - 1} ascending b-values that separate the {K} compartments")
+        api.peel_masks(np.zeros(1), self._kernel_model, b_thresholds)  # count and order of b_thresholds
+        for d in (p0, bounds):
+            if d is not None:
+                _validate_parameter_names(d, names)
+        self.p0 = p0
+        self.bounds = bounds
+        self.b_thresholds = None if b_thresholds is None else [float(t) for t in np.atleast_1d(b_thresholds)]
+        self.weighting = weighting
+        self.device = int(device)
+        self.io_dtype = _io_dtype(io_dtype)
+        self.solver_kwargs = ignored_reference_kwargs
+
+    def fit(self, xdata: np.ndarray, ydata: np.ndarray, pixel_fixed_params=None, **fit_kwargs) -> "HipPeelSolver":
+        if pixel_fixed_params:
+            raise ValueError("HipPeelSolver fits every parameter of its stages: pixel_fixed_params cannot be honoured")
+        self._reset_state()
+        xdata = np.asarray(xdata)
+        ydata = np.asarray(ydata)
+        _validate_data_shapes(xdata, ydata)
+        if ydata.ndim == 1:
+            ydata = ydata[np.newaxis, :]
+        if ydata.ndim > 2:
+            raise ValueError(f"ydata must be 1D or 2D array, but got shape {ydata.shape}.")
+        n_pixels = ydata.shape[0]
+        names = api.MODEL_PARAM_NAMES[self._kernel_model]
+        clip = None if self.bounds is None else ([self.bounds[n][0] for n in names], [self.bounds[n][1] for n in names])
+        fallback = None if self.p0 is None else [float(self.p0[n]) for n in names]
+        res = api.peel(xdata, np.ascontiguousarray(ydata, self.io_dtype), self._kernel_model, b_thresholds=self.b_thresholds,
+                       weighting=self.weighting, clip=clip, fallback=fallback, device=self.device)
+        params, status = res["params"], res["status"]
+        self.pixel_results_ = PixelResultsView(
+            params.T, None, status > 0, lambda i, st=status: None if st[i] > 0 else _PEEL_MESSAGES.get(int(st[i]), "fit failed"))
+        self.params_ = {name: [float(params[i, 0])] if n_pixels == 1 else params[i] for i, name in enumerate(names)}
+        self.diagnostics_ = {"n_pixels": n_pixels, "status": status, "n_used": res["n_used"], "ss_res": res["ss_res"]}
         return self
 
 
