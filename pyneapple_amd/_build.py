@@ -32,15 +32,15 @@ SOURCE_GROUPS = {
     "curvefit_f32": ["pnx_curvefit_f32_kernel.hpp", "pnx_curvefit_f32.hip", "pnx_model_t.hpp"],
     "nnls": ["pnx_nnls.hip", "pnx_nnls.hpp", "pnx_nnls_dev.hpp", "pnx_nnls_qr.hip", "pnx_nnls_blk.hip", "pnx_nnls_blk_kernel.hpp"],
     "sweep": ["pnx_sweep.hip", "pnx_model_t.hpp"],
-    "predict": ["pnx_predict.hip", "pnx_predict.hpp"],
+    "predict": ["pnx_predict.hip", "pnx_predict.hpp", "pnx_tile.hpp"],
     "simplex": ["pnx_simplex.hip", "pnx_simplex.hpp"],
     "grid": ["pnx_grid.hip", "pnx_grid.hpp", "pnx_grid_args.hpp"],
-    "loglin": ["pnx_loglin.hip", "pnx_loglin.hpp", "pnx_loglin_args.hpp"],
-    "peel": ["pnx_peel.hip", "pnx_peel.hpp", "pnx_peel_args.hpp"],
+    "loglin": ["pnx_loglin.hip", "pnx_loglin.hpp", "pnx_loglin_args.hpp", "pnx_tile.hpp"],
+    "peel": ["pnx_peel.hip", "pnx_peel.hpp", "pnx_peel_args.hpp", "pnx_tile.hpp"],
     # the host boundary (streamed path, chunk ring, deferred NNLS hand-over, peak tables): host-mode / PCIe-inclusive figures and
     # the host-path fuzz summaries are stamped with this id, so that they are not replayed as current after pnx_api.hip changes
     # (round 4: the orchestration of both host paths moved into pnx_host_pipeline.hpp; the peak analysis the rings call is pnx_spectrum.hip)
-    "host": ["pnx_api.hip", "pnx_internal.hpp", "pnx_host_pipeline.hpp", "pnx_spectrum.hip"],
+    "host": ["pnx_api.hip", "pnx_internal.hpp", "pnx_host_pipeline.hpp", "pnx_spectrum.hip", "pnx_launch.hpp", "pnx_args_common.hpp"],
 }
 
 

@@ -283,25 +283,45 @@ LOGLINEAR_WEIGHTING = {"none": 0, "signal2": 1}  # w = 1 / w = y^2 (include/pnx.
 LOGLINEAR_MAX_REWEIGHT = 8  # kLogLinMaxReweight of csrc/pnx_loglin_args.hpp
 
 
-def _loglinear_args(b, n_b, dt, bvalue_mask, weighting, clip):
-    """The small host arguments of pnx_loglinear_f64 / _f32 in the storage type `dt`: b, the uint8 mask or None, the weighting
-    code, lo / hi (2,) or None."""
+def _b_values(b, n_b, dt):
     b = np.ascontiguousarray(b, dt)
     if b.shape != (n_b,):
         raise ValueError(f"b has shape {b.shape}, expected ({n_b},)")
-    use = None
-    if bvalue_mask is not None:
-        use = np.ascontiguousarray(np.asarray(bvalue_mask) != 0, np.uint8)
-        if use.shape != (n_b,):
-            raise ValueError(f"bvalue_mask has shape {use.shape}, expected ({n_b},)")
+    return b
+
+
+def _weighting_and_clip(dt, weighting, clip, n, clip_text):
+    """The weighting code and lo / hi (n,) in the storage type `dt`, or None: what _loglinear_args and _peel_args check alike."""
     if weighting not in LOGLINEAR_WEIGHTING:
         raise ValueError(f"weighting must be one of {sorted(LOGLINEAR_WEIGHTING)}, got {weighting!r}")
     lo = hi = None
     if clip is not None:
         lo, hi = (np.ascontiguousarray(a, dt) for a in clip)
-        if lo.shape != (2,) or hi.shape != (2,):
-            raise ValueError("clip must be (lo, hi) with two entries each: the bounds of S0 and D")
-    return b, use, LOGLINEAR_WEIGHTING[weighting], lo, hi
+        if lo.shape != (n,) or hi.shape != (n,):
+            raise ValueError(clip_text)
+    return LOGLINEAR_WEIGHTING[weighting], lo, hi
+
+
+def _loglinear_args(b, n_b, dt, bvalue_mask, weighting, clip):
+    """The small host arguments of pnx_loglinear_f64 / _f32 in the storage type `dt`: b, the uint8 mask or None, the weighting
+    code, lo / hi (2,) or None."""
+    b = _b_values(b, n_b, dt)
+    use = None
+    if bvalue_mask is not None:
+        use = np.ascontiguousarray(np.asarray(bvalue_mask) != 0, np.uint8)
+        if use.shape != (n_b,):
+            raise ValueError(f"bvalue_mask has shape {use.shape}, expected ({n_b},)")
+    return (b, use, *_weighting_and_clip(dt, weighting, clip, 2, "clip must be (lo, hi) with two entries each: the bounds of S0 and D"))
+
+
+def _loglinear_call(f32, args, n_reweight, y, params, pcov, status, n_used, ss_res, mem, device, stream):
+    """pnx_loglinear_f64, or _f32 where the storage type is float32, on host arrays or device tensors; args: what _loglinear_args
+    made of the small host arguments."""
+    b, use, wcode, lo, hi = args
+    n_vox, n_b = (int(s) for s in y.shape)
+    fn = load().pnx_loglinear_f32 if f32 else load().pnx_loglinear_f64
+    check(fn(n_vox, n_b, ptr(b), ptr(use), wcode, int(n_reweight), int(lo is not None), ptr(lo), ptr(hi), ptr(y), ptr(params),
+             ptr(pcov), ptr(status), ptr(n_used), ptr(ss_res), mem, int(device), stream))
 
 
 def loglinear(b, y, *, bvalue_mask=None, weighting="signal2", n_reweight=0, clip=None, want_pcov=True, device=0, out=None):
@@ -317,15 +337,13 @@ def loglinear(b, y, *, bvalue_mask=None, weighting="signal2", n_reweight=0, clip
     dt = np.float32 if getattr(y, "dtype", None) == np.float32 else np.float64
     y = np.ascontiguousarray(np.atleast_2d(y), dt)
     n_vox, n_b = y.shape
-    b, use, wcode, lo, hi = _loglinear_args(b, n_b, dt, bvalue_mask, weighting, clip)
+    args = _loglinear_args(b, n_b, dt, bvalue_mask, weighting, clip)
     params = _out(out, "params", (2, n_vox), dt)
     pcov = _out(out, "pcov", (n_vox, 2, 2), dt) if want_pcov else None
     status = _out(out, "status", (n_vox,), np.int8)
     n_used = _out(out, "n_used", (n_vox,), np.int32)
     ss_res = _out(out, "ss_res", (n_vox,), dt)
-    fn = load().pnx_loglinear_f32 if dt is np.float32 else load().pnx_loglinear_f64
-    check(fn(n_vox, n_b, ptr(b), ptr(use), wcode, int(n_reweight), int(clip is not None), ptr(lo), ptr(hi), ptr(y), ptr(params),
-             ptr(pcov), ptr(status), ptr(n_used), ptr(ss_res), MEM_HOST, int(device), None))
+    _loglinear_call(dt is np.float32, args, n_reweight, y, params, pcov, status, n_used, ss_res, MEM_HOST, device, None)
     return dict(params=params, pcov=pcov, status=status, n_used=n_used, ss_res=ss_res)
 
 
@@ -335,11 +353,8 @@ def loglinear_device(b, y, params, pcov, status, n_used, ss_res, device, *, bval
     (2, n_vox), and -- each may be None -- pcov (n_vox, 2, 2), status int8, n_used int32, ss_res (n_vox,).  float32 tensors select
     pnx_loglinear_f32.  b, bvalue_mask and the clip bounds are host arrays, as `loglinear` takes them."""
     f32 = "float32" in str(getattr(y, "dtype", ""))
-    n_vox, n_b = (int(s) for s in y.shape)
-    b, use, wcode, lo, hi = _loglinear_args(b, n_b, np.float32 if f32 else np.float64, bvalue_mask, weighting, clip)
-    fn = load().pnx_loglinear_f32 if f32 else load().pnx_loglinear_f64
-    check(fn(n_vox, n_b, ptr(b), ptr(use), wcode, int(n_reweight), int(clip is not None), ptr(lo), ptr(hi), ptr(y), ptr(params),
-             ptr(pcov), ptr(status), ptr(n_used), ptr(ss_res), MEM_DEVICE, int(device), stream))
+    args = _loglinear_args(b, int(y.shape[1]), np.float32 if f32 else np.float64, bvalue_mask, weighting, clip)
+    _loglinear_call(f32, args, n_reweight, y, params, pcov, status, n_used, ss_res, MEM_DEVICE, device, stream)
 
 
 PEEL_STAGES = {"mono": 1, "bi_reduced": 2, "bi_s0": 2, "bi_full": 2, "tri_reduced": 3, "tri_s0": 3, "tri_full": 3}  # exponentials
@@ -364,9 +379,7 @@ def _peel_args(b, n_b, dt, model, masks, b_thresholds, weighting, clip, fallback
     if model not in PEEL_STAGES:
         raise ValueError(f"model must be one of {sorted(PEEL_STAGES)}, got {model!r}")
     K, n = PEEL_STAGES[model], len(MODEL_PARAM_NAMES[model])
-    b = np.ascontiguousarray(b, dt)
-    if b.shape != (n_b,):
-        raise ValueError(f"b has shape {b.shape}, expected ({n_b},)")
+    b = _b_values(b, n_b, dt)
     if (masks is None) == (b_thresholds is None) and not (K == 1 and masks is None):
         raise ValueError("peel takes either masks (K, n_b) or b_thresholds (K - 1 ascending values)")
     if masks is None:
@@ -375,18 +388,23 @@ def _peel_args(b, n_b, dt, model, masks, b_thresholds, weighting, clip, fallback
         use = np.ascontiguousarray(np.atleast_2d(np.asarray(masks)) != 0, np.uint8)
         if use.shape != (K, n_b):
             raise ValueError(f"masks has shape {use.shape}, expected ({K}, {n_b})")
-    if weighting not in LOGLINEAR_WEIGHTING:
-        raise ValueError(f"weighting must be one of {sorted(LOGLINEAR_WEIGHTING)}, got {weighting!r}")
-    lo = hi = None
-    if clip is not None:
-        lo, hi = (np.ascontiguousarray(a, dt) for a in clip)
-        if lo.shape != (n,) or hi.shape != (n,):
-            raise ValueError(f"clip must be (lo, hi) with {n} entries each: the bounds of {MODEL_PARAM_NAMES[model]}")
+    wcode, lo, hi = _weighting_and_clip(dt, weighting, clip, n,
+                                        f"clip must be (lo, hi) with {n} entries each: the bounds of {MODEL_PARAM_NAMES[model]}")
     if fallback is not None:
         fallback = np.ascontiguousarray(fallback, dt)
         if fallback.shape != (n,):
             raise ValueError(f"fallback must have {n} entries: {MODEL_PARAM_NAMES[model]}")
-    return b, use, LOGLINEAR_WEIGHTING[weighting], lo, hi, fallback
+    return b, use, wcode, lo, hi, fallback
+
+
+def _peel_call(f32, args, model, y, params, status, n_used, ss_res, mem, device, stream):
+    """pnx_peel_f64, or _f32 where the storage type is float32, on host arrays or device tensors; args: what _peel_args made of the
+    small host arguments."""
+    b, use, wcode, lo, hi, fb = args
+    n_vox, n_b = (int(s) for s in y.shape)
+    fn = load().pnx_peel_f32 if f32 else load().pnx_peel_f64
+    check(fn(MODEL_IDS[model], n_vox, n_b, ptr(b), ptr(use), wcode, int(lo is not None), ptr(lo), ptr(hi), ptr(fb), ptr(y), ptr(params),
+             ptr(status), ptr(n_used), ptr(ss_res), mem, int(device), stream))
 
 
 def peel(b, y, model, *, masks=None, b_thresholds=None, weighting="signal2", clip=None, fallback=None, device=0, out=None):
@@ -402,14 +420,12 @@ def peel(b, y, model, *, masks=None, b_thresholds=None, weighting="signal2", cli
     dt = np.float32 if getattr(y, "dtype", None) == np.float32 else np.float64
     y = np.ascontiguousarray(np.atleast_2d(y), dt)
     n_vox, n_b = y.shape
-    b, use, wcode, lo, hi, fb = _peel_args(b, n_b, dt, model, masks, b_thresholds, weighting, clip, fallback)
+    args = _peel_args(b, n_b, dt, model, masks, b_thresholds, weighting, clip, fallback)
     params = _out(out, "params", (len(MODEL_PARAM_NAMES[model]), n_vox), dt)
     status = _out(out, "status", (n_vox,), np.int8)
     n_used = _out(out, "n_used", (PEEL_STAGES[model], n_vox), np.int32)
     ss_res = _out(out, "ss_res", (n_vox,), dt)
-    fn = load().pnx_peel_f32 if dt is np.float32 else load().pnx_peel_f64
-    check(fn(MODEL_IDS[model], n_vox, n_b, ptr(b), ptr(use), wcode, int(clip is not None), ptr(lo), ptr(hi), ptr(fb), ptr(y), ptr(params),
-             ptr(status), ptr(n_used), ptr(ss_res), MEM_HOST, int(device), None))
+    _peel_call(dt is np.float32, args, model, y, params, status, n_used, ss_res, MEM_HOST, device, None)
     return dict(params=params, status=status, n_used=n_used, ss_res=ss_res)
 
 
@@ -419,11 +435,8 @@ def peel_device(b, y, model, params, status, n_used, ss_res, device, *, masks=No
     (n_params, n_vox), and -- each may be None -- status int8, n_used (K, n_vox) int32, ss_res (n_vox,).  float32 tensors select
     pnx_peel_f32.  b, the masks or thresholds, the clip bounds and the fallback are host arrays, as `peel` takes them."""
     f32 = "float32" in str(getattr(y, "dtype", ""))
-    n_vox, n_b = (int(s) for s in y.shape)
-    b, use, wcode, lo, hi, fb = _peel_args(b, n_b, np.float32 if f32 else np.float64, model, masks, b_thresholds, weighting, clip, fallback)
-    fn = load().pnx_peel_f32 if f32 else load().pnx_peel_f64
-    check(fn(MODEL_IDS[model], n_vox, n_b, ptr(b), ptr(use), wcode, int(clip is not None), ptr(lo), ptr(hi), ptr(fb), ptr(y), ptr(params),
-             ptr(status), ptr(n_used), ptr(ss_res), MEM_DEVICE, int(device), stream))
+    args = _peel_args(b, int(y.shape[1]), np.float32 if f32 else np.float64, model, masks, b_thresholds, weighting, clip, fallback)
+    _peel_call(f32, args, model, y, params, status, n_used, ss_res, MEM_DEVICE, device, stream)
 
 
 class NnlsPlan:

@@ -21,7 +21,7 @@
 #include "pnx_grid.hpp"
 #include "pnx_grid_args.hpp"
 #include "pnx_host_pipeline.hpp"
-#include "pnx_internal.hpp"
+#include "pnx_launch.hpp"
 #include "pnx_loglin.hpp"
 #include "pnx_nnls.hpp"
 #include "pnx_peel.hpp"
@@ -42,12 +42,6 @@ int set_error(int code, const char *fmt, ...) {
     return code;
 }
 const char *last_error_text() { return g_err; }
-
-#define PNX_HIP(call)                                                                              \
-    do {                                                                                           \
-        hipError_t e__ = (call);                                                                   \
-        if (e__ != hipSuccess) return set_error(PNX_ERR_HIP, "%s: %s", #call, hipGetErrorString(e__)); \
-    } while (0)
 
 struct DeviceInfo {
     bool ok = false;
@@ -75,6 +69,13 @@ static int get_device(int device, DeviceInfo **out) {
         d.ok = true;
     }
     *out = &d;
+    return PNX_OK;
+}
+
+// get_device, and the calling thread bound to it
+static int use_device(int device, DeviceInfo **out) {
+    if (int rc = get_device(device, out)) return rc;
+    PNX_HIP(hipSetDevice(device));
     return PNX_OK;
 }
 
@@ -486,6 +487,19 @@ static int chunk_ring(const ArrayTable &A, size_t nv, size_t chunk, int max_slot
     return run_pipeline(n_chunks, n_slots, k_streams, touchers, device, user_stream, ops);
 }
 
+// The ring with the settings every host-array call shares: default_chunk voxels per chunk (PNX_HOST_CHUNK), three slots
+// (PNX_HOST_SLOTS), two kernel streams (PNX_HOST_KSTREAMS) and the page-touch helpers the calls in flight leave room for.
+static int ring_call(const ArrayTable &A, size_t nv, int default_chunk, int device, hipStream_t st, const ChunkLaunch &launch,
+                     const HostCallGuard &hg) {
+    const size_t chunk = (size_t)dev_env_int("PNX_HOST_CHUNK", default_chunk, 1024, 1 << 26);
+    return chunk_ring(A, nv, chunk, dev_env_int("PNX_HOST_SLOTS", 3, 2, 8), dev_env_int("PNX_HOST_KSTREAMS", 2, 1, 4), hg.touchers(), device, st,
+                      launch);
+}
+static int ring_call(const ArrayTable &A, size_t nv, int default_chunk, int device, hipStream_t st, const ChunkLaunch &launch) {
+    HostCallGuard hg;  // this call is in flight from here on
+    return ring_call(A, nv, default_chunk, device, st, launch, hg);
+}
+
 // ---- host-pointer calls, streamed --------------------------------------------------------------------------------
 // The chunk ring above launches one persistent kernel per chunk, and every one of them ends in a drain tail (lanes whose
 // queue ran dry idle until the slowest voxel of their wave has converged): seven tails cost C3 about 10 ms of its 50.
@@ -771,9 +785,7 @@ static int curvefit_batch(const pnx_curvefit_opts *o, int64_t n_vox, const T *b,
         return set_error(PNX_ERR_INVALID, "opts->queue_order is for PNX_MEM_DEVICE calls (a host-array call completes its pieces in index order)");
     if (n_vox == 0) return PNX_OK;
     DeviceInfo *dev;
-    rc = get_device(device, &dev);
-    if (rc) return rc;
-    PNX_HIP(hipSetDevice(device));
+    if ((rc = use_device(device, &dev))) return rc;
     const int n = o->n_free;
     const size_t nv = (size_t)n_vox;
     const bool pv = o->per_voxel_p0_bounds != 0, fpv = o->n_fixed && o->fixed_per_voxel;
@@ -861,9 +873,8 @@ static int curvefit_batch(const pnx_curvefit_opts *o, int64_t n_vox, const T *b,
     // ---- host staging: chunk ring (run_pipeline above)
     // float32 transfers are half as long per voxel: a larger chunk (fewer drain tails of the persistent kernel) at the same
     // exposed transfer latency -- C3 float32: 86.3 M voxels/s at 768 Ki, 89.8 M at 1 Mi, 82.5 M at 2 Mi (profiles/host_chunk_sweep_f32.py)
-    const size_t chunk = (size_t)dev_env_int("PNX_HOST_CHUNK", F32 ? 1 << 20 : 3 << 18, 1024, 1 << 26);
-    return chunk_ring(A, nv, chunk, dev_env_int("PNX_HOST_SLOTS", 3, 2, 8), dev_env_int("PNX_HOST_KSTREAMS", 2, 1, 4), hg.touchers(), device,
-                      (hipStream_t)stream, [&](size_t c, const DevSet &D, hipStream_t st) { return curvefit_on(o, A, sh, D, c, dev, st); });
+    return ring_call(A, nv, F32 ? 1 << 20 : 3 << 18, device, (hipStream_t)stream,
+                     [&](size_t c, const DevSet &D, hipStream_t st) { return curvefit_on(o, A, sh, D, c, dev, st); }, hg);
 }
 
 // ---- constrained curve fit, f1 + f2 <= 1: pnx_curvefit_simplex_f64 (streaming kernels: pnx_simplex.hip) -----------------
@@ -952,8 +963,7 @@ extern "C" int pnx_curvefit_simplex_f64(const pnx_curvefit_opts *o, int64_t n_vo
     if (mem != PNX_MEM_HOST && mem != PNX_MEM_DEVICE) return set_error(PNX_ERR_INVALID, "mem=%d", mem);
     if (n_vox == 0) return PNX_OK;
     DeviceInfo *dev;
-    if ((rc = get_device(device, &dev))) return rc;
-    PNX_HIP(hipSetDevice(device));
+    if ((rc = use_device(device, &dev))) return rc;
     const int n = o->n_free;
     const bool pv = o->per_voxel_p0_bounds != 0;
     if (mem == PNX_MEM_DEVICE) {
@@ -985,14 +995,11 @@ extern "C" int pnx_curvefit_simplex_f64(const pnx_curvefit_opts *o, int64_t n_vo
     A.add(cost, sizeof(double), 1, true).always = pcov != nullptr;
     A.add(lambda, sizeof(double), 1, true);
     A.add(face, 1, 1, true);
-    HostCallGuard hg;
-    const size_t chunk = (size_t)dev_env_int("PNX_HOST_CHUNK", 3 << 18, 1024, 1 << 26);
-    return chunk_ring(A, (size_t)n_vox, chunk, dev_env_int("PNX_HOST_SLOTS", 3, 2, 8), dev_env_int("PNX_HOST_KSTREAMS", 2, 1, 4), hg.touchers(),
-                      device, (hipStream_t)stream, [&](size_t c, const DevSet &D, hipStream_t st) {
-                          return simplex_on(o, (int64_t)c, sh.b, D.d(CF_Y), per_voxel_or(A, D, CF_P0, sh.p0), per_voxel_or(A, D, CF_LO, sh.lo),
-                                            per_voxel_or(A, D, CF_HI, sh.hi), D.d(CF_POPT), D.d(CF_PCOV), (int8_t *)D.dev[CF_STAT],
-                                            (int32_t *)D.dev[CF_NFEV], D.d(CF_COST), D.d(SX_LAMBDA), (int8_t *)D.dev[SX_FACE], dev, st);
-                      });
+    return ring_call(A, (size_t)n_vox, 3 << 18, device, (hipStream_t)stream, [&](size_t c, const DevSet &D, hipStream_t st) {
+        return simplex_on(o, (int64_t)c, sh.b, D.d(CF_Y), per_voxel_or(A, D, CF_P0, sh.p0), per_voxel_or(A, D, CF_LO, sh.lo),
+                          per_voxel_or(A, D, CF_HI, sh.hi), D.d(CF_POPT), D.d(CF_PCOV), (int8_t *)D.dev[CF_STAT], (int32_t *)D.dev[CF_NFEV],
+                          D.d(CF_COST), D.d(SX_LAMBDA), (int8_t *)D.dev[SX_FACE], dev, st);
+    });
 }
 
 // ---- fp32 arithmetic: pnx_curvefit_fast_f32 (kernel: pnx_curvefit_f32_kernel.hpp, launch: pnx_curvefit_f32.hip) ---------
@@ -1052,9 +1059,7 @@ extern "C" int pnx_curvefit_fast_f32(const pnx_curvefit_opts *o, int64_t n_vox, 
     if (mem != PNX_MEM_HOST && mem != PNX_MEM_DEVICE) return set_error(PNX_ERR_INVALID, "mem=%d", mem);
     if (n_vox == 0) return PNX_OK;
     DeviceInfo *dev;
-    rc = get_device(device, &dev);
-    if (rc) return rc;
-    PNX_HIP(hipSetDevice(device));
+    if ((rc = use_device(device, &dev))) return rc;
     const int n = o->n_free;
     const size_t nv = (size_t)n_vox;
     const bool pv = o->per_voxel_p0_bounds != 0;
@@ -1076,14 +1081,11 @@ extern "C" int pnx_curvefit_fast_f32(const pnx_curvefit_opts *o, int64_t n_vox, 
     A.add(status, 1, 1, true).always = pcov != nullptr;  // the covariance epilogue reads status and cost
     A.add(nfev, sizeof(int32_t), 1, true);
     A.add(cost, sizeof(float), 1, true).always = pcov != nullptr;
-    HostCallGuard hg;
-    const size_t chunk = (size_t)dev_env_int("PNX_HOST_CHUNK", 1 << 20, 1024, 1 << 26);
-    return chunk_ring(A, nv, chunk, dev_env_int("PNX_HOST_SLOTS", 3, 2, 8), dev_env_int("PNX_HOST_KSTREAMS", 2, 1, 4), hg.touchers(), device,
-                      (hipStream_t)stream, [&](size_t c, const DevSet &D, hipStream_t st) {
-                          auto f = [&](int k) { return (float *)D.dev[k]; };
-                          return curvefit_f32_device(o, (int64_t)c, b, f(CF_Y), pv ? f(CF_P0) : p0, pv ? f(CF_LO) : lo, pv ? f(CF_HI) : hi,
-                                                     f(CF_POPT), f(CF_PCOV), (int8_t *)D.dev[CF_STAT], (int32_t *)D.dev[CF_NFEV], f(CF_COST), dev, st);
-                      });
+    return ring_call(A, nv, 1 << 20, device, (hipStream_t)stream, [&](size_t c, const DevSet &D, hipStream_t st) {
+        auto f = [&](int k) { return (float *)D.dev[k]; };
+        return curvefit_f32_device(o, (int64_t)c, b, f(CF_Y), pv ? f(CF_P0) : p0, pv ? f(CF_LO) : lo, pv ? f(CF_HI) : hi, f(CF_POPT), f(CF_PCOV),
+                                   (int8_t *)D.dev[CF_STAT], (int32_t *)D.dev[CF_NFEV], f(CF_COST), dev, st);
+    });
 }
 
 // ---- log-linear mono-exponential fit: pnx_loglinear_f64 / _f32 (kernel: pnx_loglin.hip, argument checks: pnx_loglin_args.hpp) ---
@@ -1097,8 +1099,7 @@ static int loglinear(int64_t n_vox, int n_b, const T *b, const uint8_t *use, int
     if (rc) return rc;
     if (n_vox == 0) return PNX_OK;
     DeviceInfo *dev;
-    if ((rc = get_device(device, &dev))) return rc;
-    PNX_HIP(hipSetDevice(device));
+    if ((rc = use_device(device, &dev))) return rc;
     hipStream_t st = (hipStream_t)stream;
     if (mem == PNX_MEM_DEVICE) return loglinear_device<T>(o, n_vox, y, params, pcov, status, n_used, ss_res, st);
     enum { LL_Y, LL_P, LL_PCOV, LL_STAT, LL_NUSED, LL_SS };
@@ -1109,13 +1110,10 @@ static int loglinear(int64_t n_vox, int n_b, const T *b, const uint8_t *use, int
     A.add(status, 1, 1, true);
     A.add(n_used, sizeof(int32_t), 1, true);
     A.add(ss_res, sizeof(T), 1, true);
-    HostCallGuard hg;
-    const size_t chunk = (size_t)dev_env_int("PNX_HOST_CHUNK", sizeof(T) == 4 ? 1 << 20 : 3 << 18, 1024, 1 << 26);
-    return chunk_ring(A, (size_t)n_vox, chunk, dev_env_int("PNX_HOST_SLOTS", 3, 2, 8), dev_env_int("PNX_HOST_KSTREAMS", 2, 1, 4), hg.touchers(),
-                      device, st, [&](size_t n, const DevSet &D, hipStream_t s) {
-                          return loglinear_device<T>(o, (int64_t)n, (const T *)D.dev[LL_Y], (T *)D.dev[LL_P], (T *)D.dev[LL_PCOV],
-                                                     (int8_t *)D.dev[LL_STAT], (int32_t *)D.dev[LL_NUSED], (T *)D.dev[LL_SS], s);
-                      });
+    return ring_call(A, (size_t)n_vox, sizeof(T) == 4 ? 1 << 20 : 3 << 18, device, st, [&](size_t n, const DevSet &D, hipStream_t s) {
+        return loglinear_device<T>(o, (int64_t)n, (const T *)D.dev[LL_Y], (T *)D.dev[LL_P], (T *)D.dev[LL_PCOV], (int8_t *)D.dev[LL_STAT],
+                                   (int32_t *)D.dev[LL_NUSED], (T *)D.dev[LL_SS], s);
+    });
 }
 
 // ---- exponential peeling: pnx_peel_f64 / _f32 (kernel: pnx_peel.hip, argument checks: pnx_peel_args.hpp) -----------------------
@@ -1128,8 +1126,7 @@ static int peel(int model, int64_t n_vox, int n_b, const T *b, const uint8_t *us
     if (rc) return rc;
     if (n_vox == 0) return PNX_OK;
     DeviceInfo *dev;
-    if ((rc = get_device(device, &dev))) return rc;
-    PNX_HIP(hipSetDevice(device));
+    if ((rc = use_device(device, &dev))) return rc;
     hipStream_t st = (hipStream_t)stream;
     if (mem == PNX_MEM_DEVICE) return peel_device<T>(o, n_vox, y, params, status, n_used, ss_res, st);
     enum { PL_Y, PL_P, PL_STAT, PL_NUSED, PL_SS };
@@ -1139,13 +1136,10 @@ static int peel(int model, int64_t n_vox, int n_b, const T *b, const uint8_t *us
     A.add(status, 1, 1, true);
     A.add(n_used, sizeof(int32_t), (size_t)o.n_stage, true).pmajor = true;
     A.add(ss_res, sizeof(T), 1, true);
-    HostCallGuard hg;
-    const size_t chunk = (size_t)dev_env_int("PNX_HOST_CHUNK", sizeof(T) == 4 ? 1 << 20 : 3 << 18, 1024, 1 << 26);
-    return chunk_ring(A, (size_t)n_vox, chunk, dev_env_int("PNX_HOST_SLOTS", 3, 2, 8), dev_env_int("PNX_HOST_KSTREAMS", 2, 1, 4), hg.touchers(),
-                      device, st, [&](size_t n, const DevSet &D, hipStream_t s) {
-                          return peel_device<T>(o, (int64_t)n, (const T *)D.dev[PL_Y], (T *)D.dev[PL_P], (int8_t *)D.dev[PL_STAT],
-                                                (int32_t *)D.dev[PL_NUSED], (T *)D.dev[PL_SS], s);
-                      });
+    return ring_call(A, (size_t)n_vox, sizeof(T) == 4 ? 1 << 20 : 3 << 18, device, st, [&](size_t n, const DevSet &D, hipStream_t s) {
+        return peel_device<T>(o, (int64_t)n, (const T *)D.dev[PL_Y], (T *)D.dev[PL_P], (int8_t *)D.dev[PL_STAT], (int32_t *)D.dev[PL_NUSED],
+                              (T *)D.dev[PL_SS], s);
+    });
 }
 
 extern "C" {
@@ -1197,8 +1191,7 @@ int pnx_curvefit_predict_f64(const pnx_curvefit_opts *o, int64_t n_vox, int n_x,
     if (mem != PNX_MEM_HOST && mem != PNX_MEM_DEVICE) return set_error(PNX_ERR_INVALID, "mem=%d", mem);
     if (n_vox == 0) return PNX_OK;
     DeviceInfo *dev;
-    if ((rc = get_device(device, &dev))) return rc;
-    PNX_HIP(hipSetDevice(device));
+    if ((rc = use_device(device, &dev))) return rc;
     hipStream_t st = (hipStream_t)stream;
     if (!ss_res) y = nullptr;
     if (mem == PNX_MEM_DEVICE) return model_predict_device(&c, n_vox, n_x, x, params, fixed, y, pred, ss_res, st);
@@ -1233,8 +1226,7 @@ int pnx_curvefit_grid_start_f64(const pnx_curvefit_opts *o, int64_t n_vox, const
     if ((rc = grid_check_args(&c, n_vox, b, y, n_atoms, atoms, fixed, lo, hi, project_amplitude, p0_out, mem, &s0_row))) return rc;
     if (n_vox == 0) return PNX_OK;
     DeviceInfo *dev;
-    if ((rc = get_device(device, &dev))) return rc;
-    PNX_HIP(hipSetDevice(device));
+    if ((rc = use_device(device, &dev))) return rc;
     hipStream_t st = (hipStream_t)stream;
     AsyncBuf dict_buf;  // the dictionary: built once per call, stream-ordered, freed behind the work that reads it
     GridDict D;
@@ -1249,12 +1241,9 @@ int pnx_curvefit_grid_start_f64(const pnx_curvefit_opts *o, int64_t n_vox, const
     A.add(p0_out, sizeof(double), c.n_free, true).pmajor = true;
     A.add(best, sizeof(int32_t), 1, true);
     A.add(cost, sizeof(double), 1, true);
-    HostCallGuard hg;
-    const size_t chunk = (size_t)dev_env_int("PNX_HOST_CHUNK", 3 << 18, 1024, 1 << 26);
-    return chunk_ring(A, (size_t)n_vox, chunk, dev_env_int("PNX_HOST_SLOTS", 3, 2, 8), dev_env_int("PNX_HOST_KSTREAMS", 2, 1, 4), hg.touchers(),
-                      device, st, [&](size_t n, const DevSet &S, hipStream_t s) {
-                          return grid_match_device(D, (int64_t)n, S.d(GS_Y), S.d(GS_P0), (int32_t *)S.dev[GS_BEST], S.d(GS_COST), dev->cus, s);
-                      });
+    return ring_call(A, (size_t)n_vox, 3 << 18, device, st, [&](size_t n, const DevSet &S, hipStream_t s) {
+        return grid_match_device(D, (int64_t)n, S.d(GS_Y), S.d(GS_P0), (int32_t *)S.dev[GS_BEST], S.d(GS_COST), dev->cus, s);
+    });
 }
 
 int pnx_loglinear_f64(int64_t n_vox, int n_b, const double *b_host, const uint8_t *use_host, int weighting, int n_reweight, int clip,
@@ -1298,9 +1287,8 @@ int pnx_nnls_plan_create(pnx_nnls_plan **plan, int n_meas, int n_bins, const dou
     if (n_bins > kNnlsWideBins) return set_error(PNX_ERR_UNSUPPORTED, "n_bins=%d > %d", n_bins, kNnlsWideBins);
     if (n_meas > kNnlsMaxMeas) return set_error(PNX_ERR_UNSUPPORTED, "n_meas=%d > %d", n_meas, kNnlsMaxMeas);
     DeviceInfo *dev;
-    int rc = get_device(device, &dev);
+    int rc = use_device(device, &dev);
     if (rc) return rc;
-    PNX_HIP(hipSetDevice(device));
     pnx_nnls_plan *p = new pnx_nnls_plan();
     rc = nnls_plan_init(&p->d, n_meas, n_bins, basis, reg, n_reg, device, dev->cus);
     if (rc) {
@@ -1701,9 +1689,8 @@ int pnx_nnls_regularization_matrix(int n_bins, int order, double mu, double *reg
 int pnx_nnls_basis(int n_meas, const double *b, int n_bins, const double *bins, double *basis, int device) {
     if (!b || !bins || !basis || n_meas < 1 || n_bins < 1) return set_error(PNX_ERR_INVALID, "bad basis arguments");
     DeviceInfo *dev;
-    int rc = get_device(device, &dev);
+    int rc = use_device(device, &dev);
     if (rc) return rc;
-    PNX_HIP(hipSetDevice(device));
     return nnls_build_basis(n_meas, b, n_bins, bins, basis);
 }
 
@@ -1715,9 +1702,8 @@ static int bulk_copy(void *dst, const void *src, size_t bytes, bool to_device, i
     if (!bytes) return PNX_OK;
     if (!dst || !src) return set_error(PNX_ERR_INVALID, "NULL pointer");
     DeviceInfo *dev;
-    int rc = get_device(device, &dev);
+    int rc = use_device(device, &dev);
     if (rc) return rc;
-    PNX_HIP(hipSetDevice(device));
     PNX_HIP(hipStreamSynchronize(after));  // the producer of a device source / the last reader of a device destination
     const size_t piece = (size_t)env_int("PNX_COPY_PIECE_MB", 32, 1, 1024) << 20;
     const size_t n_pieces = (bytes + piece - 1) / piece;
@@ -1849,9 +1835,8 @@ extern "C" int pnx_label_sums_f64(const double *rows, const int32_t *labels, int
     const size_t lds = ((size_t)n_labels * c + n_labels) * sizeof(double);
     if (lds > 64 * 1024) return set_error(PNX_ERR_UNSUPPORTED, "n_labels * (c + 1) = %zu entries do not fit the 64 KB LDS table", lds / 8);
     DeviceInfo *dev;
-    int rc = get_device(device, &dev);
+    int rc = use_device(device, &dev);
     if (rc) return rc;
-    PNX_HIP(hipSetDevice(device));
     hipStream_t st = (hipStream_t)stream;
     const bool host = mem == PNX_MEM_HOST;
     const size_t tab = (size_t)n_labels * c;

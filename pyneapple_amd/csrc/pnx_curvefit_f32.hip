@@ -3,7 +3,7 @@
 #include <cstdio>
 
 #include "pnx_curvefit_f32_kernel.hpp"
-#include "pnx_internal.hpp"
+#include "pnx_launch.hpp"
 
 namespace pnx {
 namespace f32 {
@@ -30,15 +30,8 @@ template <int MODEL, bool PV> static int launch_one(const CurvefitF32Args &args,
     if (bytes(waves) > 160 * 1024) return set_error(PNX_ERR_UNSUPPORTED, "n_b=%d does not fit the LDS tile", args.n_b);
     const int block = waves * kWave;
     const size_t shmem = bytes(waves);
-    static bool attr_done[64] = {false};  // function attributes are per device
-    int cur_dev = 0;
-    (void)hipGetDevice(&cur_dev);
-    bool &attr_set = attr_done[cur_dev & 63];
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) return set_error(PNX_ERR_HIP, "hipFuncSetAttribute: %s", hipGetErrorString(e));
-        attr_set = true;
-    }
+    if (hipError_t ea = allow_big_lds<curvefit_f32_kernel<MODEL, PV>>(); ea != hipSuccess)
+        return set_error(PNX_ERR_HIP, "hipFuncSetAttribute: %s", hipGetErrorString(ea));
     int occ = 0;
     hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kern, block, shmem);
     if (e != hipSuccess || occ < 1) return set_error(PNX_ERR_HIP, "occupancy query failed (shmem=%zu): %s", shmem, hipGetErrorString(e));

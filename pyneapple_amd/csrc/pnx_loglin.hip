@@ -1,29 +1,21 @@
 // pnx_loglin.hip -- the log-linear mono-exponential fit ln S = ln S0 - b D per voxel (pnx_loglinear_f64 / _f32):
 // a closed form over one pass of the data, so a voxel costs its signal row in and its results out.
 //
-//   loglinear_kernel<T>   one lane per voxel, one wave and 64 voxels per block.  The block's (64, n_b) signal tile is contiguous in
-//                         memory but a lane's own row is n_b elements from its neighbour's, so it comes in as 16-byte lines, lane
-//                         after lane, into LDS ([voxel][n_b | 1] doubles: the odd row stride spreads the lanes' rows over the
-//                         banks), as model_predict_kernel's tile does.  A second tile of the same shape keeps log y: every later
-//                         pass -- the centred sums, the re-weighting passes, both residuals -- reads LDS and evaluates no
-//                         logarithm again.  b-values, mask and bounds are kernel arguments, read with scalar loads.
+//   loglinear_kernel<T>   one lane per voxel, one wave and 64 voxels per block.  The block's (64, n_b) signal tile comes into LDS
+//                         through the shared loader (pnx_tile.hpp: load_tile, [voxel][n_b | 1] doubles).  A second tile of the
+//                         same shape keeps log y: every later pass -- the centred sums (the line fit that every stage of
+//                         peel_kernel repeats), the re-weighting passes, both residuals -- reads LDS and evaluates no logarithm
+//                         again.  b-values, mask and bounds are kernel arguments, read with scalar loads.
 //                         T is the storage type (double / float); the tile and the arithmetic are fp64 for both.
 #include <hip/hip_runtime.h>
 
 #include <cstring>
 
-#include "pnx_internal.hpp"
+#include "pnx_launch.hpp"
 #include "pnx_loglin.hpp"
+#include "pnx_tile.hpp"
 
 namespace pnx {
-
-#define PNX_LL_HIP(call)                                                                           \
-    do {                                                                                           \
-        hipError_t e__ = (call);                                                                   \
-        if (e__ != hipSuccess) return set_error(PNX_ERR_HIP, "%s: %s", #call, hipGetErrorString(e__)); \
-    } while (0)
-
-constexpr int kLLWave = 64;
 
 template <typename T> struct LogLinArgs {
     LogLinOpts o;
@@ -36,23 +28,6 @@ template <typename T> struct LogLinArgs {
     long long n_vox;
 };
 
-template <typename T> struct Line16;  // 16 bytes of T
-template <> struct Line16<double> {
-    typedef __attribute__((ext_vector_type(2))) double type;
-    static constexpr int N = 2;
-};
-template <> struct Line16<float> {
-    typedef __attribute__((ext_vector_type(4))) float type;
-    static constexpr int N = 4;
-};
-
-__device__ __forceinline__ int ll_tile_at(int e, int n_b, float inv, int S) {  // element e of the (c, n_b) tile -> its LDS index
-    int q = (int)((float)e * inv);
-    q -= (q * n_b > e);
-    q += ((q + 1) * n_b <= e);
-    return q * S + (e - q * n_b);
-}
-
 // weight of a usable sample: 1, y^2, or exp(a - b D)^2 at the previous estimate (mode 2)
 __device__ __forceinline__ double ll_weight(int mode, double y, double b, double a, double D) {
     if (mode == 0) return 1.0;
@@ -61,30 +36,14 @@ __device__ __forceinline__ double ll_weight(int mode, double y, double b, double
     return e * e;
 }
 
-template <typename T> __global__ void __launch_bounds__(kLLWave) loglinear_kernel(const LogLinArgs<T> a) {
-    typedef typename Line16<T>::type line_t;
-    constexpr int V = Line16<T>::N;
+template <typename T> __global__ void __launch_bounds__(kTileRows) loglinear_kernel(const LogLinArgs<T> a) {
     extern __shared__ __attribute__((aligned(16))) double ll_tile[];  // y [64][S], then log y [64][S]
     const int lane = threadIdx.x, n_b = a.o.n_b, S = n_b | 1;
-    double *ty = ll_tile, *tl = ll_tile + kLLWave * S;
-    const long long v0 = (long long)blockIdx.x * kLLWave;
-    const int c = (a.n_vox - v0) < kLLWave ? (int)(a.n_vox - v0) : kLLWave;
+    double *ty = ll_tile, *tl = ll_tile + kTileRows * S;
+    const long long v0 = (long long)blockIdx.x * kTileRows;
+    const int c = (a.n_vox - v0) < kTileRows ? (int)(a.n_vox - v0) : kTileRows;
     const int n_el = c * n_b;
-    const T *src = a.y + (size_t)v0 * n_b;  // v0 is a multiple of 64: as aligned as y itself
-    const float inv = 1.0f / (float)n_b;
-    if (((uintptr_t)a.y & 15) == 0) {
-        for (int e = V * lane; e < n_el; e += V * kLLWave) {
-            if (e + V <= n_el) {
-                const line_t v = __builtin_nontemporal_load(reinterpret_cast<const line_t *>(src + e));
-#pragma unroll
-                for (int k = 0; k < V; ++k) ty[ll_tile_at(e + k, n_b, inv, S)] = (double)v[k];
-            } else {
-                for (int k = e; k < n_el; ++k) ty[ll_tile_at(k, n_b, inv, S)] = (double)src[k];
-            }
-        }
-    } else {
-        for (int e = lane; e < n_el; e += kLLWave) ty[ll_tile_at(e, n_b, inv, S)] = (double)src[e];
-    }
+    load_tile(ty, a.y, v0, n_el, n_b, lane);
     __syncthreads();
     const int rl = lane < c ? lane : c - 1;  // lanes past the end repeat the last voxel, never stored
     const double *my = ty + rl * S;
@@ -198,14 +157,8 @@ template <typename T>
 int loglinear_device(const LogLinOpts &o, int64_t n_vox, const T *y_d, T *params_d, T *pcov_d, int8_t *status_d, int32_t *n_used_d,
                      T *ss_res_d, hipStream_t stream) {
     if (n_vox <= 0) return PNX_OK;
-    static bool attr_done[64] = {false};
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (!attr_done[dev & 63]) {
-        PNX_LL_HIP(hipFuncSetAttribute((const void *)loglinear_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        attr_done[dev & 63] = true;
-    }
-    const long long blocks = (n_vox + kLLWave - 1) / kLLWave;
+    PNX_ALLOW_BIG_LDS(loglinear_kernel<T>);
+    const long long blocks = (n_vox + kTileRows - 1) / kTileRows;
     if (blocks > 0x7fffffffLL) return set_error(PNX_ERR_UNSUPPORTED, "loglinear: n_vox=%lld in one launch", (long long)n_vox);
     LogLinArgs<T> a;
     memset(&a, 0, sizeof(a));
@@ -217,8 +170,8 @@ int loglinear_device(const LogLinOpts &o, int64_t n_vox, const T *y_d, T *params
     a.n_used = n_used_d;
     a.ss = ss_res_d;
     a.n_vox = n_vox;
-    hipLaunchKernelGGL((loglinear_kernel<T>), dim3((unsigned)blocks), dim3(kLLWave), loglin_lds_bytes(o.n_b), stream, a);
-    PNX_LL_HIP(hipGetLastError());
+    hipLaunchKernelGGL((loglinear_kernel<T>), dim3((unsigned)blocks), dim3(kTileRows), loglin_lds_bytes(o.n_b), stream, a);
+    PNX_HIP(hipGetLastError());
     return PNX_OK;
 }
 

@@ -3,16 +3,10 @@
 // pnx_grid_args.hpp: pnx_api.hip and pnx_loglin.hip use it, tests/host_stub/loglin_args_stub.cpp builds the same code for the
 // CPU under AddressSanitizer / UBSan.
 #pragma once
-#include <cmath>
-#include <cstddef>
-#include <cstdint>
-
-#include "../../include/pnx.h"
+#include "pnx_args_common.hpp"
+#include "pnx_tile.hpp"
 
 namespace pnx {
-// records a printf-style message for pnx_last_error() and returns `code` (pnx_api.hip; the stub defines its own)
-int set_error(int code, const char *fmt, ...) __attribute__((format(printf, 2, 3)));
-
 constexpr int kLogLinMaxReweight = 8;
 
 // What a call hands the kernel by value: 1 KB of b-values, 128 mask bits, the switches and the clip bounds.
@@ -36,36 +30,20 @@ inline int loglin_check_args(int64_t n_vox, int n_b, const T *b, const uint8_t *
     if (!b) return set_error(PNX_ERR_INVALID, "loglinear: b is NULL");
     if (n_vox && !y) return set_error(PNX_ERR_INVALID, "loglinear: y is NULL");
     if (n_vox && !params) return set_error(PNX_ERR_INVALID, "loglinear: params is NULL");
-    for (int i = 0; i < n_b; ++i)
-        if (!std::isfinite((double)b[i])) return set_error(PNX_ERR_INVALID, "loglinear: b[%d] is not finite", i);
-    if (weighting != 0 && weighting != 1) return set_error(PNX_ERR_INVALID, "loglinear: weighting=%d (0: none, 1: signal^2)", weighting);
+    int rc;
+    if ((rc = args_check_b("loglinear", n_b, b)) || (rc = args_check_weighting("loglinear", weighting))) return rc;
     if (n_reweight < 0 || n_reweight > kLogLinMaxReweight)
         return set_error(PNX_ERR_INVALID, "loglinear: n_reweight=%d out of range [0,%d]", n_reweight, kLogLinMaxReweight);
-    int kept = 0, first = -1;
-    bool distinct = false;
-    for (int i = 0; i < n_b; ++i) {
-        if (use && !use[i]) continue;
-        if (first < 0) first = i;
-        distinct = distinct || b[i] != b[first];
-        ++kept;
-    }
-    if (kept < 2) return set_error(PNX_ERR_INVALID, "loglinear: use keeps %d of %d b-values, a line needs 2", kept, n_b);
-    if (!distinct) return set_error(PNX_ERR_INVALID, "loglinear: the b-values that use keeps are all equal (%g), a line needs 2 distinct ones", (double)b[first]);
-    if (clip) {
-        if (!lo || !hi) return set_error(PNX_ERR_INVALID, "loglinear: clip needs lo and hi, got NULL");
-        for (int k = 0; k < 2; ++k)
-            if (!((double)lo[k] < (double)hi[k]))
-                return set_error(PNX_ERR_INVALID, "loglinear: clip needs lo[%d] < hi[%d], got %g and %g", k, k, (double)lo[k], (double)hi[k]);
-    }
-    if (mem != PNX_MEM_HOST && mem != PNX_MEM_DEVICE) return set_error(PNX_ERR_INVALID, "loglinear: mem=%d", mem);
+    const MaskRow m = args_mask_row(n_b, b, use);
+    if (m.kept < 2) return set_error(PNX_ERR_INVALID, "loglinear: use keeps %d of %d b-values, a line needs 2", m.kept, n_b);
+    if (!m.distinct) return set_error(PNX_ERR_INVALID, "loglinear: the b-values that use keeps are all equal (%g), a line needs 2 distinct ones", (double)b[m.first]);
+    if ((rc = args_check_clip("loglinear", clip, 2, lo, hi)) || (rc = args_check_mem("loglinear", mem))) return rc;
     o->n_b = n_b;
     o->weighting = weighting;
     o->n_reweight = n_reweight;
     o->clip = clip != 0;
-    for (int k = 0; k < PNX_MAX_BVALUES / 64; ++k) o->use[k] = 0;
-    for (int i = 0; i < PNX_MAX_BVALUES; ++i) o->b[i] = i < n_b ? (double)b[i] : 0.0;
-    for (int i = 0; i < n_b; ++i)
-        if (!use || use[i]) o->use[i >> 6] |= 1ull << (i & 63);
+    args_pack_mask(n_b, use, o->use);
+    args_copy_b(n_b, b, o->b);
     for (int k = 0; k < 2; ++k) {
         o->lo[k] = clip ? (double)lo[k] : 0.0;
         o->hi[k] = clip ? (double)hi[k] : 0.0;
@@ -73,7 +51,6 @@ inline int loglin_check_args(int64_t n_vox, int n_b, const T *b, const uint8_t *
     return PNX_OK;
 }
 
-// LDS of one block: the signal tile and its logarithms, [64][n_b | 1] doubles each (the odd row stride spreads a wave's rows over
-// the banks); 132 KB at 128 b-values, inside a workgroup's 160 KB.
-inline size_t loglin_lds_bytes(int n_b) { return (size_t)2 * 64 * (size_t)(n_b | 1) * sizeof(double); }
+// LDS of one block: the signal tile and its logarithms (pnx_tile.hpp); 132 KB at 128 b-values, inside a workgroup's 160 KB.
+inline size_t loglin_lds_bytes(int n_b) { return tile_lds_bytes(2, n_b); }
 }  // namespace pnx

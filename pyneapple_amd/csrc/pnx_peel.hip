@@ -2,31 +2,24 @@
 // _f32): K log-linear stages, the slowest compartment first, each on its own b-values and on what the stages
 // before left of the signal.  A closed form: a voxel costs its signal row in and its results out.
 //
-//   peel_kernel<T>   one lane per voxel, one wave and 64 voxels per block.  The block's (64, n_b) signal tile comes in as 16-byte
-//                    lines into LDS ([voxel][n_b | 1] doubles, the odd row stride spreads the lanes' rows over the banks), as
-//                    loglinear_kernel's does.  A second tile of the same shape holds the running residual r, one row per lane:
-//                    a stage reads it twice (the weighted means, then the centred sums) and rewrites it once.  y itself stays for
-//                    ss_res.  Two tiles are 132 KB at 128 b-values and a third does not fit, so no logarithm is kept at any n_b:
-//                    both passes of a stage evaluate log r (the same instruction sequence on the same value, hence the same
-//                    bits).  Per stage only A_k, D_k and n_used stay in registers.  b-values, the K masks, bounds and fallback
-//                    are kernel arguments, read with scalar loads.
+//   peel_kernel<T>   one lane per voxel, one wave and 64 voxels per block.  The block's (64, n_b) signal tile comes into LDS
+//                    through the shared loader (pnx_tile.hpp: load_tile, [voxel][n_b | 1] doubles).  A second tile of the same
+//                    shape holds the running residual r, one row per lane: a stage reads it twice (the weighted means, then
+//                    the centred sums: loglinear_kernel's line fit, operation for operation) and rewrites it once.  y itself
+//                    stays for ss_res.  Two tiles are 132 KB at 128 b-values and a third does not fit, so no logarithm is kept at
+//                    any n_b: both passes of a stage evaluate log r (the same instruction sequence on the same value, hence the
+//                    same bits).  Per stage only A_k, D_k and n_used stay in registers.  b-values, the K masks, bounds and
+//                    fallback are kernel arguments, read with scalar loads.
 //                    T is the storage type (double / float); the tiles and the arithmetic are fp64 for both.
 #include <hip/hip_runtime.h>
 
 #include <cstring>
 
-#include "pnx_internal.hpp"
+#include "pnx_launch.hpp"
 #include "pnx_peel.hpp"
+#include "pnx_tile.hpp"
 
 namespace pnx {
-
-#define PNX_PEEL_HIP(call)                                                                         \
-    do {                                                                                           \
-        hipError_t e__ = (call);                                                                   \
-        if (e__ != hipSuccess) return set_error(PNX_ERR_HIP, "%s: %s", #call, hipGetErrorString(e__)); \
-    } while (0)
-
-constexpr int kPeelWave = 64;
 
 template <typename T> struct PeelArgs {
     PeelOpts o;
@@ -38,47 +31,14 @@ template <typename T> struct PeelArgs {
     long long n_vox;
 };
 
-template <typename T> struct PeelLine16;  // 16 bytes of T
-template <> struct PeelLine16<double> {
-    typedef __attribute__((ext_vector_type(2))) double type;
-    static constexpr int N = 2;
-};
-template <> struct PeelLine16<float> {
-    typedef __attribute__((ext_vector_type(4))) float type;
-    static constexpr int N = 4;
-};
-
-__device__ __forceinline__ int peel_tile_at(int e, int n_b, float inv, int S) {  // element e of the (c, n_b) tile -> its LDS index
-    int q = (int)((float)e * inv);
-    q -= (q * n_b > e);
-    q += ((q + 1) * n_b <= e);
-    return q * S + (e - q * n_b);
-}
-
-template <typename T> __global__ void __launch_bounds__(kPeelWave) peel_kernel(const PeelArgs<T> a) {
-    typedef typename PeelLine16<T>::type line_t;
-    constexpr int V = PeelLine16<T>::N;
+template <typename T> __global__ void __launch_bounds__(kTileRows) peel_kernel(const PeelArgs<T> a) {
     extern __shared__ __attribute__((aligned(16))) double peel_tile[];  // y [64][S], then r [64][S]
     const int lane = threadIdx.x, n_b = a.o.n_b, S = n_b | 1, K = a.o.n_stage;
-    double *ty = peel_tile, *tr = peel_tile + kPeelWave * S;
-    const long long v0 = (long long)blockIdx.x * kPeelWave;
-    const int c = (a.n_vox - v0) < kPeelWave ? (int)(a.n_vox - v0) : kPeelWave;
+    double *ty = peel_tile, *tr = peel_tile + kTileRows * S;
+    const long long v0 = (long long)blockIdx.x * kTileRows;
+    const int c = (a.n_vox - v0) < kTileRows ? (int)(a.n_vox - v0) : kTileRows;
     const int n_el = c * n_b;
-    const T *src = a.y + (size_t)v0 * n_b;  // v0 is a multiple of 64: as aligned as y itself
-    const float inv = 1.0f / (float)n_b;
-    if (((uintptr_t)a.y & 15) == 0) {
-        for (int e = V * lane; e < n_el; e += V * kPeelWave) {
-            if (e + V <= n_el) {
-                const line_t v = __builtin_nontemporal_load(reinterpret_cast<const line_t *>(src + e));
-#pragma unroll
-                for (int k = 0; k < V; ++k) ty[peel_tile_at(e + k, n_b, inv, S)] = (double)v[k];
-            } else {
-                for (int k = e; k < n_el; ++k) ty[peel_tile_at(k, n_b, inv, S)] = (double)src[k];
-            }
-        }
-    } else {
-        for (int e = lane; e < n_el; e += kPeelWave) ty[peel_tile_at(e, n_b, inv, S)] = (double)src[e];
-    }
+    load_tile(ty, a.y, v0, n_el, n_b, lane);
     __syncthreads();
     const int rl = lane < c ? lane : c - 1;  // lanes past the end repeat the last voxel, never stored
     const double *my = ty + rl * S;
@@ -214,14 +174,8 @@ template <typename T>
 int peel_device(const PeelOpts &o, int64_t n_vox, const T *y_d, T *params_d, int8_t *status_d, int32_t *n_used_d, T *ss_res_d,
                 hipStream_t stream) {
     if (n_vox <= 0) return PNX_OK;
-    static bool attr_done[64] = {false};
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (!attr_done[dev & 63]) {
-        PNX_PEEL_HIP(hipFuncSetAttribute((const void *)peel_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        attr_done[dev & 63] = true;
-    }
-    const long long blocks = (n_vox + kPeelWave - 1) / kPeelWave;
+    PNX_ALLOW_BIG_LDS(peel_kernel<T>);
+    const long long blocks = (n_vox + kTileRows - 1) / kTileRows;
     if (blocks > 0x7fffffffLL) return set_error(PNX_ERR_UNSUPPORTED, "peel: n_vox=%lld in one launch", (long long)n_vox);
     PeelArgs<T> a;
     memset(&a, 0, sizeof(a));
@@ -232,8 +186,8 @@ int peel_device(const PeelOpts &o, int64_t n_vox, const T *y_d, T *params_d, int
     a.n_used = n_used_d;
     a.ss = ss_res_d;
     a.n_vox = n_vox;
-    hipLaunchKernelGGL((peel_kernel<T>), dim3((unsigned)blocks), dim3(kPeelWave), peel_lds_bytes(o.n_b), stream, a);
-    PNX_PEEL_HIP(hipGetLastError());
+    hipLaunchKernelGGL((peel_kernel<T>), dim3((unsigned)blocks), dim3(kTileRows), peel_lds_bytes(o.n_b), stream, a);
+    PNX_HIP(hipGetLastError());
     return PNX_OK;
 }
 

@@ -3,16 +3,10 @@
 // types, like pnx_loglin_args.hpp: pnx_api.hip and pnx_peel.hip use it, tests/host_stub/peel_args_stub.cpp builds the same code
 // for the CPU under AddressSanitizer / UBSan.
 #pragma once
-#include <cmath>
-#include <cstddef>
-#include <cstdint>
-
-#include "../../include/pnx.h"
+#include "pnx_args_common.hpp"
+#include "pnx_tile.hpp"
 
 namespace pnx {
-// records a printf-style message for pnx_last_error() and returns `code` (pnx_api.hip; the stub defines its own)
-int set_error(int code, const char *fmt, ...) __attribute__((format(printf, 2, 3)));
-
 constexpr int kPeelMaxStages = 3;
 constexpr int kPeelMaxParams = 6;
 
@@ -53,31 +47,16 @@ inline int peel_check_args(int model, int64_t n_vox, int n_b, const T *b, const 
     if (!use) return set_error(PNX_ERR_INVALID, "peel: use is NULL");
     if (n_vox && !y) return set_error(PNX_ERR_INVALID, "peel: y is NULL");
     if (n_vox && !params) return set_error(PNX_ERR_INVALID, "peel: params is NULL");
-    for (int i = 0; i < n_b; ++i)
-        if (!std::isfinite((double)b[i])) return set_error(PNX_ERR_INVALID, "peel: b[%d] is not finite", i);
-    if (weighting != 0 && weighting != 1) return set_error(PNX_ERR_INVALID, "peel: weighting=%d (0: none, 1: signal^2)", weighting);
+    int rc;
+    if ((rc = args_check_b("peel", n_b, b)) || (rc = args_check_weighting("peel", weighting))) return rc;
     for (int k = 0; k < K; ++k) {
-        const uint8_t *row = use + (size_t)k * n_b;
-        int kept = 0, first = -1;
-        bool distinct = false;
-        for (int i = 0; i < n_b; ++i) {
-            if (!row[i]) continue;
-            if (first < 0) first = i;
-            distinct = distinct || b[i] != b[first];
-            ++kept;
-        }
-        if (kept < 2) return set_error(PNX_ERR_INVALID, "peel: use row %d keeps %d of %d b-values, a line needs 2", k, kept, n_b);
-        if (!distinct)
+        const MaskRow m = args_mask_row(n_b, b, use + (size_t)k * n_b);
+        if (m.kept < 2) return set_error(PNX_ERR_INVALID, "peel: use row %d keeps %d of %d b-values, a line needs 2", k, m.kept, n_b);
+        if (!m.distinct)
             return set_error(PNX_ERR_INVALID, "peel: the b-values that use row %d keeps are all equal (%g), a line needs 2 distinct ones", k,
-                             (double)b[first]);
+                             (double)b[m.first]);
     }
-    if (clip) {
-        if (!lo || !hi) return set_error(PNX_ERR_INVALID, "peel: clip needs lo and hi, got NULL");
-        for (int j = 0; j < np; ++j)
-            if (!((double)lo[j] < (double)hi[j]))
-                return set_error(PNX_ERR_INVALID, "peel: clip needs lo[%d] < hi[%d], got %g and %g", j, j, (double)lo[j], (double)hi[j]);
-    }
-    if (mem != PNX_MEM_HOST && mem != PNX_MEM_DEVICE) return set_error(PNX_ERR_INVALID, "peel: mem=%d", mem);
+    if ((rc = args_check_clip("peel", clip, np, lo, hi)) || (rc = args_check_mem("peel", mem))) return rc;
     o->model = model;
     o->n_stage = K;
     o->n_params = np;
@@ -85,12 +64,9 @@ inline int peel_check_args(int model, int64_t n_vox, int n_b, const T *b, const 
     o->weighting = weighting;
     o->clip = clip != 0;
     o->has_fallback = fallback != nullptr;
-    for (int k = 0; k < kPeelMaxStages; ++k)
-        for (int q = 0; q < PNX_MAX_BVALUES / 64; ++q) o->use[k][q] = 0;
-    for (int k = 0; k < K; ++k)
-        for (int i = 0; i < n_b; ++i)
-            if (use[(size_t)k * n_b + i]) o->use[k][i >> 6] |= 1ull << (i & 63);
-    for (int i = 0; i < PNX_MAX_BVALUES; ++i) o->b[i] = i < n_b ? (double)b[i] : 0.0;
+    for (int k = 0; k < kPeelMaxStages; ++k)  // the rows past K: no bits
+        args_pack_mask(k < K ? n_b : 0, k < K ? use + (size_t)k * n_b : nullptr, o->use[k]);
+    args_copy_b(n_b, b, o->b);
     for (int j = 0; j < kPeelMaxParams; ++j) {
         const bool in = j < np;
         o->lo[j] = clip && in ? (double)lo[j] : 0.0;
@@ -100,8 +76,8 @@ inline int peel_check_args(int model, int64_t n_vox, int n_b, const T *b, const 
     return PNX_OK;
 }
 
-// LDS of one block: the signal tile and the running residual, [64][n_b | 1] doubles each (the odd row stride spreads a wave's rows
-// over the banks); 132 KB at 128 b-values, inside a workgroup's 160 KB.  A third tile for the logarithms would not fit there, so
-// the kernel keeps none at any n_b and evaluates the logarithm in both passes of a stage.
-inline size_t peel_lds_bytes(int n_b) { return (size_t)2 * 64 * (size_t)(n_b | 1) * sizeof(double); }
+// LDS of one block: the signal tile and the running residual (pnx_tile.hpp); 132 KB at 128 b-values, inside a workgroup's 160 KB.
+// A third tile for the logarithms would not fit there, so the kernel keeps none at any n_b and evaluates the logarithm in both
+// passes of a stage.
+inline size_t peel_lds_bytes(int n_b) { return tile_lds_bytes(2, n_b); }
 }  // namespace pnx

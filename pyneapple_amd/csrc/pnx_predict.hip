@@ -11,9 +11,10 @@
 #include <cstring>
 
 #include "pnx_curvefit_kernel.hpp"
-#include "pnx_internal.hpp"
+#include "pnx_launch.hpp"
 #include "pnx_nnls.hpp"
 #include "pnx_predict.hpp"
+#include "pnx_tile.hpp"
 
 namespace pnx {
 
@@ -123,7 +124,7 @@ static int launch_stats(const NnlsPlanData *P, int64_t n_vox, const double *y, c
     if (blocks > cap) blocks = cap;
     hipLaunchKernelGGL((nnls_fit_stats_kernel<NT, VEC>), dim3((unsigned)blocks), dim3(kStatsWaves * 64), lds, st, x, y, P->Bp, ss, pred,
                        (long long)n_vox, P->n_bins, P->n_meas, P->bstride);
-    PNX_HIPN(hipGetLastError());
+    PNX_HIP(hipGetLastError());
     return PNX_OK;
 }
 
@@ -140,10 +141,9 @@ int nnls_fit_stats_device(const NnlsPlanData *P, int64_t n_vox, const double *y_
 }
 
 // ---- parametric models: one lane per voxel ----------------------------------------------------------------------------------
-// A block is one wave and 64 voxels.  The (64, n_x) tile of the output is contiguous in memory but a lane's own row is
-// 8 n_x bytes from its neighbour's, so the tile goes through LDS ([voxel][n_x | 1]: the odd row stride spreads the lanes' writes
-// over the banks) and leaves as 16-byte lines, lane after lane; a signal tile comes in the same way.  The x-values are kernel
-// arguments, read with scalar loads (one table for the whole grid, as the fit's b-values).
+// A block is one wave and 64 voxels.  The (64, n_x) tile of the output goes through LDS and leaves as 16-byte lines, lane after
+// lane (pnx_tile.hpp: store_tile, [voxel][n_x | 1] doubles); a signal tile comes in the same way (load_tile).  The x-values are
+// kernel arguments, read with scalar loads (one table for the whole grid, as the fit's b-values).
 struct PredictArgs {
     const double *params;  // (n_free, n_vox)
     const double *fixed;   // (n_fixed, n_vox) when fixed_pv
@@ -161,13 +161,7 @@ struct PredictArgs {
     double x[kMaxB];
 };
 
-__device__ __forceinline__ int tile_at(int e, int n_x, float inv, int S) {  // element e of the (c, n_x) tile -> its LDS index
-    int q = (int)((float)e * inv);
-    q -= (q * n_x > e);
-    q += ((q + 1) * n_x <= e);
-    return q * S + (e - q * n_x);
-}
-
+static_assert(kWave == kTileRows, "a block of model_predict_kernel is the tile helpers' one wave");
 template <int MODEL, bool T1>
 __global__ void __launch_bounds__(kWave) model_predict_kernel(const PredictArgs a) {
     using M = Model<MODEL>;
@@ -177,23 +171,8 @@ __global__ void __launch_bounds__(kWave) model_predict_kernel(const PredictArgs 
     const long long v0 = (long long)blockIdx.x * kWave;
     const int c = (a.n_vox - v0) < kWave ? (int)(a.n_vox - v0) : kWave;
     const int n_el = c * n_x;
-    const size_t g0 = (size_t)v0 * n_x;  // even: v0 is a multiple of 64
-    const float inv = 1.0f / (float)n_x;
     if (a.y) {
-        const double *src = a.y + g0;
-        if (((uintptr_t)a.y & 15) == 0) {
-            for (int e = 2 * lane; e < n_el; e += 2 * kWave) {
-                if (e + 1 < n_el) {
-                    const f64x2 v = __builtin_nontemporal_load(reinterpret_cast<const f64x2 *>(src + e));
-                    tile[tile_at(e, n_x, inv, S)] = v.x;
-                    tile[tile_at(e + 1, n_x, inv, S)] = v.y;
-                } else {
-                    tile[tile_at(e, n_x, inv, S)] = src[e];
-                }
-            }
-        } else {
-            for (int e = lane; e < n_el; e += kWave) tile[tile_at(e, n_x, inv, S)] = src[e];
-        }
+        load_tile(tile, a.y, v0, n_el, n_x, lane);
         __syncthreads();
     }
     const size_t v = (size_t)v0 + (lane < c ? lane : c - 1);  // lanes past the end repeat the last voxel, never stored
@@ -227,37 +206,17 @@ __global__ void __launch_bounds__(kWave) model_predict_kernel(const PredictArgs 
     if (a.ss && lane < c) a.ss[v] = ss;
     if (a.pred) {
         __syncthreads();
-        double *dst = a.pred + g0;
-        if (((uintptr_t)a.pred & 15) == 0) {
-            for (int e = 2 * lane; e < n_el; e += 2 * kWave) {
-                if (e + 1 < n_el) {
-                    f64x2 o;
-                    o.x = tile[tile_at(e, n_x, inv, S)];
-                    o.y = tile[tile_at(e + 1, n_x, inv, S)];
-                    __builtin_nontemporal_store(o, reinterpret_cast<f64x2 *>(dst + e));
-                } else {
-                    dst[e] = tile[tile_at(e, n_x, inv, S)];
-                }
-            }
-        } else {
-            for (int e = lane; e < n_el; e += kWave) dst[e] = tile[tile_at(e, n_x, inv, S)];
-        }
+        store_tile(a.pred, v0, tile, n_el, n_x, lane);
     }
 }
 
 template <int MODEL, bool T1> static int launch_predict(const PredictArgs &a, hipStream_t st) {
-    static bool attr_done[64] = {false};
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (!attr_done[dev & 63]) {
-        PNX_HIPN(hipFuncSetAttribute((const void *)model_predict_kernel<MODEL, T1>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        attr_done[dev & 63] = true;
-    }
-    const size_t lds = (size_t)kWave * (a.n_x | 1) * sizeof(double);  // 66 KB at 128 x-values
+    PNX_ALLOW_BIG_LDS(model_predict_kernel<MODEL, T1>);
+    const size_t lds = tile_lds_bytes(1, a.n_x);  // 66 KB at 128 x-values
     const long long blocks = (a.n_vox + kWave - 1) / kWave;
     if (blocks > 0x7fffffffLL) return set_error(PNX_ERR_UNSUPPORTED, "predict: n_vox=%lld in one launch", a.n_vox);
     hipLaunchKernelGGL((model_predict_kernel<MODEL, T1>), dim3((unsigned)blocks), dim3(kWave), lds, st, a);
-    PNX_HIPN(hipGetLastError());
+    PNX_HIP(hipGetLastError());
     return PNX_OK;
 }
 

@@ -21,18 +21,12 @@
 #include <hipcub/hipcub.hpp>
 
 #include "pnx_curvefit_kernel.hpp"
-#include "pnx_internal.hpp"
+#include "pnx_launch.hpp"
 #include "pnx_simplex.hpp"
 
 namespace pnx {
 
 using f64x2 = __attribute__((ext_vector_type(2))) double;
-
-#define SX_HIP(call)                                                                                 \
-    do {                                                                                             \
-        hipError_t e__ = (call);                                                                     \
-        if (e__ != hipSuccess) return set_error(PNX_ERR_HIP, "%s: %s", #call, hipGetErrorString(e__)); \
-    } while (0)
 
 struct StreamBuf {  // stream-ordered scratch, freed behind the work that uses it
     void *p = nullptr;
@@ -90,12 +84,12 @@ int simplex_select(const double *popt_d, int64_t n_vox, const int8_t *status_d, 
     StreamBuf head, tmp;
     if (int rc = head.alloc(sizeof(Head), st)) return rc;
     Head *hd = (Head *)head.p;
-    SX_HIP(hipMemsetAsync(hd, 0xff, sizeof(Head), st));  // min_nfev = UINT_MAX
+    PNX_HIP(hipMemsetAsync(hd, 0xff, sizeof(Head), st));  // min_nfev = UINT_MAX
     size_t blocks = ((size_t)n_vox + 255) / 256;
     if (blocks > 16384) blocks = 16384;
     hipLaunchKernelGGL(simplex_classify_kernel, dim3((unsigned)blocks), dim3(256), 0, st, popt_d, popt_d + 2 * (size_t)n_vox, status_d,
                        nfev_d, (long long)n_vox, flags_d, lambda_d, face_d, &hd->min_nfev);
-    SX_HIP(hipGetLastError());
+    PNX_HIP(hipGetLastError());
     // hipCUB takes an int count: calls beyond 2^30 voxels are cut into pieces (as pnx_mask_select_f64 does)
     const FlagSet pred{flags_d};
     long long total = 0;
@@ -106,16 +100,16 @@ int simplex_select(const double *popt_d, int64_t n_vox, const int8_t *status_d, 
         const int m = (int)((n_vox - off) < piece ? (n_vox - off) : piece);
         hipcub::CountingInputIterator<long long> it(off);
         size_t need = 0;
-        SX_HIP(hipcub::DeviceSelect::If(nullptr, need, it, (long long *)idx_d + total, &hd->count, m, pred, st));
+        PNX_HIP(hipcub::DeviceSelect::If(nullptr, need, it, (long long *)idx_d + total, &hd->count, m, pred, st));
         if (!tmp.p || need > bytes) {
             if (tmp.p) (void)hipFreeAsync(tmp.p, st);
             tmp.p = nullptr;
             if (int rc = tmp.alloc(need, st)) return rc;
             bytes = need;
         }
-        SX_HIP(hipcub::DeviceSelect::If(tmp.p, need, it, (long long *)idx_d + total, &hd->count, m, pred, st));
-        SX_HIP(hipMemcpyAsync(&h, hd, sizeof(Head), hipMemcpyDeviceToHost, st));
-        SX_HIP(hipStreamSynchronize(st));
+        PNX_HIP(hipcub::DeviceSelect::If(tmp.p, need, it, (long long *)idx_d + total, &hd->count, m, pred, st));
+        PNX_HIP(hipMemcpyAsync(&h, hd, sizeof(Head), hipMemcpyDeviceToHost, st));
+        PNX_HIP(hipStreamSynchronize(st));
         total += h.count;
     }
     *n_viol = total;
@@ -203,23 +197,17 @@ __global__ void __launch_bounds__(kWave) simplex_gather_kernel(const GatherArgs 
     }
 }
 
-template <typename K> static int allow_big_lds(K kern, bool *done) {
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (!done[dev & 63]) {
-        SX_HIP(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        done[dev & 63] = true;
-    }
+template <auto kern> static int allow_big_lds_of() {
+    PNX_ALLOW_BIG_LDS(kern);
     return PNX_OK;
 }
 
 template <bool S0> static int launch_gather(const GatherArgs &a, hipStream_t st) {
-    static bool attr_done[64] = {false};
-    if (int rc = allow_big_lds(simplex_gather_kernel<S0>, attr_done)) return rc;
+    if (int rc = allow_big_lds_of<simplex_gather_kernel<S0>>()) return rc;
     const size_t lds = (size_t)kWave * a.n_b * sizeof(double);  // 64 KB at 128 b-values
     const long long blocks = (a.m + kWave - 1) / kWave;
     hipLaunchKernelGGL((simplex_gather_kernel<S0>), dim3((unsigned)blocks), dim3(kWave), lds, st, a);
-    SX_HIP(hipGetLastError());
+    PNX_HIP(hipGetLastError());
     return PNX_OK;
 }
 
@@ -348,12 +336,11 @@ __global__ void __launch_bounds__(kWave) simplex_merge_kernel(const MergeArgs a)
 }
 
 template <int MODEL> static int launch_merge(const MergeArgs &a, hipStream_t st) {
-    static bool attr_done[64] = {false};
-    if (int rc = allow_big_lds(simplex_merge_kernel<MODEL>, attr_done)) return rc;
+    if (int rc = allow_big_lds_of<simplex_merge_kernel<MODEL>>()) return rc;
     const size_t lds = (size_t)kWave * (a.n_b | 1) * sizeof(double);  // 66 KB at 128 b-values
     const long long blocks = (a.m + kWave - 1) / kWave;
     hipLaunchKernelGGL((simplex_merge_kernel<MODEL>), dim3((unsigned)blocks), dim3(kWave), lds, st, a);
-    SX_HIP(hipGetLastError());
+    PNX_HIP(hipGetLastError());
     return PNX_OK;
 }
 

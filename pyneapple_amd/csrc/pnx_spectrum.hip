@@ -23,7 +23,7 @@
 
 #include <cmath>
 
-#include "pnx_internal.hpp"
+#include "pnx_launch.hpp"
 
 namespace pnx {
 namespace {
@@ -431,12 +431,6 @@ struct DevTmp {
 }  // namespace
 }  // namespace pnx
 
-#define PNX_HIPS(call)                                                                                    \
-    do {                                                                                                  \
-        hipError_t e__ = (call);                                                                          \
-        if (e__ != hipSuccess) return pnx::set_error(PNX_ERR_HIP, "%s: %s", #call, hipGetErrorString(e__)); \
-    } while (0)
-
 extern "C" {
 
 int pnx_nnls_spectrum_peaks_f64(int64_t n_vox, int n_bins, const double *spectrum, const double *bins_host, double height,
@@ -456,10 +450,10 @@ int pnx_nnls_spectrum_peaks_f64(int64_t n_vox, int n_bins, const double *spectru
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return set_error(PNX_ERR_NO_DEVICE, "no HIP device visible");
     if (device < 0 || device >= ndev) return set_error(PNX_ERR_INVALID, "device %d out of range", device);
-    PNX_HIPS(hipSetDevice(device));
+    PNX_HIP(hipSetDevice(device));
     hipStream_t st = (hipStream_t)stream;
     hipDeviceProp_t prop;
-    PNX_HIPS(hipGetDeviceProperties(&prop, device));
+    PNX_HIP(hipGetDeviceProperties(&prop, device));
 
     DevTmp dspec, dnp, dd, df, ddc, dfc;
     PeakArgs a;
@@ -483,24 +477,24 @@ int pnx_nnls_spectrum_peaks_f64(int64_t n_vox, int n_bins, const double *spectru
         a.d_cut = n_cut ? d_cut : nullptr;
         a.f_cut = f_cut;
     } else {
-        PNX_HIPS(hipMalloc(&dspec.p, nv * n_bins * sizeof(double)));
-        PNX_HIPS(hipMemcpyAsync(dspec.p, spectrum, nv * n_bins * sizeof(double), hipMemcpyHostToDevice, st));
+        PNX_HIP(hipMalloc(&dspec.p, nv * n_bins * sizeof(double)));
+        PNX_HIP(hipMemcpyAsync(dspec.p, spectrum, nv * n_bins * sizeof(double), hipMemcpyHostToDevice, st));
         a.spec = (const double *)dspec.p;
         a.n_peaks = nullptr;
         if (n_peaks) {
-            PNX_HIPS(hipMalloc(&dnp.p, nv * sizeof(int32_t)));
+            PNX_HIP(hipMalloc(&dnp.p, nv * sizeof(int32_t)));
             a.n_peaks = (int32_t *)dnp.p;
         }
         a.d_values = a.f_values = a.d_cut = a.f_cut = nullptr;
         if (max_peaks) {
-            PNX_HIPS(hipMalloc(&dd.p, nv * max_peaks * sizeof(double)));
-            PNX_HIPS(hipMalloc(&df.p, nv * max_peaks * sizeof(double)));
+            PNX_HIP(hipMalloc(&dd.p, nv * max_peaks * sizeof(double)));
+            PNX_HIP(hipMalloc(&df.p, nv * max_peaks * sizeof(double)));
             a.d_values = (double *)dd.p;
             a.f_values = (double *)df.p;
         }
         if (n_cut) {
-            PNX_HIPS(hipMalloc(&ddc.p, nv * n_cut * sizeof(double)));
-            PNX_HIPS(hipMalloc(&dfc.p, nv * n_cut * sizeof(double)));
+            PNX_HIP(hipMalloc(&ddc.p, nv * n_cut * sizeof(double)));
+            PNX_HIP(hipMalloc(&dfc.p, nv * n_cut * sizeof(double)));
             a.d_cut = (double *)ddc.p;
             a.f_cut = (double *)dfc.p;
         }
@@ -510,7 +504,7 @@ int pnx_nnls_spectrum_peaks_f64(int64_t n_vox, int n_bins, const double *spectru
     if (grid > cap) grid = cap;
     if (wide) {  // stream ordered: allocated, filled (the copy from pageable memory is staged before the call returns), used, freed
         double *dbins = nullptr;
-        PNX_HIPS(hipMallocAsync((void **)&dbins, (size_t)n_bins * sizeof(double), st));
+        PNX_HIP(hipMallocAsync((void **)&dbins, (size_t)n_bins * sizeof(double), st));
         hipError_t e = hipMemcpyAsync(dbins, bins_host, (size_t)n_bins * sizeof(double), hipMemcpyHostToDevice, st);
         a.bins_wide = dbins;
         if (e == hipSuccess) {
@@ -522,20 +516,20 @@ int pnx_nnls_spectrum_peaks_f64(int64_t n_vox, int n_bins, const double *spectru
             return pnx::set_error(PNX_ERR_HIP, "wide spectrum launch: %s", hipGetErrorString(e != hipSuccess ? e : e2));
     } else {
         hipLaunchKernelGGL(spectrum_peaks_kernel<4>, dim3((unsigned)grid), dim3(256), 0, st, a);
-        PNX_HIPS(hipGetLastError());
+        PNX_HIP(hipGetLastError());
     }
     if (mem == PNX_MEM_HOST) {
-        if (n_peaks) PNX_HIPS(hipMemcpyAsync(n_peaks, a.n_peaks, nv * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+        if (n_peaks) PNX_HIP(hipMemcpyAsync(n_peaks, a.n_peaks, nv * sizeof(int32_t), hipMemcpyDeviceToHost, st));
         if (max_peaks) {
-            PNX_HIPS(hipMemcpyAsync(d_values, a.d_values, nv * max_peaks * sizeof(double), hipMemcpyDeviceToHost, st));
-            PNX_HIPS(hipMemcpyAsync(f_values, a.f_values, nv * max_peaks * sizeof(double), hipMemcpyDeviceToHost, st));
+            PNX_HIP(hipMemcpyAsync(d_values, a.d_values, nv * max_peaks * sizeof(double), hipMemcpyDeviceToHost, st));
+            PNX_HIP(hipMemcpyAsync(f_values, a.f_values, nv * max_peaks * sizeof(double), hipMemcpyDeviceToHost, st));
         }
         if (n_cut) {
-            PNX_HIPS(hipMemcpyAsync(d_cut, a.d_cut, nv * n_cut * sizeof(double), hipMemcpyDeviceToHost, st));
-            PNX_HIPS(hipMemcpyAsync(f_cut, a.f_cut, nv * n_cut * sizeof(double), hipMemcpyDeviceToHost, st));
+            PNX_HIP(hipMemcpyAsync(d_cut, a.d_cut, nv * n_cut * sizeof(double), hipMemcpyDeviceToHost, st));
+            PNX_HIP(hipMemcpyAsync(f_cut, a.f_cut, nv * n_cut * sizeof(double), hipMemcpyDeviceToHost, st));
         }
     }
-    if (mem == PNX_MEM_HOST) PNX_HIPS(hipStreamSynchronize(st));  // the staging buffers are freed on return; device mode only enqueues
+    if (mem == PNX_MEM_HOST) PNX_HIP(hipStreamSynchronize(st));  // the staging buffers are freed on return; device mode only enqueues
     return PNX_OK;
 }
 
@@ -547,7 +541,7 @@ int pnx_scatter_maps_f32(const double *values, const int64_t *linear_index, int6
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return set_error(PNX_ERR_NO_DEVICE, "no HIP device visible");
     if (device < 0 || device >= ndev) return set_error(PNX_ERR_INVALID, "device %d out of range", device);
-    PNX_HIPS(hipSetDevice(device));
+    PNX_HIP(hipSetDevice(device));
     hipStream_t st = (hipStream_t)stream;
     const size_t nout = (size_t)n_spatial * k;
     if (mem == PNX_MEM_HOST) {
@@ -559,24 +553,24 @@ int pnx_scatter_maps_f32(const double *values, const int64_t *linear_index, int6
     const long long *ix = (const long long *)linear_index;
     float *o = out;
     if (mem == PNX_MEM_HOST) {
-        PNX_HIPS(hipMalloc(&dv.p, (size_t)n_px * k * sizeof(double) + 8));
-        PNX_HIPS(hipMalloc(&di.p, (size_t)n_px * sizeof(long long) + 8));
-        PNX_HIPS(hipMalloc(&dout.p, nout * sizeof(float) + 8));
-        PNX_HIPS(hipMemcpyAsync(dv.p, values, (size_t)n_px * k * sizeof(double), hipMemcpyHostToDevice, st));
-        PNX_HIPS(hipMemcpyAsync(di.p, linear_index, (size_t)n_px * sizeof(long long), hipMemcpyHostToDevice, st));
+        PNX_HIP(hipMalloc(&dv.p, (size_t)n_px * k * sizeof(double) + 8));
+        PNX_HIP(hipMalloc(&di.p, (size_t)n_px * sizeof(long long) + 8));
+        PNX_HIP(hipMalloc(&dout.p, nout * sizeof(float) + 8));
+        PNX_HIP(hipMemcpyAsync(dv.p, values, (size_t)n_px * k * sizeof(double), hipMemcpyHostToDevice, st));
+        PNX_HIP(hipMemcpyAsync(di.p, linear_index, (size_t)n_px * sizeof(long long), hipMemcpyHostToDevice, st));
         v = (const double *)dv.p;
         ix = (const long long *)di.p;
         o = (float *)dout.p;
     }
-    PNX_HIPS(hipMemsetAsync(o, 0, nout * sizeof(float), st));
+    PNX_HIP(hipMemsetAsync(o, 0, nout * sizeof(float), st));
     if (n_px) {
         const long long tot = (long long)n_px * k;
         hipLaunchKernelGGL(scatter_maps_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, v, ix, (long long)n_px, k, o);
-        PNX_HIPS(hipGetLastError());
+        PNX_HIP(hipGetLastError());
     }
     if (mem == PNX_MEM_HOST) {
-        PNX_HIPS(hipMemcpyAsync(out, o, nout * sizeof(float), hipMemcpyDeviceToHost, st));
-        PNX_HIPS(hipStreamSynchronize(st));
+        PNX_HIP(hipMemcpyAsync(out, o, nout * sizeof(float), hipMemcpyDeviceToHost, st));
+        PNX_HIP(hipStreamSynchronize(st));
     }
     return PNX_OK;
 }
