@@ -28,8 +28,8 @@ NNLS_FLAGS = os.environ.get("PNX_NNLS_FLAGS", "").split()  # e.g. -DPNX_NNLS_GBA
 # kernel source groups: profiles/*_traffic.json / *_flops.json are stamped with source_id(group) of the build they were
 # measured on, and bench.py only replays counters whose stamp matches the sources it is running
 SOURCE_GROUPS = {
-    "curvefit": ["pnx_curvefit_kernel.hpp", "pnx_curvefit_inst.hip"],
-    "curvefit_f32": ["pnx_curvefit_f32_kernel.hpp", "pnx_curvefit_f32.hip", "pnx_model_t.hpp"],
+    "curvefit": ["pnx_curvefit_kernel.hpp", "pnx_curvefit_inst.hip", "pnx_trf_math.hpp"],
+    "curvefit_f32": ["pnx_curvefit_f32_kernel.hpp", "pnx_curvefit_f32.hip", "pnx_model_t.hpp", "pnx_trf_math.hpp"],
     "nnls": ["pnx_nnls.hip", "pnx_nnls.hpp", "pnx_nnls_dev.hpp", "pnx_nnls_qr.hip", "pnx_nnls_blk.hip", "pnx_nnls_blk_kernel.hpp"],
     "sweep": ["pnx_sweep.hip", "pnx_model_t.hpp"],
     "predict": ["pnx_predict.hip", "pnx_predict.hpp", "pnx_tile.hpp"],

@@ -25,7 +25,7 @@ template <int MODEL, bool PV> static int launch_one(const CurvefitF32Args &args,
     // LDS per block: b-value table + per wave the signal tile, the parked R factor and singular vectors.  Up to 4 waves per
     // block; fewer when two blocks per CU (two waves per SIMD) would not fit 160 KiB, or one block would not.
     int waves = 4;
-    auto bytes = [&](int w) { return sizeof(float) * (kMaxB + (size_t)w * ParkF<N>::per_wave(args.n_b)); };
+    auto bytes = [&](int w) { return sizeof(float) * (kMaxB + (size_t)w * Park<N>::per_wave(args.n_b)); };
     while (waves > 1 && 2 * bytes(waves) > 160 * 1024) --waves;
     if (bytes(waves) > 160 * 1024) return set_error(PNX_ERR_UNSUPPORTED, "n_b=%d does not fit the LDS tile", args.n_b);
     const int block = waves * kWave;

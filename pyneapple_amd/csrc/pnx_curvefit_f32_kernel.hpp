@@ -14,13 +14,14 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "pnx_curvefit_kernel.hpp"  // Model<>, colperm<>, kWave / kMaxB / kMaxP, LaneState, BoolC, lds_void, the fp64 jacobi_svd of the epilogue
+#include "pnx_curvefit_kernel.hpp"  // Model<>, colperm<>, kWave / kMaxB / kMaxP, LaneState, Park<>, BoolC, lds_void, ColPerm
 #include "pnx_model_t.hpp"
+#include "pnx_trf_math.hpp"  // the TRF algebra with T = float: qr_merge, jacobi_svd, solve_lsq_trust_region, select_step, ...
 
 namespace pnx {
 namespace f32 {
 
-constexpr float kEpsF = 1.1920929e-07f;  // FLT_EPSILON
+constexpr float kEpsF = TrfTraits<float>::eps;  // FLT_EPSILON
 // rows merged into the QR factor per Householder block step (RB x (N + 1) floats of registers)
 template <int N> constexpr int row_blk() { return N >= 6 ? 4 : 8; }
 
@@ -44,404 +45,18 @@ struct CurvefitF32Args {
     float b[kMaxB];
 };
 
-template <int N> __device__ inline float dotn(const float *a, const float *b) {
-    float s = 0;
-#pragma unroll
-    for (int i = 0; i < N; ++i) s += a[i] * b[i];
-    return s;
-}
-template <int N> __device__ inline float normn(const float *a) { return sqrtf(dotn<N>(a, a)); }
-
-// Reciprocal / square root with reciprocal square root from the hardware seeds (v_rcp_f32 / v_rsq_f32, 1 ulp) and one Newton
-// step.  Used only inside orthogonal transformations, as in the fp64 kernel.  Arguments are finite and > 0.
-__device__ inline float fast_rcp(float x) {
-    float r = __builtin_amdgcn_rcpf(x);
-    return fmaf(fmaf(-x, r, 1.0f), r, r);
-}
-// returns sqrt(x), *rs = 1/sqrt(x)
-__device__ inline float fast_sqrt_rsqrt(float x, float *rs) {
-    const float y = __builtin_amdgcn_rsqf(x);
-    float g = x * y, h = 0.5f * y;
-    const float r = fmaf(-h, g, 0.5f);
-    g = fmaf(g, r, g);
-    h = fmaf(h, r, h);
-    *rs = h + h;
-    return g;
-}
-
-// Merge RB rows (J part in blk[r][0..N), rhs in blk[r][N]) into the upper-triangular factor R | q
-// by Householder reflections acting on [R[k][k]; blk[:,k]].  Afterwards blk is garbage.
-template <int N, int RB> __device__ inline void qr_merge(float (&R)[N][N], float (&q)[N], float (&blk)[RB][N + 1]) {
-#pragma unroll
-    for (int k = 0; k < N; ++k) {
-        float sig = 0;
-#pragma unroll
-        for (int r = 0; r < RB; ++r) sig += blk[r][k] * blk[r][k];
-        if (sig > 0) {
-            const float alpha = R[k][k];
-            float rs;
-            const float nrm = fast_sqrt_rsqrt(alpha * alpha + sig, &rs);
-            const float beta = alpha <= 0 ? nrm : -nrm;
-            const float v0 = alpha - beta;            // |v0| >= nrm > 0
-            const float inv_v0 = copysignf(fast_rcp(fabsf(v0)), v0);
-            const float tau = -v0 * (alpha <= 0 ? rs : -rs);  // -v0 / beta
-#pragma unroll
-            for (int r = 0; r < RB; ++r) blk[r][k] *= inv_v0;
-            R[k][k] = beta;
-#pragma unroll
-            for (int j = k + 1; j <= N; ++j) {
-                float w = (j < N) ? R[k][j] : q[k];
-#pragma unroll
-                for (int r = 0; r < RB; ++r) w += blk[r][k] * blk[r][j];
-                w *= tau;
-                if (j < N)
-                    R[k][j] -= w;
-                else
-                    q[k] -= w;
-#pragma unroll
-                for (int r = 0; r < RB; ++r) blk[r][j] -= w * blk[r][k];
-            }
-        }
-    }
-}
-
-// One-sided Jacobi SVD of the N x N matrix W (in place: W <- U*diag(s)), V accumulates the right
-// singular vectors (columns).  Callers pass the TRANSPOSE of a triangular factor (lower triangular W):
-// row-cyclic Jacobi converges in ~1 sweep less on R^T than on R (Drmac-Veselic), see DESIGN.md.
-// A sweep whose largest |cos(angle)| was below 3e-4 (the square root of the fp32 resolution) is the last one: Jacobi
-// converges quadratically, so the rotations of that sweep already leave the off-diagonal at the 1e-7 level.
-template <int N> __device__ inline void jacobi_svd(float (&W)[N][N], float (&V)[N][N]) {
-#pragma unroll
-    for (int i = 0; i < N; ++i)
-#pragma unroll
-        for (int j = 0; j < N; ++j) V[i][j] = (i == j) ? 1.0f : 0.0f;
-    if (N == 1) return;
-    for (int sweep = 0; sweep < 30; ++sweep) {
-        bool rotated = false;  // some pair of this sweep had g^2 / (a b) >= 1e-7 (tested as a product: no division)
-#pragma unroll
-        for (int p = 0; p < N - 1; ++p) {
-#pragma unroll
-            for (int q = p + 1; q < N; ++q) {
-                float a = 0, b = 0, g = 0;
-#pragma unroll
-                for (int i = 0; i < N; ++i) {
-                    a += W[i][p] * W[i][p];
-                    b += W[i][q] * W[i][q];
-                    g += W[i][p] * W[i][q];
-                }
-                const float g2 = g * g, ab = a * b;
-                if (g2 > 1.0e-13f * ab) {  // |cos| > 3e-7
-                    rotated = rotated || (g2 >= 1.0e-7f * ab);
-                    // t = tan(theta) = sign(zeta) / (|zeta| + sqrtf(1 + zeta^2)),  zeta = (b - a) / (2 g)
-                    const float num = b - a, den = 2.0f * g;
-                    float rs;
-                    const float hyp = fast_sqrt_rsqrt(num * num + den * den, &rs);
-                    float t = fabsf(den) * fast_rcp(fabsf(num) + hyp);
-                    t = ((num < 0) != (den < 0)) ? -t : t;
-                    float c;
-                    (void)fast_sqrt_rsqrt(1.0f + t * t, &c);
-                    const float s = c * t;
-#pragma unroll
-                    for (int i = 0; i < N; ++i) {
-                        const float wp = W[i][p], wq = W[i][q];
-                        W[i][p] = c * wp - s * wq;
-                        W[i][q] = s * wp + c * wq;
-                        const float vp = V[i][p], vq = V[i][q];
-                        V[i][p] = c * vp - s * vq;
-                        V[i][q] = s * vp + c * vq;
-                    }
-                }
-            }
-        }
-        if (!rotated) break;
-    }
-}
-
-// scipy/optimize/_lsq/common.py:400-464 with rstep = 0 (np.nextafter form)
-__device__ inline float strictly_feasible0(float x, float lb, float ub) {
-    if (x <= lb) x = nextafterf(lb, ub);
-    if (x >= ub) x = nextafterf(ub, lb);  // numpy applies the lower mask first, then the upper one
-    if (x < lb || x > ub) x = 0.5f * (lb + ub);
-    return x;
-}
-// least_squares.py:827-828 with rstep = 8 FLT_EPSILON: SciPy's 1e-10 is below fp32 resolution (lb + 1e-10 |lb| == lb), and a
-// start value that stays ON a bound has a zero Coleman-Li scale
-__device__ inline float strictly_feasible_r(float x, float lb, float ub) {
-    const float rstep = 8.0f * kEpsF;
-    const float lower_dist = x - lb, upper_dist = ub - x;
-    const float lt = rstep * fmaxf(1.0f, fabsf(lb)), ut = rstep * fmaxf(1.0f, fabsf(ub));
-    int active = 0;
-    if (isfinite(lb) && lower_dist <= fminf(upper_dist, lt)) active = -1;
-    if (isfinite(ub) && upper_dist <= fminf(lower_dist, ut)) active = 1;
-    if (active == -1) x = lb + lt;
-    if (active == 1) x = ub - ut;
-    if (x < lb || x > ub) x = 0.5f * (lb + ub);
-    return x;
-}
-
-// scipy/optimize/_lsq/common.py:367-397
-template <int N>
-__device__ inline float step_size_to_bound(const float *x, const float *s, const float *lb, const float *ub,
-                                            int *hits) {
-    float steps[N];
-    float mn = INFINITY;
-#pragma unroll
-    for (int i = 0; i < N; ++i) {
-        // max((lb - x) / s, (ub - x) / s) is the quotient with the larger numerator for s > 0 and with the smaller one for
-        // s < 0 (lb <= ub): one IEEE division instead of two, the same value bit for bit
-        const float num = (s[i] > 0) ? (ub[i] - x[i]) : (lb[i] - x[i]);
-        steps[i] = (s[i] != 0) ? num / s[i] : INFINITY;
-        mn = fminf(mn, steps[i]);
-    }
-    if (hits) {
-#pragma unroll
-        for (int i = 0; i < N; ++i) hits[i] = (steps[i] == mn) ? ((s[i] > 0) - (s[i] < 0)) : 0;
-    }
-    return mn;
-}
-
-// 0.5*||R2 s||^2 + g_h.s  ==  evaluate_quadratic(J_h, g_h, s, diag=diag_h) (common.py:325-362), because
-// R2^T R2 = J_h^T J_h + diag(diag_h).
-template <int N> __device__ inline void rmul(const float (&R)[N][N], const float *s, float *out) {
-#pragma unroll
-    for (int i = 0; i < N; ++i) {
-        float a = 0;
-#pragma unroll
-        for (int j = i; j < N; ++j) a += R[i][j] * s[j];
-        out[i] = a;
-    }
-}
-
-// common.py:303-322
-__device__ inline float minimize_quadratic_1d(float a, float b, float lb, float ub, float c, float &y) {
-    float tb = lb, yb = lb * (a * lb + b) + c;
-    const float yu = ub * (a * ub + b) + c;
-    if (yu < yb) {
-        yb = yu;
-        tb = ub;
-    }
-    if (a != 0) {
-        const float ext = -0.5f * b / a;
-        if (lb < ext && ext < ub) {
-            const float ye = ext * (a * ext + b) + c;
-            if (ye < yb) {
-                yb = ye;
-                tb = ext;
-            }
-        }
-    }
-    y = yb;
-    return tb;
-}
-
-// common.py:57-168
-template <int N>
-__device__ inline float solve_lsq_trust_region(int m, const float *uf, const float *s, const float (&V)[N][N],
-                                                float smax, float smin, float Delta, float initial_alpha,
-                                                float *p) {
-    float suf[N], t[N];
-#pragma unroll
-    for (int i = 0; i < N; ++i) suf[i] = s[i] * uf[i];
-    const bool full_rank = (m >= N) && (smin > kEpsF * m * smax);
-    if (full_rank) {
-#pragma unroll
-        for (int i = 0; i < N; ++i) t[i] = uf[i] / s[i];
-#pragma unroll
-        for (int i = 0; i < N; ++i) {
-            float a = 0;
-#pragma unroll
-            for (int k = 0; k < N; ++k) a += V[i][k] * t[k];
-            p[i] = -a;
-        }
-        if (normn<N>(p) <= Delta) return 0.0f;
-    }
-    float alpha_upper = normn<N>(suf) / Delta;
-    float alpha_lower = 0.0f;
-    auto phi_and_derivative = [&](float alpha, float &phi, float &phi_prime) {
-        float pn2 = 0, sp = 0;
-#pragma unroll
-        for (int i = 0; i < N; ++i) {
-            const float denom = s[i] * s[i] + alpha;
-            const float q = suf[i] / denom;
-            pn2 += q * q;
-            sp += q * q / denom;  // suf^2 / denom^3 without the cube: denom^3 leaves the fp32 range for signals of amplitude 1e3
-        }
-        const float p_norm = sqrtf(pn2);
-        phi = p_norm - Delta;
-        phi_prime = -sp / p_norm;
-    };
-    float phi, phi_prime;
-    if (full_rank) {
-        phi_and_derivative(0.0f, phi, phi_prime);
-        alpha_lower = -phi / phi_prime;
-    }
-    float alpha;
-    if (!full_rank && initial_alpha == 0)
-        alpha = fmaxf(0.001f * alpha_upper, sqrtf(alpha_lower * alpha_upper));
-    else
-        alpha = initial_alpha;
-    for (int it = 0; it < 10; ++it) {
-        if (alpha < alpha_lower || alpha > alpha_upper)
-            alpha = fmaxf(0.001f * alpha_upper, sqrtf(alpha_lower * alpha_upper));
-        phi_and_derivative(alpha, phi, phi_prime);
-        if (phi < 0) alpha_upper = alpha;
-        const float ratio = phi / phi_prime;
-        alpha_lower = fmaxf(alpha_lower, alpha - ratio);
-        alpha -= (phi + Delta) * ratio / Delta;
-        if (fabsf(phi) < 0.01f * Delta) break;
-    }
-#pragma unroll
-    for (int i = 0; i < N; ++i) t[i] = suf[i] / (s[i] * s[i] + alpha);
-#pragma unroll
-    for (int i = 0; i < N; ++i) {
-        float a = 0;
-#pragma unroll
-        for (int k = 0; k < N; ++k) a += V[i][k] * t[k];
-        p[i] = -a;
-    }
-    const float sc = Delta / normn<N>(p);
-#pragma unroll
-    for (int i = 0; i < N; ++i) p[i] *= sc;
-    return alpha;
-}
-
-// trf.py:128-202.  Returns predicted reduction; writes step / step_h.
-template <int N>
-__device__ inline float select_step(const float *x, const float (&R2)[N][N], const float *g_h, float *p,
-                                     float *p_h, const float *d, float Delta, const float *lb, const float *ub,
-                                     float theta, float *step, float *step_h) {
-    bool inb = true;
-#pragma unroll
-    for (int i = 0; i < N; ++i) {
-        const float xp = x[i] + p[i];
-        inb = inb && (xp >= lb[i]) && (xp <= ub[i]);
-    }
-    float t1[N], t2[N];
-    if (inb) {
-        rmul<N>(R2, p_h, t1);
-        const float p_value = 0.5f * dotn<N>(t1, t1) + dotn<N>(p_h, g_h);
-#pragma unroll
-        for (int i = 0; i < N; ++i) {
-            step[i] = p[i];
-            step_h[i] = p_h[i];
-        }
-        return -p_value;
-    }
-    int hits[N];
-    const float p_stride = step_size_to_bound<N>(x, p, lb, ub, hits);
-    float r_h[N], r[N], xb[N];
-#pragma unroll
-    for (int i = 0; i < N; ++i) {
-        r_h[i] = hits[i] ? -p_h[i] : p_h[i];
-        r[i] = d[i] * r_h[i];
-    }
-#pragma unroll
-    for (int i = 0; i < N; ++i) {
-        p[i] *= p_stride;
-        p_h[i] *= p_stride;
-        xb[i] = x[i] + p[i];
-    }
-    // intersect_trust_region(p_h, r_h, Delta) (common.py:18-54), positive root
-    float to_tr;
-    {
-        const float a = dotn<N>(r_h, r_h), b = dotn<N>(p_h, r_h), c = dotn<N>(p_h, p_h) - Delta * Delta;
-        const float dd = sqrtf(b * b - a * c);
-        const float q = -(b + copysignf(dd, b));
-        const float ta = q / a, tb = c / q;
-        to_tr = fmaxf(ta, tb);
-    }
-    float to_bound = step_size_to_bound<N>(xb, r, lb, ub, nullptr);
-    float r_stride = fminf(to_bound, to_tr);
-    float r_stride_l, r_stride_u;
-    if (r_stride > 0) {
-        r_stride_l = (1 - theta) * p_stride / r_stride;
-        r_stride_u = (r_stride == to_bound) ? theta * to_bound : to_tr;
-    } else {
-        r_stride_l = 0;
-        r_stride_u = -1;
-    }
-    float r_value;
-    if (r_stride_l <= r_stride_u) {
-        // build_quadratic_1d(J_h, g_h, r_h, s0=p_h, diag=diag_h) (common.py:250-300)
-        rmul<N>(R2, r_h, t1);   // v
-        rmul<N>(R2, p_h, t2);   // u
-        const float a = 0.5f * dotn<N>(t1, t1);
-        const float b = dotn<N>(g_h, r_h) + dotn<N>(t2, t1);
-        const float c = 0.5f * dotn<N>(t2, t2) + dotn<N>(g_h, p_h);
-        r_stride = minimize_quadratic_1d(a, b, r_stride_l, r_stride_u, c, r_value);
-#pragma unroll
-        for (int i = 0; i < N; ++i) {
-            r_h[i] = r_h[i] * r_stride + p_h[i];
-            r[i] = r_h[i] * d[i];
-        }
-    } else
-        r_value = INFINITY;
-#pragma unroll
-    for (int i = 0; i < N; ++i) {
-        p[i] *= theta;
-        p_h[i] *= theta;
-    }
-    rmul<N>(R2, p_h, t1);
-    const float p_value = 0.5f * dotn<N>(t1, t1) + dotn<N>(p_h, g_h);
-
-    float ag_h[N], ag[N];
-#pragma unroll
-    for (int i = 0; i < N; ++i) {
-        ag_h[i] = -g_h[i];
-        ag[i] = d[i] * ag_h[i];
-    }
-    to_tr = Delta / normn<N>(ag_h);
-    to_bound = step_size_to_bound<N>(x, ag, lb, ub, nullptr);
-    float ag_stride = (to_bound < to_tr) ? theta * to_bound : to_tr;
-    float ag_value;
-    {
-        rmul<N>(R2, ag_h, t1);
-        const float a = 0.5f * dotn<N>(t1, t1);
-        const float b = dotn<N>(g_h, ag_h);
-        ag_stride = minimize_quadratic_1d(a, b, 0.0f, ag_stride, 0.0f, ag_value);
-    }
-    if (p_value < r_value && p_value < ag_value) {
-#pragma unroll
-        for (int i = 0; i < N; ++i) {
-            step[i] = p[i];
-            step_h[i] = p_h[i];
-        }
-        return -p_value;
-    } else if (r_value < p_value && r_value < ag_value) {
-#pragma unroll
-        for (int i = 0; i < N; ++i) {
-            step[i] = r[i];
-            step_h[i] = r_h[i];
-        }
-        return -r_value;
-    } else {
-#pragma unroll
-        for (int i = 0; i < N; ++i) {
-            step[i] = ag[i] * ag_stride;
-            step_h[i] = ag_h[i] * ag_stride;
-        }
-        return -ag_value;
-    }
-}
-
 // ---------------------------------------------------------------------------------------------
 // The kernel.  Block = up to 4 wavefronts; LDS: b-values + per wave the signal tile y[row][lane] (floats: one conflict-free
-// ds_read_b32 per row), the packed R factor of the current iterate and (N <= 5) the right singular vectors.
+// ds_read_b32 per row), the packed R factor of the current iterate and (N <= 5) the right singular vectors: Park<N> with a
+// tile of n_b rows, counted in floats.
 // ---------------------------------------------------------------------------------------------
-template <int N> struct ParkF {
-    static constexpr int NR = N * (N + 1) / 2;
-    static constexpr bool kParkV = (N <= 5);
-    static constexpr int NV = kParkV ? N * N : 0;
-    // floats of LDS per wave besides the b-value table
-    __host__ __device__ static constexpr int per_wave(int n_b) { return kWave * (n_b + NR + NV); }
-};
 
 // Loop order as curvefit_kernel: refill, row pass at x_new, D (accept / reject, radius, ftol / xtol), B-light (Coleman-Li
 // scaling, gtol), outputs of finished voxels + refill, B-heavy (augmented QR + Jacobi SVD), C (trust-region step).
 template <int MODEL, bool PV>
 __global__ void __launch_bounds__(64 * 4, 2) curvefit_f32_kernel(const CurvefitF32Args A) {
     using MT = ModelT<MODEL, float>;
-    using PK = ParkF<MT::NALL>;
+    using PK = Park<MT::NALL>;
     constexpr int N = MT::NALL;
     auto CP = [](int k) constexpr { return colperm<MODEL>(k); };  // factor column k = parameter CP(k)
 
@@ -791,7 +406,7 @@ __global__ void __launch_bounds__(64 * 4, 2) curvefit_f32_kernel(const CurvefitF
 // ---------------------------------------------------------------------------------------------
 // Covariance epilogue (one lane per voxel): the packed fp32 R factor that curvefit_f32_kernel parked in pcov[vox] ->
 //   pinv(J^T J) * 2 cost / (m - n)  (scipy/optimize/_minpack_py.py:1036-1066), NaN for failed voxels.
-// Computed in fp64 (the fp64 kernel's jacobi_svd) and stored as float.  Singular values are dropped below
+// Computed in fp64 (jacobi_svd<N, double> of pnx_trf_math.hpp) and stored as float.  Singular values are dropped below
 // FLT_EPSILON * max(m, n) * s_max -- the factor is an fp32 one -- where SciPy uses the fp64 epsilon.
 // ---------------------------------------------------------------------------------------------
 template <int N>
@@ -817,7 +432,7 @@ __global__ void __launch_bounds__(256) pcov_f32_kernel(float *pcov, const int8_t
 #pragma unroll
             for (int j = i; j < N; ++j) W[j][i] = (double)pc[t++];  // W = R^T
     }
-    pnx::jacobi_svd<N>(W, Vw);
+    jacobi_svd<N>(W, Vw);
     double s2[N], sm = 0;
 #pragma unroll
     for (int k = 0; k < N; ++k) {

@@ -4,6 +4,7 @@
 
 #include "pnx_curvefit_kernel.hpp"
 #include "pnx_internal.hpp"
+#include "pnx_launch.hpp"
 
 #ifndef PNX_MODEL
 #error "compile with -DPNX_MODEL=<0..6>"
@@ -30,20 +31,13 @@ static int launch_one(const CurvefitArgs &args, int device_cus, hipStream_t stre
     // LDS per block: b-value table + per wave: [n_b][64] signal tile, parked R factor and singular vectors.
     // Up to 4 waves per block; fewer when that would not fit 160 KiB.
     int waves = PNX_CF_BLOCK_WAVES;
-    auto bytes = [&](int w) { return sizeof(double) * ((args.use_sigma ? 2 * kMaxB : kMaxB) + (size_t)w * Park<N>::per_wave(args.n_b)); };  // + the 1 / sigma table
+    auto bytes = [&](int w) { return sizeof(double) * ((args.use_sigma ? 2 * kMaxB : kMaxB) + (size_t)w * Park<N>::per_wave_f64(args.n_b)); };  // + the 1 / sigma table
     while (waves > 1 && bytes(waves) > 160 * 1024) --waves;
     if (bytes(waves) > 160 * 1024) return set_error(PNX_ERR_UNSUPPORTED, "n_b=%d does not fit the LDS tile", args.n_b);
     const int block = waves * kWave;
     const size_t shmem = bytes(waves);
-    static bool attr_done[64] = {false};  // function attributes are per device
-    int cur_dev = 0;
-    (void)hipGetDevice(&cur_dev);
-    bool &attr_set = attr_done[cur_dev & 63];
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) return set_error(PNX_ERR_HIP, "hipFuncSetAttribute: %s", hipGetErrorString(e));
-        attr_set = true;
-    }
+    if (hipError_t ea = allow_big_lds<curvefit_kernel<MODEL, N, FD, PV, T1, STREAM>>(); ea != hipSuccess)
+        return set_error(PNX_ERR_HIP, "hipFuncSetAttribute: %s", hipGetErrorString(ea));
     int occ = 0;
     hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kern, block, shmem);
     if (e != hipSuccess || occ < 1) return set_error(PNX_ERR_HIP, "occupancy query failed (shmem=%zu): %s", shmem, hipGetErrorString(e));

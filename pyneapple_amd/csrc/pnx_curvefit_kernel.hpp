@@ -25,6 +25,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "pnx_trf_math.hpp"  // the TRF algebra shared with the fp32 kernel: qr_merge, jacobi_svd, solve_lsq_trust_region, select_step, ...
+
 namespace pnx {
 
 constexpr int kWave = 64;
@@ -38,7 +40,7 @@ template <int N> constexpr int row_blk() { return PNX_ROW_BLK; }
 #else
 template <int N> constexpr int row_blk() { return N >= 7 ? 2 : (N >= 5 ? 4 : 8); }  // N = 7: 450 -> 200 B of spills with 2
 #endif
-constexpr double kEps = 2.220446049250313e-16;
+constexpr double kEps = TrfTraits<double>::eps;
 constexpr double kSqrtEps = 1.4901161193847656e-08;
 template <bool B> struct BoolC {  // compile-time flag handed to a generic lambda
     static constexpr bool value = B;
@@ -208,41 +210,6 @@ template <int MODEL> __device__ constexpr int comp_of_param(int j) {
     return -1;
 }
 
-// ---------------------------------------------------------------------------------------------
-// Small dense helpers, everything statically indexed (register resident).
-// ---------------------------------------------------------------------------------------------
-template <int N> __device__ inline double dotn(const double *a, const double *b) {
-    double s = 0;
-#pragma unroll
-    for (int i = 0; i < N; ++i) s += a[i] * b[i];
-    return s;
-}
-template <int N> __device__ inline double normn(const double *a) { return sqrt(dotn<N>(a, a)); }
-
-// Reciprocal / reciprocal square root to ~1 ulp from the hardware seeds (v_rcp_f64 / v_rsq_f64) and two
-// Newton steps: 5-6 VALU ops instead of the 11 (fdiv) / 18 (sqrt) of the IEEE-exact expansions.  Used only
-// inside orthogonal transformations (Householder, Givens/Jacobi), where a last-bit error perturbs
-// orthogonality at the 1e-16 level and nothing else.  Arguments are finite and > 0.
-__device__ inline double fast_rcp(double x) {
-    double r = __builtin_amdgcn_rcp(x);
-    r = fma(fma(-x, r, 1.0), r, r);
-    r = fma(fma(-x, r, 1.0), r, r);
-    return r;
-}
-// returns sqrt(x), *rs = 1/sqrt(x)
-__device__ inline double fast_sqrt_rsqrt(double x, double *rs) {
-    double y = __builtin_amdgcn_rsq(x);
-    double g = x * y, h = 0.5 * y;
-    double r = fma(-h, g, 0.5);
-    g = fma(g, r, g);
-    h = fma(h, r, h);
-    r = fma(-h, g, 0.5);
-    g = fma(g, r, g);
-    h = fma(h, r, h);
-    *rs = h + h;
-    return g;
-}
-
 // exp(x), fp64, <= 1 ulp class: the reduction and the degree-11 polynomial of the device library's exp (k = rint(x / ln 2),
 // r = x - k ln2_hi - k ln2_lo, |r| <= 0.347) without its overflow / underflow selects -- v_ldexp_f64 saturates to inf / 0
 // by itself, v_cvt_i32_f64 saturates k, NaN propagates through the polynomial -- and with the polynomial split into
@@ -285,360 +252,6 @@ __device__ inline double exp_fast(double x) {
 #endif
 }
 
-// Merge RB rows (J part in blk[r][0..N), rhs in blk[r][N]) into the upper-triangular factor R | q
-// by Householder reflections acting on [R[k][k]; blk[:,k]].  Afterwards blk is garbage.
-template <int N, int RB> __device__ inline void qr_merge(double (&R)[N][N], double (&q)[N], double (&blk)[RB][N + 1]) {
-#pragma unroll
-    for (int k = 0; k < N; ++k) {
-        double sig = 0;
-#pragma unroll
-        for (int r = 0; r < RB; ++r) sig += blk[r][k] * blk[r][k];
-        if (sig > 0) {
-            const double alpha = R[k][k];
-            double rs;
-            const double nrm = fast_sqrt_rsqrt(alpha * alpha + sig, &rs);
-            const double beta = alpha <= 0 ? nrm : -nrm;
-            const double v0 = alpha - beta;            // |v0| >= nrm > 0
-            const double inv_v0 = copysign(fast_rcp(fabs(v0)), v0);
-            const double tau = -v0 * (alpha <= 0 ? rs : -rs);  // -v0 / beta
-#pragma unroll
-            for (int r = 0; r < RB; ++r) blk[r][k] *= inv_v0;
-            R[k][k] = beta;
-#pragma unroll
-            for (int j = k + 1; j <= N; ++j) {
-                double w = (j < N) ? R[k][j] : q[k];
-#pragma unroll
-                for (int r = 0; r < RB; ++r) w += blk[r][k] * blk[r][j];
-                w *= tau;
-                if (j < N)
-                    R[k][j] -= w;
-                else
-                    q[k] -= w;
-#pragma unroll
-                for (int r = 0; r < RB; ++r) blk[r][j] -= w * blk[r][k];
-            }
-        }
-    }
-}
-
-// One-sided Jacobi SVD of the N x N matrix W (in place: W <- U*diag(s)), V accumulates the right
-// singular vectors (columns).  Callers pass the TRANSPOSE of a triangular factor (lower triangular W):
-// row-cyclic Jacobi converges in ~1 sweep less on R^T than on R (Drmac-Veselic), see DESIGN.md.
-// A sweep whose largest |cos(angle)| was below 1e-8 is the last one: Jacobi converges quadratically, so the
-// rotations of that sweep already leave the off-diagonal at the 1e-16 level.
-template <int N> __device__ inline void jacobi_svd(double (&W)[N][N], double (&V)[N][N]) {
-#pragma unroll
-    for (int i = 0; i < N; ++i)
-#pragma unroll
-        for (int j = 0; j < N; ++j) V[i][j] = (i == j) ? 1.0 : 0.0;
-    if (N == 1) return;
-    for (int sweep = 0; sweep < 30; ++sweep) {
-        bool rotated = false;  // some pair of this sweep had g^2 / (a b) >= 1e-16 (tested as a product: no division)
-#pragma unroll
-        for (int p = 0; p < N - 1; ++p) {
-#pragma unroll
-            for (int q = p + 1; q < N; ++q) {
-                double a = 0, b = 0, g = 0;
-#pragma unroll
-                for (int i = 0; i < N; ++i) {
-                    a += W[i][p] * W[i][p];
-                    b += W[i][q] * W[i][q];
-                    g += W[i][p] * W[i][q];
-                }
-                const double g2 = g * g, ab = a * b;
-                if (g2 > 1.0e-30 * ab) {  // |cos| > 1e-15
-                    rotated = rotated || (g2 >= 1.0e-16 * ab);
-                    // t = tan(theta) = sign(zeta) / (|zeta| + sqrt(1 + zeta^2)),  zeta = (b - a) / (2 g)
-                    const double num = b - a, den = 2.0 * g;
-                    double rs;
-                    const double hyp = fast_sqrt_rsqrt(num * num + den * den, &rs);
-                    double t = fabs(den) * fast_rcp(fabs(num) + hyp);
-                    t = ((num < 0) != (den < 0)) ? -t : t;
-                    double c;
-                    (void)fast_sqrt_rsqrt(1.0 + t * t, &c);
-                    const double s = c * t;
-#pragma unroll
-                    for (int i = 0; i < N; ++i) {
-                        const double wp = W[i][p], wq = W[i][q];
-                        W[i][p] = c * wp - s * wq;
-                        W[i][q] = s * wp + c * wq;
-                        const double vp = V[i][p], vq = V[i][q];
-                        V[i][p] = c * vp - s * vq;
-                        V[i][q] = s * vp + c * vq;
-                    }
-                }
-            }
-        }
-        if (!rotated) break;
-    }
-}
-
-// scipy/optimize/_lsq/common.py:400-464 with rstep = 0 (np.nextafter form)
-__device__ inline double strictly_feasible0(double x, double lb, double ub) {
-    if (x <= lb) x = nextafter(lb, ub);
-    if (x >= ub) x = nextafter(ub, lb);  // numpy applies the lower mask first, then the upper one
-    if (x < lb || x > ub) x = 0.5 * (lb + ub);
-    return x;
-}
-// same with rstep = 1e-10 (least_squares.py:827-828)
-__device__ inline double strictly_feasible_r(double x, double lb, double ub) {
-    const double rstep = 1e-10;
-    const double lower_dist = x - lb, upper_dist = ub - x;
-    const double lt = rstep * fmax(1.0, fabs(lb)), ut = rstep * fmax(1.0, fabs(ub));
-    int active = 0;
-    if (isfinite(lb) && lower_dist <= fmin(upper_dist, lt)) active = -1;
-    if (isfinite(ub) && upper_dist <= fmin(lower_dist, ut)) active = 1;
-    if (active == -1) x = lb + lt;
-    if (active == 1) x = ub - ut;
-    if (x < lb || x > ub) x = 0.5 * (lb + ub);
-    return x;
-}
-
-// scipy/optimize/_lsq/common.py:367-397
-template <int N>
-__device__ inline double step_size_to_bound(const double *x, const double *s, const double *lb, const double *ub,
-                                            int *hits) {
-    double steps[N];
-    double mn = INFINITY;
-#pragma unroll
-    for (int i = 0; i < N; ++i) {
-        // max((lb - x) / s, (ub - x) / s) is the quotient with the larger numerator for s > 0 and with the smaller one for
-        // s < 0 (lb <= ub): one IEEE division instead of two, the same value bit for bit
-        const double num = (s[i] > 0) ? (ub[i] - x[i]) : (lb[i] - x[i]);
-        steps[i] = (s[i] != 0) ? num / s[i] : INFINITY;
-        mn = fmin(mn, steps[i]);
-    }
-    if (hits) {
-#pragma unroll
-        for (int i = 0; i < N; ++i) hits[i] = (steps[i] == mn) ? ((s[i] > 0) - (s[i] < 0)) : 0;
-    }
-    return mn;
-}
-
-// 0.5*||R2 s||^2 + g_h.s  ==  evaluate_quadratic(J_h, g_h, s, diag=diag_h) (common.py:325-362), because
-// R2^T R2 = J_h^T J_h + diag(diag_h).
-template <int N> __device__ inline void rmul(const double (&R)[N][N], const double *s, double *out) {
-#pragma unroll
-    for (int i = 0; i < N; ++i) {
-        double a = 0;
-#pragma unroll
-        for (int j = i; j < N; ++j) a += R[i][j] * s[j];
-        out[i] = a;
-    }
-}
-
-// common.py:303-322
-__device__ inline double minimize_quadratic_1d(double a, double b, double lb, double ub, double c, double &y) {
-    double tb = lb, yb = lb * (a * lb + b) + c;
-    const double yu = ub * (a * ub + b) + c;
-    if (yu < yb) {
-        yb = yu;
-        tb = ub;
-    }
-    if (a != 0) {
-        const double ext = -0.5 * b / a;
-        if (lb < ext && ext < ub) {
-            const double ye = ext * (a * ext + b) + c;
-            if (ye < yb) {
-                yb = ye;
-                tb = ext;
-            }
-        }
-    }
-    y = yb;
-    return tb;
-}
-
-// common.py:57-168
-template <int N>
-__device__ inline double solve_lsq_trust_region(int m, const double *uf, const double *s, const double (&V)[N][N],
-                                                double smax, double smin, double Delta, double initial_alpha,
-                                                double *p) {
-    double suf[N], t[N];
-#pragma unroll
-    for (int i = 0; i < N; ++i) suf[i] = s[i] * uf[i];
-    const bool full_rank = (m >= N) && (smin > kEps * m * smax);
-    if (full_rank) {
-#pragma unroll
-        for (int i = 0; i < N; ++i) t[i] = uf[i] / s[i];
-#pragma unroll
-        for (int i = 0; i < N; ++i) {
-            double a = 0;
-#pragma unroll
-            for (int k = 0; k < N; ++k) a += V[i][k] * t[k];
-            p[i] = -a;
-        }
-        if (normn<N>(p) <= Delta) return 0.0;
-    }
-    double alpha_upper = normn<N>(suf) / Delta;
-    double alpha_lower = 0.0;
-    auto phi_and_derivative = [&](double alpha, double &phi, double &phi_prime) {
-        double pn2 = 0, sp = 0;
-#pragma unroll
-        for (int i = 0; i < N; ++i) {
-            const double denom = s[i] * s[i] + alpha;
-            const double q = suf[i] / denom;
-            pn2 += q * q;
-            sp += suf[i] * suf[i] / (denom * denom * denom);
-        }
-        const double p_norm = sqrt(pn2);
-        phi = p_norm - Delta;
-        phi_prime = -sp / p_norm;
-    };
-    double phi, phi_prime;
-    if (full_rank) {
-        phi_and_derivative(0.0, phi, phi_prime);
-        alpha_lower = -phi / phi_prime;
-    }
-    double alpha;
-    if (!full_rank && initial_alpha == 0)
-        alpha = fmax(0.001 * alpha_upper, sqrt(alpha_lower * alpha_upper));
-    else
-        alpha = initial_alpha;
-    for (int it = 0; it < 10; ++it) {
-        if (alpha < alpha_lower || alpha > alpha_upper)
-            alpha = fmax(0.001 * alpha_upper, sqrt(alpha_lower * alpha_upper));
-        phi_and_derivative(alpha, phi, phi_prime);
-        if (phi < 0) alpha_upper = alpha;
-        const double ratio = phi / phi_prime;
-        alpha_lower = fmax(alpha_lower, alpha - ratio);
-        alpha -= (phi + Delta) * ratio / Delta;
-        if (fabs(phi) < 0.01 * Delta) break;
-    }
-#pragma unroll
-    for (int i = 0; i < N; ++i) t[i] = suf[i] / (s[i] * s[i] + alpha);
-#pragma unroll
-    for (int i = 0; i < N; ++i) {
-        double a = 0;
-#pragma unroll
-        for (int k = 0; k < N; ++k) a += V[i][k] * t[k];
-        p[i] = -a;
-    }
-    const double sc = Delta / normn<N>(p);
-#pragma unroll
-    for (int i = 0; i < N; ++i) p[i] *= sc;
-    return alpha;
-}
-
-// trf.py:128-202.  Returns predicted reduction; writes step / step_h.
-template <int N>
-__device__ inline double select_step(const double *x, const double (&R2)[N][N], const double *g_h, double *p,
-                                     double *p_h, const double *d, double Delta, const double *lb, const double *ub,
-                                     double theta, double *step, double *step_h) {
-    bool inb = true;
-#pragma unroll
-    for (int i = 0; i < N; ++i) {
-        const double xp = x[i] + p[i];
-        inb = inb && (xp >= lb[i]) && (xp <= ub[i]);
-    }
-    double t1[N], t2[N];
-    if (inb) {
-        rmul<N>(R2, p_h, t1);
-        const double p_value = 0.5 * dotn<N>(t1, t1) + dotn<N>(p_h, g_h);
-#pragma unroll
-        for (int i = 0; i < N; ++i) {
-            step[i] = p[i];
-            step_h[i] = p_h[i];
-        }
-        return -p_value;
-    }
-    int hits[N];
-    const double p_stride = step_size_to_bound<N>(x, p, lb, ub, hits);
-    double r_h[N], r[N], xb[N];
-#pragma unroll
-    for (int i = 0; i < N; ++i) {
-        r_h[i] = hits[i] ? -p_h[i] : p_h[i];
-        r[i] = d[i] * r_h[i];
-    }
-#pragma unroll
-    for (int i = 0; i < N; ++i) {
-        p[i] *= p_stride;
-        p_h[i] *= p_stride;
-        xb[i] = x[i] + p[i];
-    }
-    // intersect_trust_region(p_h, r_h, Delta) (common.py:18-54), positive root
-    double to_tr;
-    {
-        const double a = dotn<N>(r_h, r_h), b = dotn<N>(p_h, r_h), c = dotn<N>(p_h, p_h) - Delta * Delta;
-        const double dd = sqrt(b * b - a * c);
-        const double q = -(b + copysign(dd, b));
-        const double ta = q / a, tb = c / q;
-        to_tr = fmax(ta, tb);
-    }
-    double to_bound = step_size_to_bound<N>(xb, r, lb, ub, nullptr);
-    double r_stride = fmin(to_bound, to_tr);
-    double r_stride_l, r_stride_u;
-    if (r_stride > 0) {
-        r_stride_l = (1 - theta) * p_stride / r_stride;
-        r_stride_u = (r_stride == to_bound) ? theta * to_bound : to_tr;
-    } else {
-        r_stride_l = 0;
-        r_stride_u = -1;
-    }
-    double r_value;
-    if (r_stride_l <= r_stride_u) {
-        // build_quadratic_1d(J_h, g_h, r_h, s0=p_h, diag=diag_h) (common.py:250-300)
-        rmul<N>(R2, r_h, t1);   // v
-        rmul<N>(R2, p_h, t2);   // u
-        const double a = 0.5 * dotn<N>(t1, t1);
-        const double b = dotn<N>(g_h, r_h) + dotn<N>(t2, t1);
-        const double c = 0.5 * dotn<N>(t2, t2) + dotn<N>(g_h, p_h);
-        r_stride = minimize_quadratic_1d(a, b, r_stride_l, r_stride_u, c, r_value);
-#pragma unroll
-        for (int i = 0; i < N; ++i) {
-            r_h[i] = r_h[i] * r_stride + p_h[i];
-            r[i] = r_h[i] * d[i];
-        }
-    } else
-        r_value = INFINITY;
-#pragma unroll
-    for (int i = 0; i < N; ++i) {
-        p[i] *= theta;
-        p_h[i] *= theta;
-    }
-    rmul<N>(R2, p_h, t1);
-    const double p_value = 0.5 * dotn<N>(t1, t1) + dotn<N>(p_h, g_h);
-
-    double ag_h[N], ag[N];
-#pragma unroll
-    for (int i = 0; i < N; ++i) {
-        ag_h[i] = -g_h[i];
-        ag[i] = d[i] * ag_h[i];
-    }
-    to_tr = Delta / normn<N>(ag_h);
-    to_bound = step_size_to_bound<N>(x, ag, lb, ub, nullptr);
-    double ag_stride = (to_bound < to_tr) ? theta * to_bound : to_tr;
-    double ag_value;
-    {
-        rmul<N>(R2, ag_h, t1);
-        const double a = 0.5 * dotn<N>(t1, t1);
-        const double b = dotn<N>(g_h, ag_h);
-        ag_stride = minimize_quadratic_1d(a, b, 0.0, ag_stride, 0.0, ag_value);
-    }
-    if (p_value < r_value && p_value < ag_value) {
-#pragma unroll
-        for (int i = 0; i < N; ++i) {
-            step[i] = p[i];
-            step_h[i] = p_h[i];
-        }
-        return -p_value;
-    } else if (r_value < p_value && r_value < ag_value) {
-#pragma unroll
-        for (int i = 0; i < N; ++i) {
-            step[i] = r[i];
-            step_h[i] = r_h[i];
-        }
-        return -r_value;
-    } else {
-#pragma unroll
-        for (int i = 0; i < N; ++i) {
-            step[i] = ag[i] * ag_stride;
-            step_h[i] = ag_h[i] * ag_stride;
-        }
-        return -ag_value;
-    }
-}
-
 // ---------------------------------------------------------------------------------------------
 // The kernel.  Block = WAVES wavefronts; LDS: b-values + per-wave signal tile y[row][lane].
 // ---------------------------------------------------------------------------------------------
@@ -648,9 +261,11 @@ template <int N> struct Park {
     static constexpr int NR = N * (N + 1) / 2;          // packed R factor of J at the current iterate (for pcov)
     static constexpr bool kParkV = (N <= 5);            // right singular vectors live in LDS between B and C
     static constexpr int NV = kParkV ? N * N : 0;
-    // doubles of LDS per wave besides the b-value table
-    // the signal tile is [ceil(n_b / 2)][64 lanes][2] (the layout a 16-byte LDS-DMA load per lane produces)
-    __host__ __device__ static constexpr int per_wave(int n_b) { return kWave * (((n_b + 1) & ~1) + NR + NV); }
+    // scalars of LDS per wave besides the b-value table; tile_rows = rows of the wave's signal tile
+    __host__ __device__ static constexpr int per_wave(int tile_rows) { return kWave * (tile_rows + NR + NV); }
+    // the fp64 signal tile is [ceil(n_b / 2)][64 lanes][2] (the layout a 16-byte LDS-DMA load per lane produces): an even row count
+    // (= per_wave((n_b + 1) & ~1), written out: folded as one expression the compiler emits the same code as it always did)
+    __host__ __device__ static constexpr int per_wave_f64(int n_b) { return kWave * (((n_b + 1) & ~1) + NR + NV); }
 };
 
 // Loop order -- one iteration = one row pass per lane:
@@ -689,7 +304,7 @@ __global__ void __launch_bounds__(64 * PNX_CF_BLOCK_WAVES, PNX_CF_WAVES_PER_SIMD
     const int wave = threadIdx.x / kWave;
     const bool use_w = A.use_sigma != 0;                  // wave uniform: selects the row loop of a pass, nothing else changes without sigma
     const double *wsh = smem + kMaxB;                     // [kMaxB] 1 / sigma per measurement -- only allocated with sigma
-    double *ytile = smem + (use_w ? 2 * kMaxB : kMaxB) + (size_t)wave * PK::per_wave(n_b);  // [ceil(n_b/2)][64][2], wave-uniform base
+    double *ytile = smem + (use_w ? 2 * kMaxB : kMaxB) + (size_t)wave * PK::per_wave_f64(n_b);  // [ceil(n_b/2)][64][2], wave-uniform base
     double *ysh = ytile + 2 * lane;                                         // this lane's pair column
     double *rpark = ytile + (size_t)((n_b + 1) & ~1) * kWave + lane;        // [NR][64]
     double *vpark = rpark + (size_t)PK::NR * kWave;                           // [NV][64]

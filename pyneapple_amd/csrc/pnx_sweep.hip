@@ -18,6 +18,7 @@
 
 #include "pnx_curvefit_kernel.hpp"
 #include "pnx_internal.hpp"
+#include "pnx_launch.hpp"
 #include "pnx_model_t.hpp"
 
 namespace pnx {
@@ -327,15 +328,8 @@ static int launch_sweep_full(const SweepArgs<T> &a, long long n_full, int cus, i
     const size_t shmem = sizeof(T) * (kMaxB + (size_t)(block / kWave) * kWave * (NB + 1));
     long long want = (n_full + 3) / 4, cap = (long long)cus * bpc;
     const int grid = (int)(want < cap ? want : cap);
-    static bool attr_done[64] = {false};  // function attributes are per device
-    int cur_dev = 0;
-    (void)hipGetDevice(&cur_dev);
-    bool &attr_set = attr_done[cur_dev & 63];
-    if (!attr_set) {
-        hipError_t ea = hipFuncSetAttribute((const void *)sweep_full_kernel<MODEL, T, NB>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (ea != hipSuccess) return set_error(PNX_ERR_HIP, "hipFuncSetAttribute: %s", hipGetErrorString(ea));
-        attr_set = true;
-    }
+    if (hipError_t ea = allow_big_lds<sweep_full_kernel<MODEL, T, NB>>(); ea != hipSuccess)
+        return set_error(PNX_ERR_HIP, "hipFuncSetAttribute: %s", hipGetErrorString(ea));
     hipLaunchKernelGGL((sweep_full_kernel<MODEL, T, NB>), dim3(grid), dim3(block), shmem, st, a, n_full);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return set_error(PNX_ERR_HIP, "sweep launch: %s", hipGetErrorString(e));
@@ -358,15 +352,8 @@ static int launch_sweep_nt(const SweepArgs<T> &a, int cus, hipStream_t st) {
     long long cap = (long long)cus * bpc;  // memory-bound: ~2048 blocks, grid-stride the rest
     int grid = (int)(want < cap ? want : cap);
     if (grid < 1) grid = 1;
-    static bool attr_done[64] = {false};  // function attributes are per device
-    int cur_dev = 0;
-    (void)hipGetDevice(&cur_dev);
-    bool &attr_set = attr_done[cur_dev & 63];
-    if (!attr_set) {
-        hipError_t ea = hipFuncSetAttribute((const void *)sweep_kernel<MODEL, T, NT>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (ea != hipSuccess) return set_error(PNX_ERR_HIP, "hipFuncSetAttribute: %s", hipGetErrorString(ea));
-        attr_set = true;
-    }
+    if (hipError_t ea = allow_big_lds<sweep_kernel<MODEL, T, NT>>(); ea != hipSuccess)
+        return set_error(PNX_ERR_HIP, "hipFuncSetAttribute: %s", hipGetErrorString(ea));
     if (dev_getenv("PNX_LAUNCH_TRACE")) {  // diagnostic: the copy path is the kernel's own predicate (vec_ok)
         const bool vec = (a.n_b % (int)(16 / sizeof(T))) == 0 && (reinterpret_cast<uintptr_t>(a.y) % 16) == 0;
         fprintf(stderr, "[pnx launch] sweep generic model=%d f%d n_b=%d v_first=%lld block=%d lds=%zu grid=%d copy=%s\n", MODEL,
