@@ -414,6 +414,32 @@ PNX_API int pnx_curvefit_grid_start_f64(const pnx_curvefit_opts *opts, int64_t n
                                 const double *atoms, const double *fixed, const double *lo, const double *hi, int project_amplitude,
                                 double *p0_out, int32_t *best, double *cost, int mem, int device, void *stream);
 /*
+ * Posterior over a dictionary of parameter vectors: the Bayesian grid fit of noisy IVIM data.  The arguments,
+ * the dictionary, the weighting, the (projected) amplitude a_g(v) and the cost c_g(v) are pnx_curvefit_grid_start_f64's, and so
+ * are its refusals (per_voxel_p0_bounds, fixed_per_voxel, queue_order, projection without a free S0, an atom outside lo / hi).
+ *   log_prior (n_atoms,) host or NULL (uniform): every entry finite or -inf, at least one finite (PNX_ERR_INVALID otherwise);
+ *     an atom at -inf is excluded.
+ *   noise_sd > 0: known Gaussian noise sd in the units of the (sigma-weighted) signal; == 0: the noise scale is marginalised under
+ *     a Jeffreys prior; negative or non-finite: PNX_ERR_INVALID.
+ * Per voxel v, in fp64, with tol_v = 4 n_b 2^-52 (||y_v||^2 + max_g ||s_g||^2), the rounding bound of the expanded cost:
+ *   l_g = log_prior_g - c_g / noise_sd^2                      (known noise)
+ *   l_g = log_prior_g - (nu / 2) log(max(c_g, tol_v))         (marginalised; nu = n_b, n_b - 1 with project_amplitude)
+ *   L = log sum_g exp(l_g);  W_g = exp(l_g - L);  padded and excluded atoms have weight 0.
+ *   mean[k] = sum_g W_g theta_kg, theta_kg = atoms[k, g], or a_g(v) in a projected S0 row;
+ *   sd[k] = sqrt(max(0, sum_g W_g (theta_kg - mean[k])^2)), accumulated by a weighted Welford / Chan merge (no E[x^2] - mean^2);
+ *   map_atom = argmax_g l_g, the lowest index among equal l;  map_p = that atom's parameters, copied (its S0 row holds a_g(v)
+ *     under projection);  log_evidence = L - log sum_g exp(log_prior_g);  ess = (sum W)^2 / sum W^2 in [1, n_atoms].
+ * A voxel with a non-finite (weighted) signal gets NaN in every floating output and map_atom = -1; its neighbours are not affected.
+ *   mean, sd, map_p (n_free, n_vox); map_atom (n_vox) int32; log_evidence, ess (n_vox): out, host|device as `mem`; all but mean
+ *   may be NULL.  PNX_MEM_DEVICE only enqueues; PNX_MEM_HOST goes through the chunk ring.  The (n_vox, n_atoms) matrix never
+ *   reaches memory.
+ */
+PNX_API int pnx_curvefit_grid_posterior_f64(const pnx_curvefit_opts *opts, int64_t n_vox, const double *b, const double *y, int n_atoms,
+                                    const double *atoms, const double *fixed, const double *lo, const double *hi,
+                                    int project_amplitude, const double *log_prior, double noise_sd, double *mean, double *sd,
+                                    int32_t *map_atom, double *map_p, double *log_evidence, double *ess, int mem, int device,
+                                    void *stream);
+/*
  * Log-linear mono-exponential fit, ln S = ln S0 - b D by (weighted) linear least squares per voxel: the ADC
  * map, step 1 of a segmented IVIM fit, a cheap source of S0 / D start values.  A closed form over one pass of the data: a voxel
  * costs its signal row in and its results out.  Per voxel, in fp64, in the order written:

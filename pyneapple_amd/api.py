@@ -279,6 +279,80 @@ def grid_start_device(opts, n_vox, b, y, atoms, fixed, lo, hi, project_amplitude
                                              stream))
 
 
+def grid_posterior_slab_atoms(n_b, n_free):
+    """Atoms per LDS slab of the posterior kernel (grid_posterior_slab of csrc/pnx_grid_posterior_args.hpp): the widest multiple of
+    16, at most 256, whose dictionary rows ([n_b padded to 4][stride], stride = 16 mod 32) and 3 + n_free values per atom fit 64 KB."""
+    kpad, width = (int(n_b) + 3) & ~3, 16
+    for w in range(16, 257, 16):
+        if kpad * (w if w & 16 else w + 16) + (3 + int(n_free)) * w <= 8192:
+            width = w
+    return width
+
+
+def _posterior_log_prior(log_prior, n_atoms):
+    if log_prior is None:
+        return None
+    lp = np.ascontiguousarray(log_prior, np.float64)
+    if lp.shape != (n_atoms,):
+        raise ValueError(f"log_prior has shape {lp.shape}, expected ({n_atoms},): one entry per atom")
+    return lp
+
+
+def grid_posterior(model, b, y, atoms, lo, hi, *, log_prior=None, noise_sd=0.0, fixed_idx=(), fixed_vals=None, sigma=None,
+                   project_amplitude=False, t1_mode=0, tr=0., tm=0., device=0, out=None):
+    """Posterior of every voxel over a dictionary of parameter vectors on host (numpy) arrays (pnx_curvefit_grid_posterior_f64;
+    method: include/pnx.h).  The arguments of `grid_start`, and
+    log_prior: None (uniform) or (n_atoms,) log prior weights, finite or -inf (an atom at -inf is excluded);
+    noise_sd: > 0 a known Gaussian noise sd in the units of the (sigma-weighted) signal, 0 (default) marginalises the noise scale.
+    Returns dict(mean, sd, map_p (n_free, n_vox), map_atom (n_vox,) int32 (-1 for a non-finite signal, whose floating outputs are
+    NaN), log_evidence (n_vox,), ess (n_vox,) the effective number of atoms that carry the posterior: near 1 the grid is too
+    coarse for sd to mean anything).  `out`: optional dict of preallocated result arrays under the same keys."""
+    _lib.require_device()
+    b = np.ascontiguousarray(b, np.float64)
+    y = np.ascontiguousarray(np.atleast_2d(y), np.float64)
+    n_vox, n_b = y.shape
+    if b.shape != (n_b,):
+        raise ValueError(f"b has shape {b.shape}, expected ({n_b},)")
+    atoms, lo, hi = (np.ascontiguousarray(a, np.float64) for a in (atoms, lo, hi))
+    fv = None
+    if len(fixed_idx):
+        fv = np.ascontiguousarray(fixed_vals, np.float64)
+        if fv.ndim != 1:
+            raise ValueError("grid_posterior takes shared fixed values (n_fixed,): per-voxel fixed maps are not built")
+    o = make_opts(model, n_b, fixed_idx, jac="analytic", t1_mode=t1_mode, tr=tr, tm=tm, sigma=sigma)
+    n = o.n_free
+    if atoms.ndim != 2 or atoms.shape[0] != n or lo.shape != (n,) or hi.shape != (n,):
+        raise ValueError(f"atoms must have shape ({n}, n_atoms), lo / hi ({n},)")
+    if fv is not None and fv.shape != (o.n_fixed,):
+        raise ValueError("fixed_vals has the wrong shape")
+    lp = _posterior_log_prior(log_prior, atoms.shape[1])
+    res = {key: _out(out, key, (n, n_vox), np.float64) for key in ("mean", "sd", "map_p")}
+    res["map_atom"] = _out(out, "map_atom", (n_vox,), np.int32)
+    res["log_evidence"] = _out(out, "log_evidence", (n_vox,), np.float64)
+    res["ess"] = _out(out, "ess", (n_vox,), np.float64)
+    check(load().pnx_curvefit_grid_posterior_f64(C.byref(o), n_vox, ptr(b), ptr(y), int(atoms.shape[1]), ptr(atoms), ptr(fv), ptr(lo), ptr(hi),
+                                                 int(bool(project_amplitude)), ptr(lp), float(noise_sd), ptr(res["mean"]), ptr(res["sd"]),
+                                                 ptr(res["map_atom"]), ptr(res["map_p"]), ptr(res["log_evidence"]), ptr(res["ess"]), MEM_HOST,
+                                                 int(device), None))
+    return res
+
+
+def grid_posterior_device(opts, n_vox, b, y, atoms, fixed, lo, hi, project_amplitude, log_prior, noise_sd, mean, sd, map_atom, map_p,
+                          log_evidence, ess, device, stream=None):
+    """Enqueue the grid posterior on HBM-resident float64 torch tensors (asynchronous; caller synchronises): y (n_vox, n_b), mean /
+    sd / map_p (n_free, n_vox), map_atom (n_vox,) int32, log_evidence / ess (n_vox,) on the device, all but mean may be None; b,
+    atoms (n_free, n_atoms), shared fixed values, lo, hi and log_prior (n_atoms,) or None are host arrays.  `opts` from make_opts."""
+    b, atoms, lo, hi = (np.ascontiguousarray(a, np.float64) for a in (b, atoms, lo, hi))
+    if fixed is not None:
+        fixed = np.ascontiguousarray(fixed, np.float64)
+    if atoms.ndim != 2:
+        raise ValueError("atoms must have shape (n_free, n_atoms)")
+    lp = _posterior_log_prior(log_prior, atoms.shape[1])
+    check(load().pnx_curvefit_grid_posterior_f64(C.byref(opts), int(n_vox), ptr(b), ptr(y), int(atoms.shape[1]), ptr(atoms), ptr(fixed), ptr(lo),
+                                                 ptr(hi), int(bool(project_amplitude)), ptr(lp), float(noise_sd), ptr(mean), ptr(sd),
+                                                 ptr(map_atom), ptr(map_p), ptr(log_evidence), ptr(ess), MEM_DEVICE, int(device), stream))
+
+
 LOGLINEAR_WEIGHTING = {"none": 0, "signal2": 1}  # w = 1 / w = y^2 (include/pnx.h)
 LOGLINEAR_MAX_REWEIGHT = 8  # kLogLinMaxReweight of csrc/pnx_loglin_args.hpp
 

@@ -10,10 +10,11 @@ its constraint sum(f_i) <= 1, not in its algorithm (pnx_curvefit_simplex_f64).
 
 `HipLogLinearSolver` has no counterpart in the reference: the linearised mono-exponential fit as a closed form
 (pnx_loglinear_f64), with the reference's solver contract.  `HipPeelSolver` likewise: exponential peeling of the bi- and
-tri-exponential models (pnx_peel_f64).
+tri-exponential models (pnx_peel_f64).  `HipBayesGridSolver` likewise: posterior mean and sd over a parameter grid
+(pnx_curvefit_grid_posterior_f64).
 
 Registered under the `pyneapple.solvers` entry-point group (pyproject.toml) as `hip_curvefit` / `hip_nnls` /
-`hip_constrained_curvefit` / `hip_loglinear` / `hip_peel`;
+`hip_constrained_curvefit` / `hip_loglinear` / `hip_peel` / `hip_bayes_grid`;
 extra scalar keys of `[Fitting.solver]` arrive as keyword arguments (io/toml.py:328-338): `device`,
 `n_gpus`, `jacobian`.
 """
@@ -107,6 +108,39 @@ def _shard_device(first: int, k: int) -> int:
 def _split(n: int, parts: int):
     edges = np.linspace(0, n, parts + 1).astype(np.int64)
     return [(int(a), int(b)) for a, b in zip(edges[:-1], edges[1:]) if b > a]
+
+
+def _grid_atoms(what, model, kernel_model, p0, bounds, grid, project, project_name=None):
+    """The atoms of a dictionary from a grid dict (`p0_grid` of HipCurveFitSolver, `grid` of HipBayesGridSolver; `what` names the
+    argument in the messages): the Cartesian product of the sequences in `model.param_names` order, the last parameter fastest; a
+    parameter the dict does not name takes its scalar `p0`.  Returns (grid as lists, project, atoms (n_free, n_atoms))."""
+    import itertools
+
+    names = list(model.param_names)
+    if not isinstance(grid, dict):
+        raise ValueError(f"{what} must be a dict from parameter name to a sequence of candidate values")
+    unknown = [n for n in grid if n not in names]
+    if unknown:
+        raise ValueError(f"{what} names parameters the model does not fit: {unknown} (free parameters: {names})")
+    has_s0 = "S0" in names and kernel_model in api.PROJECT_MODELS
+    if project is None:
+        project = has_s0
+    if project and not has_s0:
+        raise ValueError(f"{project_name or what + '_project'}=True needs a model with a free amplitude S0 {api.PROJECT_MODELS}, not {kernel_model!r}")
+    axes = []
+    for n in names:
+        vals = np.atleast_1d(np.asarray(grid[n], float)) if n in grid else np.array([float(p0[n])])
+        lo, hi = bounds[n]
+        if vals.ndim != 1 or vals.size < 1:
+            raise ValueError(f"{what}[{n!r}] must be a non-empty 1-D sequence of values")
+        if not ((vals >= lo) & (vals <= hi)).all():
+            raise ValueError(f"{what}[{n!r}] holds a value outside the bounds ({lo}, {hi}) of {n}")
+        axes.append(vals)
+    n_atoms = int(np.prod([a.size for a in axes], dtype=np.int64))
+    if n_atoms > api.GRID_MAX_ATOMS:
+        raise ValueError(f"{what} spans {n_atoms} atoms, more than the {api.GRID_MAX_ATOMS} the dictionary search takes")
+    atoms = np.ascontiguousarray(np.array(list(itertools.product(*axes)), float).T)  # (n_free, n_atoms)
+    return {n: list(map(float, np.atleast_1d(v))) for n, v in grid.items()}, bool(project), atoms
 
 
 class HipCurveFitSolver(CurveFitBase):
@@ -236,37 +270,10 @@ class HipCurveFitSolver(CurveFitBase):
             if project:
                 raise ValueError("p0_grid_project=True needs a p0_grid")
             return
-        import itertools
-
         if self.precision == "float32" or self.io_dtype is not np.float64:
             raise ValueError("p0_grid is built for precision='float64' and io_dtype='float64': the dictionary search reads and "
                              "writes float64 arrays")
-        names = list(self.model.param_names)
-        if not isinstance(p0_grid, dict):
-            raise ValueError("p0_grid must be a dict from parameter name to a sequence of candidate values")
-        unknown = [n for n in p0_grid if n not in names]
-        if unknown:
-            raise ValueError(f"p0_grid names parameters the model does not fit: {unknown} (free parameters: {names})")
-        has_s0 = "S0" in names and self._kernel_model in api.PROJECT_MODELS
-        if project is None:
-            project = has_s0
-        if project and not has_s0:
-            raise ValueError(f"p0_grid_project=True needs a model with a free amplitude S0 {api.PROJECT_MODELS}, not {self._kernel_model!r}")
-        axes = []
-        for n in names:
-            vals = np.atleast_1d(np.asarray(p0_grid[n], float)) if n in p0_grid else np.array([float(self.p0[n])])
-            lo, hi = self.bounds[n]
-            if vals.ndim != 1 or vals.size < 1:
-                raise ValueError(f"p0_grid[{n!r}] must be a non-empty 1-D sequence of values")
-            if not ((vals >= lo) & (vals <= hi)).all():
-                raise ValueError(f"p0_grid[{n!r}] holds a value outside the bounds ({lo}, {hi}) of {n}")
-            axes.append(vals)
-        n_atoms = int(np.prod([a.size for a in axes], dtype=np.int64))
-        if n_atoms > api.GRID_MAX_ATOMS:
-            raise ValueError(f"p0_grid spans {n_atoms} atoms, more than the {api.GRID_MAX_ATOMS} the dictionary search takes")
-        self.p0_grid = {n: list(map(float, np.atleast_1d(v))) for n, v in p0_grid.items()}
-        self.p0_grid_project = bool(project)
-        self._p0_atoms = np.ascontiguousarray(np.array(list(itertools.product(*axes)), float).T)  # (n_free, n_atoms)
+        self.p0_grid, self.p0_grid_project, self._p0_atoms = _grid_atoms("p0_grid", self.model, self._kernel_model, self.p0, self.bounds, p0_grid, project)
 
     # ------------------------------------------------------------------ p0_peel: start values from the peeling fit
     def _set_p0_peel(self, p0_peel):
@@ -755,6 +762,113 @@ class HipPeelSolver(RefBaseSolver):
             params.T, None, status > 0, lambda i, st=status: None if st[i] > 0 else _PEEL_MESSAGES.get(int(st[i]), "fit failed"))
         self.params_ = {name: [float(params[i, 0])] if n_pixels == 1 else params[i] for i, name in enumerate(names)}
         self.diagnostics_ = {"n_pixels": n_pixels, "status": status, "n_used": res["n_used"], "ss_res": res["ss_res"]}
+        return self
+
+
+_BAYES_MESSAGES = {-2: "array must not contain infs or NaNs"}
+
+
+class HipBayesGridSolver(RefBaseSolver):
+    """Bayesian grid fit per voxel (pnx_curvefit_grid_posterior_f64, include/pnx.h): posterior mean and standard deviation of every
+    parameter over a grid of parameter vectors, with a per-atom prior table and a known or marginalised noise scale -- the estimator
+    for noisy IVIM data, where a non-linear fit ends in a tail of stragglers and a point estimate says nothing of its uncertainty.
+    No iteration: the cost does not depend on the noise.  Registered as `hip_bayes_grid`; no counterpart in the reference, whose
+    solver contract it keeps.
+
+    model: any of the seven layouts, with shared fixed parameters and the T1 / STEAM factor as the curve fit takes them.  `max_iter`,
+    `tol` are accepted because the TOML loader always passes them; a closed form has no use for either.  Arguments:
+        grid: dict from parameter name to a sequence of values, the meaning and the rules of HipCurveFitSolver's `p0_grid`: the
+            atoms are the Cartesian product in `model.param_names` order, the last parameter fastest; a parameter the dict does not
+            name takes its scalar `p0`; every value inside `bounds`; at most 4096 atoms.
+        p0: {name: value} for the parameters `grid` does not name.  bounds: {name: (lo, hi)} for every parameter.
+        noise_sd: None / 0 (default) marginalises the noise scale under a Jeffreys prior; > 0 is a known Gaussian noise sd in the
+            units of the (sigma-weighted) signal.
+        log_prior: None (uniform) or (n_atoms,) log weights in the order of the atoms (itertools.product over `model.param_names`);
+            -inf excludes an atom.
+        project: fit the amplitude S0 per voxel and atom, clipped to its bounds, instead of taking it from the grid.  Default:
+            True exactly when the model has a free S0 (as p0_grid_project).
+        sigma: None, a scalar or (n_b,), as HipCurveFitSolver's.  device: HIP device index.
+    Not built, hence a ValueError: per-pixel fixed parameters (the dictionary would differ from voxel to voxel), io_dtype or
+    precision "float32" (the posterior reads and writes float64 arrays and exponentiates in fp64).
+    Any other keyword (the reference's solver arguments: method, multi_threading, ...) is accepted and ignored.
+    After fit: params_ = the posterior mean keyed by the model's names; diagnostics_ {"posterior_sd", "map" (dicts name ->
+    (n_pixels,)), "map_atom", "log_evidence", "ess", "n_pixels"} (no "pcov": the sd is the uncertainty; ess near 1 says the grid
+    is too coarse for it); pixel_results_ with success = the voxel's signal was finite."""
+
+    def __init__(self, model: Any, grid=None, max_iter: int = 250, tol: float = 1e-8, p0: dict[str, float] | None = None,
+                 bounds: dict[str, tuple[float, float]] | None = None, noise_sd: float | None = None, log_prior=None, project=None,
+                 sigma=None, device: int = 0, io_dtype: str = "float64", precision: str = "float64", **ignored_reference_kwargs):
+        RefBaseSolver.__init__(self, model=model, max_iter=max_iter, tol=tol, verbose=bool(ignored_reference_kwargs.pop("verbose", False)))
+        self._kernel_model = kernel_model_key(model)
+        self._kernel_t1 = kernel_t1(model)
+        if _io_dtype(io_dtype) is not np.float64 or precision != "float64":
+            raise ValueError("HipBayesGridSolver is built for precision='float64' and io_dtype='float64': the posterior reads and writes "
+                             "float64 arrays and exponentiates in fp64")
+        if grid is None:
+            raise ValueError("grid is required: a dict from parameter name to a sequence of values")
+        names = list(model.param_names)
+        if bounds is None:
+            raise ValueError(f"bounds is required: {{name: (lo, hi)}} for every parameter of {names}")
+        _validate_parameter_names(bounds, names)
+        if isinstance(grid, dict):
+            missing = [n for n in names if n not in grid and n not in (p0 or {})]
+            if missing:
+                raise ValueError(f"neither grid nor p0 holds a value for {missing}")
+        self.grid, self.project, self._atoms = _grid_atoms("grid", model, self._kernel_model, p0 or {}, bounds, grid, project, "project")
+        self.noise_sd = 0.0 if noise_sd is None else float(noise_sd)
+        if not (np.isfinite(self.noise_sd) and self.noise_sd >= 0.0):
+            raise ValueError(f"noise_sd must be None / 0 (marginalised) or a finite positive standard deviation, got {noise_sd!r}")
+        self.log_prior = None
+        if log_prior is not None:
+            lp = np.ascontiguousarray(log_prior, np.float64).reshape(-1)
+            if lp.shape != (self._atoms.shape[1],):
+                raise ValueError(f"log_prior has {lp.size} entries for {self._atoms.shape[1]} atoms (one per atom, in the order of "
+                                 "itertools.product over model.param_names)")
+            if np.isnan(lp).any() or (lp == np.inf).any() or not np.isfinite(lp).any():
+                raise ValueError("log_prior entries must be finite or -inf, at least one of them finite")
+            self.log_prior = lp
+        self.sigma = None
+        if sigma is not None:
+            self.sigma = np.asarray(sigma, float)
+            if self.sigma.ndim > 1 and self.sigma.size != 1:
+                raise ValueError("HipBayesGridSolver implements a scalar or 1-D sigma (one standard deviation per b-value)")
+            self.sigma = self.sigma.reshape(-1)
+        self.p0 = p0
+        self.bounds = bounds
+        self.device = int(device)
+        self.io_dtype = np.float64
+        self.solver_kwargs = ignored_reference_kwargs
+
+    def fit(self, xdata: np.ndarray, ydata: np.ndarray, pixel_fixed_params=None, **fit_kwargs) -> "HipBayesGridSolver":
+        if pixel_fixed_params:
+            raise ValueError("HipBayesGridSolver is not built with per-pixel fixed parameters (pixel_fixed_params): the dictionary "
+                             "would differ from voxel to voxel")
+        self._reset_state()
+        xdata = np.asarray(xdata)
+        ydata = np.asarray(ydata)
+        _validate_data_shapes(xdata, ydata)
+        if ydata.ndim == 1:
+            ydata = ydata[np.newaxis, :]
+        if ydata.ndim > 2:
+            raise ValueError(f"ydata must be 1D or 2D array, but got shape {ydata.shape}.")
+        n_pixels = ydata.shape[0]
+        names = list(self.model.param_names)
+        all_names = list(self.model._all_param_names)
+        fixed = getattr(self.model, "fixed_params", None) or {}
+        fixed_idx = [i for i, n in enumerate(all_names) if n in fixed]
+        fixed_vals = np.array([float(fixed[all_names[i]]) for i in fixed_idx]) if fixed_idx else None
+        lo = np.array([self.bounds[n][0] for n in names], float)
+        hi = np.array([self.bounds[n][1] for n in names], float)
+        res = api.grid_posterior(self._kernel_model, xdata, ydata, self._atoms, lo, hi, log_prior=self.log_prior, noise_sd=self.noise_sd,
+                                 fixed_idx=fixed_idx, fixed_vals=fixed_vals, sigma=self.sigma, project_amplitude=self.project,
+                                 device=self.device, **self._kernel_t1)
+        mean, atom = res["mean"], res["map_atom"]
+        self.pixel_results_ = PixelResultsView(mean.T, None, atom >= 0,
+                                               lambda i, a=atom: None if a[i] >= 0 else _BAYES_MESSAGES[-2])
+        self.params_ = {name: [float(mean[i, 0])] if n_pixels == 1 else mean[i] for i, name in enumerate(names)}
+        self.diagnostics_ = {"posterior_sd": {n: res["sd"][i] for i, n in enumerate(names)},
+                             "map": {n: res["map_p"][i] for i, n in enumerate(names)}, "map_atom": atom,
+                             "log_evidence": res["log_evidence"], "ess": res["ess"], "n_pixels": n_pixels}
         return self
 
 
