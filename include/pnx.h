@@ -440,6 +440,45 @@ PNX_API int pnx_curvefit_grid_posterior_f64(const pnx_curvefit_opts *opts, int64
                                     int32_t *map_atom, double *map_p, double *log_evidence, double *ess, int mem, int device,
                                     void *stream);
 /*
+ * Variable-projection dictionary fit (VARPRO, separable least squares): only the NON-LINEAR parameters of a
+ * layout -- the K rates, and T1 where it is free -- are on the grid; the fractions and S0 of every voxel-atom pair come in closed
+ * form.  Every layout is sum_j a_j phi_j(b) with K = 1 (mono), 2 (bi) or 3 (tri) unit columns phi_j = model(b; one-hot fractions,
+ * S0 = 1) / sigma -- bi reduced: f1 = 1 and f1 = 0; tri reduced and tri S0: (f1, f2) = (1,0), (0,1), (0,0); full layouts: one
+ * f_j = 1 -- evaluated by pnx_curvefit_predict_f64's kernel (the fit's own exp, T1 / STEAM factor, shared fixed rates).
+ * Per atom g: M = Phi^T Phi.  Per voxel v and atom g, with y_w = y / sigma and c = Phi^T y_w (on the fp64 matrix cores):
+ *   free amplitudes (mono, bi / tri full, bi / tri S0):  a_hat = M^-1 c;
+ *   sum-to-one (bi / tri reduced):  a_hat_{j<K} minimises || y_w - phi_K - sum_{j<K} a_j (phi_j - phi_K) ||;
+ *   clip into the box (an exact feasible point, no division per pair):
+ *     mono     S0 = clip(a_hat_1, lo_S0, hi_S0);
+ *     full     a'_j = clip(a_hat_j, lo_fj, hi_fj);
+ *     reduced  a'_j = clip(a_hat_j, lo_fj, hi_fj) for j < K,  a'_K = 1 - sum_{j<K} a'_j;
+ *     S0       S = clip(sum a_hat, lo_S0, hi_S0),  a'_j = clip(a_hat_j, lo_fj S, hi_fj S) for j < K,  a'_K = S - sum_{j<K} a'_j;
+ *              reported S0 = S, f_j = a'_j / S, or lo_fj when S = 0;
+ *   cost_g(v) = 0.5 ||y_w||^2 - c^T a' + 0.5 a'^T M a': the true cost of the reported parameter vector.
+ * best[v] = the argmin over g, the lowest index among equal costs; p_out[:, v] = that atom's non-linear values, copied, and the
+ * clipped amplitudes mapped to the layout's fractions / S0; cost[v] its cost; clipped[v] = 1 when a clip was active at the winner.
+ * The clipped optimum is exact for K = 1; for K > 1 it is a feasible point, optimal whenever no clip is active.  As in the bounded
+ * fit the box is the feasible set: 1 - f1 - f2 may be negative (pnx_curvefit_simplex_f64 is the tool for that).  An atom whose M
+ * is not positive definite in fp64 gets a_hat = 0.  The expanded cost carries the rounding of K + 1 dot products of n_b terms and
+ * of the stored inverse: costs closer than about 4 (n_b + kappa(M)) 2^-52 (||y_w||^2 + ||a'||_1^2 max_j ||phi_j||^2) may swap.
+ * A voxel with a non-finite (weighted) signal gets best = -1, cost = NaN, clipped = 0 and p_out = fallback; its neighbours are
+ * bit-identical to a run without it.
+ *   opts: model, n_b, n_free, n_fixed, free_idx, fixed_idx, t1_mode, tr, tm, sigma are read;
+ *   b (n_b,) host; y (n_vox, n_b) host|device; nl_atoms (n_nl, n_atoms) host: the free non-linear parameters of every atom,
+ *   one row per free rate / T1 in the order of free_idx, 1 <= n_atoms <= 4096; fixed (n_fixed,) host or NULL (rates and T1 only);
+ *   lo, hi (n_free,) host; fallback (n_free,) host, inside lo / hi;
+ *   p_out (n_free, n_vox), best (n_vox) int32 or NULL, cost (n_vox) or NULL, clipped (n_vox) int8 or NULL: out, host|device as `mem`.
+ * PNX_MEM_DEVICE only enqueues (the dictionary lives in a stream-ordered buffer); PNX_MEM_HOST goes through the chunk ring.  The
+ * (n_vox, n_atoms) product never reaches memory.
+ * Refused with a message that names the argument, before any device work: per_voxel_p0_bounds, fixed_per_voxel, queue_order, a
+ * fixed fraction or a fixed S0 (PNX_ERR_UNSUPPORTED); n_atoms out of range, n_b <= K, an atom with two exactly equal rates (M is
+ * singular), a non-linear value outside its bounds, lo > hi of a fraction or S0, lo_S0 < 0, a fallback outside the bounds
+ * (PNX_ERR_INVALID).
+ */
+PNX_API int pnx_curvefit_varpro_f64(const pnx_curvefit_opts *opts, int64_t n_vox, const double *b, const double *y, int n_atoms,
+                            const double *nl_atoms, const double *fixed, const double *lo, const double *hi, const double *fallback,
+                            double *p_out, int32_t *best, double *cost, int8_t *clipped, int mem, int device, void *stream);
+/*
  * Log-linear mono-exponential fit, ln S = ln S0 - b D by (weighted) linear least squares per voxel: the ADC
  * map, step 1 of a segmented IVIM fit, a cheap source of S0 / D start values.  A closed form over one pass of the data: a voxel
  * costs its signal row in and its results out.  Per voxel, in fp64, in the order written:

@@ -353,6 +353,85 @@ def grid_posterior_device(opts, n_vox, b, y, atoms, fixed, lo, hi, project_ampli
                                                  ptr(map_atom), ptr(map_p), ptr(log_evidence), ptr(ess), MEM_DEVICE, int(device), stream))
 
 
+VARPRO_COMPARTMENTS = {"mono": 1, "bi_reduced": 2, "bi_s0": 2, "bi_full": 2, "tri_reduced": 3, "tri_s0": 3, "tri_full": 3}
+
+
+def varpro_linear_names(model):
+    """The linear parameters of a layout (fractions and S0), which pnx_curvefit_varpro_f64 solves in closed form."""
+    return [n for n in MODEL_PARAM_NAMES[model] if not n.startswith("D")]
+
+
+def varpro_slab_atoms(n_b, k):
+    """Atoms per LDS slab of the variable-projection kernel (varpro_slab of csrc/pnx_varpro_args.hpp): the widest multiple of 16, at
+    most 256, whose k blocks of dictionary rows ([n_b padded to 4][stride], stride = 16 mod 32) and k (k + 1) constants per atom
+    fit 64 KB."""
+    kpad, k, width = (int(n_b) + 3) & ~3, int(k), 16
+    for w in range(16, 257, 16):
+        if k * kpad * (w if w & 16 else w + 16) + k * (k + 1) * w <= 8192:
+            width = w
+    return width
+
+
+def _varpro_args(model, n_b, nl_atoms, lo, hi, fallback, fixed_idx, fixed_vals, sigma, t1_mode, tr, tm):
+    nl_atoms, lo, hi, fallback = (np.ascontiguousarray(a, np.float64) for a in (nl_atoms, lo, hi, fallback))
+    fv = None
+    if len(fixed_idx):
+        fv = np.ascontiguousarray(fixed_vals, np.float64)
+        if fv.ndim != 1:
+            raise ValueError("varpro takes shared fixed values (n_fixed,): per-voxel fixed maps are not built")
+    o = make_opts(model, n_b, fixed_idx, jac="analytic", t1_mode=t1_mode, tr=tr, tm=tm, sigma=sigma)
+    n = o.n_free
+    if nl_atoms.ndim != 2 or lo.shape != (n,) or hi.shape != (n,) or fallback.shape != (n,):
+        raise ValueError(f"nl_atoms must have shape (n_nonlinear_free, n_atoms), lo / hi / fallback ({n},)")
+    if fv is not None and fv.shape != (o.n_fixed,):
+        raise ValueError("fixed_vals has the wrong shape")
+    lin = {MODEL_PARAM_NAMES[model].index(name) for name in varpro_linear_names(model)}
+    n_nl = sum(1 for k in range(n) if o.free_idx[k] not in lin)
+    if nl_atoms.shape[0] != n_nl:
+        raise ValueError(f"nl_atoms has {nl_atoms.shape[0]} rows, the model has {n_nl} free non-linear parameters (rates, T1)")
+    return o, nl_atoms, lo, hi, fallback, fv
+
+
+def varpro(model, b, y, nl_atoms, lo, hi, fallback, *, fixed_idx=(), fixed_vals=None, sigma=None, t1_mode=0, tr=0., tm=0., device=0,
+           out=None):
+    """Variable-projection dictionary fit on host (numpy) arrays (pnx_curvefit_varpro_f64; method: include/pnx.h): only the
+    non-linear parameters are on the grid, the fractions and S0 of every voxel and atom come in closed form, clipped into lo / hi.
+
+    nl_atoms (n_nonlinear_free, n_atoms <= 4096): the free rates (and T1) of every atom, one row per free non-linear parameter in
+    the model's order; lo, hi, fallback (n_free,) for every free parameter; fixed_idx / fixed_vals (rates and T1 only) and sigma
+    as `curvefit` takes them (shared values only).  Returns dict(params (n_free, n_vox) -- a per-voxel start for `curvefit` --,
+    atom (n_vox,) int32 index of the chosen atom, -1 for a non-finite signal (whose params are `fallback`), cost (n_vox,)
+    0.5 ||(y - model(params)) / sigma||^2, clipped (n_vox,) int8: a clip was active at the winner).
+    `out`: optional dict of preallocated result arrays under the same keys."""
+    _lib.require_device()
+    b = np.ascontiguousarray(b, np.float64)
+    y = np.ascontiguousarray(np.atleast_2d(y), np.float64)
+    n_vox, n_b = y.shape
+    if b.shape != (n_b,):
+        raise ValueError(f"b has shape {b.shape}, expected ({n_b},)")
+    o, nl_atoms, lo, hi, fallback, fv = _varpro_args(model, n_b, nl_atoms, lo, hi, fallback, fixed_idx, fixed_vals, sigma, t1_mode, tr, tm)
+    res = dict(params=_out(out, "params", (o.n_free, n_vox), np.float64), atom=_out(out, "atom", (n_vox,), np.int32),
+               cost=_out(out, "cost", (n_vox,), np.float64), clipped=_out(out, "clipped", (n_vox,), np.int8))
+    check(load().pnx_curvefit_varpro_f64(C.byref(o), n_vox, ptr(b), ptr(y), int(nl_atoms.shape[1]), ptr(nl_atoms), ptr(fv), ptr(lo), ptr(hi),
+                                         ptr(fallback), ptr(res["params"]), ptr(res["atom"]), ptr(res["cost"]), ptr(res["clipped"]),
+                                         MEM_HOST, int(device), None))
+    return res
+
+
+def varpro_device(opts, n_vox, b, y, nl_atoms, fixed, lo, hi, fallback, params, atom, cost, clipped, device, stream=None):
+    """Enqueue the variable-projection fit on HBM-resident float64 torch tensors (asynchronous; caller synchronises): y (n_vox, n_b),
+    params (n_free, n_vox), atom (n_vox,) int32 or None, cost (n_vox,) or None, clipped (n_vox,) int8 or None on the device; b,
+    nl_atoms (n_nonlinear_free, n_atoms), shared fixed values, lo, hi, fallback are host arrays.  `opts` from make_opts."""
+    b, nl_atoms, lo, hi, fallback = (np.ascontiguousarray(a, np.float64) for a in (b, nl_atoms, lo, hi, fallback))
+    if fixed is not None:
+        fixed = np.ascontiguousarray(fixed, np.float64)
+    if nl_atoms.ndim != 2:
+        raise ValueError("nl_atoms must have shape (n_nonlinear_free, n_atoms)")
+    check(load().pnx_curvefit_varpro_f64(C.byref(opts), int(n_vox), ptr(b), ptr(y), int(nl_atoms.shape[1]), ptr(nl_atoms), ptr(fixed), ptr(lo),
+                                         ptr(hi), ptr(fallback), ptr(params), ptr(atom), ptr(cost), ptr(clipped), MEM_DEVICE, int(device),
+                                         stream))
+
+
 LOGLINEAR_WEIGHTING = {"none": 0, "signal2": 1}  # w = 1 / w = y^2 (include/pnx.h)
 LOGLINEAR_MAX_REWEIGHT = 8  # kLogLinMaxReweight of csrc/pnx_loglin_args.hpp
 

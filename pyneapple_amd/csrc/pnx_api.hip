@@ -28,6 +28,7 @@
 #include "pnx_peel.hpp"
 #include "pnx_predict.hpp"
 #include "pnx_simplex.hpp"
+#include "pnx_varpro.hpp"
 
 namespace pnx {
 
@@ -1286,6 +1287,41 @@ int pnx_curvefit_grid_posterior_f64(const pnx_curvefit_opts *o, int64_t n_vox, c
     return ring_call(A, (size_t)n_vox, 3 << 18, device, st, [&](size_t n, const DevSet &S, hipStream_t s) {
         return grid_posterior_device(D, P, (int64_t)n, S.d(GP_Y), S.d(GP_MEAN), S.d(GP_SD), (int32_t *)S.dev[GP_ATOM], S.d(GP_MAPP), S.d(GP_LOGEV),
                                      S.d(GP_ESS), dev->cus, s);
+    });
+}
+
+// ---- variable-projection dictionary fit (kernels: pnx_varpro.hip, argument checks: pnx_varpro_args.hpp) ---------------------
+int pnx_curvefit_varpro_f64(const pnx_curvefit_opts *o, int64_t n_vox, const double *b, const double *y, int n_atoms,
+                            const double *nl_atoms, const double *fixed, const double *lo, const double *hi, const double *fallback,
+                            double *p_out, int32_t *best, double *cost, int8_t *clipped, int mem, int device, void *stream) {
+    if (!o) return set_error(PNX_ERR_INVALID, "opts is NULL");
+    pnx_curvefit_opts c = *o;  // as grid start: jac_mode and the tolerances are not looked at
+    c.jac_mode = PNX_JAC_ANALYTIC;
+    c.ftol = c.xtol = c.gtol = 0.0;
+    int rc = check_curvefit_opts(&c);
+    if (rc) return rc;
+    VarproLayout L;
+    if ((rc = varpro_check_args(&c, n_vox, b, y, n_atoms, nl_atoms, fixed, lo, hi, fallback, p_out, mem, &L))) return rc;
+    if (n_vox == 0) return PNX_OK;
+    DeviceInfo *dev;
+    if ((rc = use_device(device, &dev))) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    AsyncBuf dict_buf;  // the dictionary: built once per call, stream-ordered, freed behind the work that reads it
+    VarproDict D;
+    if ((rc = dict_buf.alloc(varpro_dict_bytes(c.n_free, L.n_nl, L.k, n_atoms, c.n_b), st))) return rc;
+    if ((rc = varpro_dict_build(&c, L, b, n_atoms, nl_atoms, fixed, fallback, dict_buf.p, &D, st))) return rc;
+    if (mem == PNX_MEM_DEVICE) return varpro_match_device(D, n_vox, y, p_out, best, cost, clipped, dev->cus, st);
+    PNX_HIP(hipStreamSynchronize(st));  // the ring's streams read the dictionary: complete before the first chunk starts
+    enum { VP_Y, VP_P, VP_BEST, VP_COST, VP_CLIP };
+    ArrayTable A;
+    A.add(y, sizeof(double), c.n_b, false);
+    A.add(p_out, sizeof(double), c.n_free, true).pmajor = true;
+    A.add(best, sizeof(int32_t), 1, true);
+    A.add(cost, sizeof(double), 1, true);
+    A.add(clipped, sizeof(int8_t), 1, true);
+    return ring_call(A, (size_t)n_vox, 3 << 18, device, st, [&](size_t n, const DevSet &S, hipStream_t s) {
+        return varpro_match_device(D, (int64_t)n, S.d(VP_Y), S.d(VP_P), (int32_t *)S.dev[VP_BEST], S.d(VP_COST), (int8_t *)S.dev[VP_CLIP],
+                                   dev->cus, s);
     });
 }
 

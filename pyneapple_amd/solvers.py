@@ -11,10 +11,11 @@ its constraint sum(f_i) <= 1, not in its algorithm (pnx_curvefit_simplex_f64).
 `HipLogLinearSolver` has no counterpart in the reference: the linearised mono-exponential fit as a closed form
 (pnx_loglinear_f64), with the reference's solver contract.  `HipPeelSolver` likewise: exponential peeling of the bi- and
 tri-exponential models (pnx_peel_f64).  `HipBayesGridSolver` likewise: posterior mean and sd over a parameter grid
-(pnx_curvefit_grid_posterior_f64).
+(pnx_curvefit_grid_posterior_f64).  `HipVarProSolver` likewise: rates on a grid, fractions and S0 in closed form
+(pnx_curvefit_varpro_f64).
 
 Registered under the `pyneapple.solvers` entry-point group (pyproject.toml) as `hip_curvefit` / `hip_nnls` /
-`hip_constrained_curvefit` / `hip_loglinear` / `hip_peel` / `hip_bayes_grid`;
+`hip_constrained_curvefit` / `hip_loglinear` / `hip_peel` / `hip_bayes_grid` / `hip_varpro`;
 extra scalar keys of `[Fitting.solver]` arrive as keyword arguments (io/toml.py:328-338): `device`,
 `n_gpus`, `jacobian`.
 """
@@ -143,6 +144,57 @@ def _grid_atoms(what, model, kernel_model, p0, bounds, grid, project, project_na
     return {n: list(map(float, np.atleast_1d(v))) for n, v in grid.items()}, bool(project), atoms
 
 
+def _varpro_atoms(what, model, kernel_model, p0, bounds, rates, ordered):
+    """The atoms of a variable-projection dictionary from a dict of rate lists (`rates` of HipVarProSolver, `p0_varpro["rates"]` of
+    HipCurveFitSolver; `what` names the argument in the messages): the Cartesian product of the sequences over the model's free
+    NON-LINEAR parameters (the rates, a free T1) in `model.param_names` order, the last one fastest; one the dict does not name
+    takes its scalar `p0`.  ordered: keep only the atoms with D1 > D2 > D3 (fixed rates included).  Returns (rates as lists,
+    the non-linear names, nl_atoms (n_nonlinear_free, n_atoms))."""
+    import itertools
+
+    linear = api.varpro_linear_names(kernel_model)
+    names = [n for n in model.param_names if n not in linear]
+    if not isinstance(rates, dict):
+        raise ValueError(f"{what} must be a dict from the name of a non-linear parameter (a rate, T1) to a sequence of candidate values")
+    unknown = [n for n in rates if n not in names]
+    if unknown:
+        raise ValueError(f"{what} names {unknown}: not free non-linear parameters of the model (those are {names}; fractions and S0 are "
+                         "solved in closed form)")
+    fixed_lin = [n for n in linear if n not in model.param_names]
+    if fixed_lin:
+        raise ValueError(f"{what}: the variable projection is not built with a fixed fraction or a fixed S0 ({fixed_lin}): the linear "
+                         "structure changes; fix rates or T1 only")
+    axes = []
+    for n in names:
+        if n not in rates and n not in (p0 or {}):
+            raise ValueError(f"neither {what} nor p0 holds a value for {n!r}")
+        vals = np.atleast_1d(np.asarray(rates[n], float)) if n in rates else np.array([float(p0[n])])
+        lo, hi = bounds[n]
+        if vals.ndim != 1 or vals.size < 1:
+            raise ValueError(f"{what}[{n!r}] must be a non-empty 1-D sequence of values")
+        if not ((vals >= lo) & (vals <= hi)).all():
+            raise ValueError(f"{what}[{n!r}] holds a value outside the bounds ({lo}, {hi}) of {n}")
+        axes.append(vals)
+    full = int(np.prod([a.size for a in axes], dtype=np.int64))
+    if full > 1 << 24:
+        raise ValueError(f"{what} spans {full} combinations: too many to enumerate")
+    atoms = np.array(list(itertools.product(*axes)), float).reshape(full, len(names)).T  # (n_nl, n_atoms)
+    if ordered:
+        fixed = getattr(model, "fixed_params", None) or {}
+        d_names = sorted(n for n in model._all_param_names if n.startswith("D") and n[1:].isdigit())
+        cols = [atoms[names.index(n)] if n in names else np.full(full, float(fixed[n])) for n in d_names]
+        keep = np.ones(full, bool)
+        for a, b in zip(cols[:-1], cols[1:]):
+            keep &= a > b
+        atoms = atoms[:, keep]
+    n_atoms = atoms.shape[1]
+    if n_atoms < 1:
+        raise ValueError(f"{what} leaves no atom" + (" with D1 > D2 > D3 (ordered=True)" if ordered else ""))
+    if n_atoms > api.GRID_MAX_ATOMS:
+        raise ValueError(f"{what} spans {n_atoms} atoms, more than the {api.GRID_MAX_ATOMS} the dictionary search takes")
+    return {n: list(map(float, np.atleast_1d(v))) for n, v in rates.items()}, names, np.ascontiguousarray(atoms)
+
+
 class HipCurveFitSolver(CurveFitBase):
     """Batched bounded NLLS on MI355X with SciPy `curve_fit(method="trf")` semantics.
 
@@ -173,6 +225,12 @@ class HipCurveFitSolver(CurveFitBase):
             `bounds`; a voxel the peel could not fit starts from `p0`.  `diagnostics_` gains "p0_status" (the peel's int8 status).
             Not built with it, hence a ValueError: together with p0_grid, an explicit per-voxel p0, fixed parameters (model or per
             pixel), a T1 / STEAM model, per-voxel bounds, precision / io_dtype "float32", HipConstrainedCurveFitSolver.
+        p0_varpro: None (default) or {"rates": {name: [...]}, "ordered": True}: every voxel of `fit()` starts from its
+            variable-projection estimate (pnx_curvefit_varpro_f64; the meaning of HipVarProSolver's `rates` and `ordered`): only
+            the rates (and a free T1) are on the grid, fractions and S0 come in closed form, clipped into `bounds`; a voxel with a
+            non-finite signal starts from `p0`.  `diagnostics_` gains "p0_atom", "p0_cost" and "p0_clipped".  Opt-in.  Not built
+            with it, hence a ValueError: together with p0_grid or p0_peel, an explicit per-voxel p0, per-pixel fixed parameters, a
+            fixed fraction or S0, per-voxel bounds, precision / io_dtype "float32", HipConstrainedCurveFitSolver.
         p0_grid_project: fit the amplitude S0 per voxel and atom, clipped to its bounds, instead of taking it from the atoms
             (so S0 needs no entry in p0_grid).  Default: True exactly when the model has a free S0.
     """
@@ -200,6 +258,7 @@ class HipCurveFitSolver(CurveFitBase):
         p0_grid = solver_kwargs.pop("p0_grid", None)
         p0_grid_project = solver_kwargs.pop("p0_grid_project", None)
         p0_peel = solver_kwargs.pop("p0_peel", None)
+        p0_varpro = solver_kwargs.pop("p0_varpro", None)
         self.xtol = float(solver_kwargs.pop("xtol", 1e-8))
         self.gtol = float(solver_kwargs.pop("gtol", 1e-8))
         # sigma / absolute_sigma: the two curve_fit arguments the reference's docstring names (curvefit.py:33).  A scalar or 1-D
@@ -225,7 +284,7 @@ class HipCurveFitSolver(CurveFitBase):
         if unknown:
             raise ValueError(f"HipCurveFitSolver got solver arguments it cannot honour: {sorted(unknown)} "
                              "(supported: sigma, absolute_sigma, xtol, gtol, jacobian, device, n_gpus, io_dtype, precision, p0_grid, "
-                             "p0_grid_project, p0_peel, n_pools)")
+                             "p0_grid_project, p0_peel, p0_varpro, n_pools)")
         if method != "trf":
             raise ValueError(f"HipCurveFitSolver implements method='trf' only (got {method!r}); "
                              "use the reference CurveFitSolver for 'dogbox' / 'lm'.")
@@ -261,6 +320,7 @@ class HipCurveFitSolver(CurveFitBase):
                 raise ValueError("precision='float32' is not built with fixed parameters; use precision='float64'")
         self._set_p0_grid(p0_grid, p0_grid_project)
         self._set_p0_peel(p0_peel)
+        self._set_p0_varpro(p0_varpro)
 
     # ------------------------------------------------------------------ p0_grid: the atoms of the dictionary search
     def _set_p0_grid(self, p0_grid, project):
@@ -298,6 +358,24 @@ class HipCurveFitSolver(CurveFitBase):
             raise ValueError(f"p0_peel: {e}") from None
         self.p0_peel = {"b_thresholds": None if thresholds is None else [float(t) for t in np.atleast_1d(thresholds)],
                         "weighting": weighting}
+
+    # ------------------------------------------------------------------ p0_varpro: start values from the variable projection
+    def _set_p0_varpro(self, p0_varpro):
+        """Validates `p0_varpro` ({"rates": {...}, "ordered": True}) and builds the atoms; nothing is set up without it."""
+        self.p0_varpro, self._varpro_nl_atoms = None, None
+        if p0_varpro is None:
+            return
+        if self._p0_atoms is not None or self.p0_peel is not None:
+            raise ValueError("p0_varpro, p0_grid and p0_peel each choose the per-voxel start values; give one of them")
+        if not isinstance(p0_varpro, dict) or "rates" not in p0_varpro or set(p0_varpro) - {"rates", "ordered"}:
+            raise ValueError("p0_varpro must be a dict with the keys 'rates' and (optionally) 'ordered'")
+        if self.precision == "float32" or self.io_dtype is not np.float64:
+            raise ValueError("p0_varpro is built for precision='float64' and io_dtype='float64': the variable projection reads and "
+                             "writes float64 arrays")
+        ordered = bool(p0_varpro.get("ordered", True))
+        rates, _, self._varpro_nl_atoms = _varpro_atoms("p0_varpro['rates']", self.model, self._kernel_model, self.p0, self.bounds,
+                                                        p0_varpro["rates"], ordered)
+        self.p0_varpro = {"rates": rates, "ordered": ordered}
 
     # ------------------------------------------------------------------ p0 / bounds (curvefit.py:319-392)
     def _prepare_p0_bounds(self, p0, bounds, n_pixels):
@@ -443,8 +521,16 @@ class HipCurveFitSolver(CurveFitBase):
                                  "amplitude and diffusivity")
             if per_voxel:
                 raise ValueError("p0_peel works with shared bounds: the peel estimate is clipped into one box for the whole call")
+        varpro = self.p0_varpro is not None
+        if varpro:  # as p0_peel: a shared p0 (the solver's, or fit()'s) serves the voxels with a non-finite signal
+            if isinstance(p0, np.ndarray) and p0.ndim == 2:
+                raise ValueError("p0_varpro chooses the per-voxel start values itself: an explicit per-voxel p0 cannot be honoured")
+            if pixel_fixed_params:
+                raise ValueError("p0_varpro is not built with per-pixel fixed parameters (the dictionary would differ from voxel to voxel)")
+            if per_voxel:
+                raise ValueError("p0_varpro works with shared bounds: one dictionary serves the whole call")
         res = self._run(xdata, np.ascontiguousarray(ydata, self.io_dtype), p0_a, lo_a, hi_a, per_voxel, fixed_idx,
-                        fixed_vals, jac, grid, peel)
+                        fixed_vals, jac, grid, peel, varpro)
         self._pack(res, n_pixels, free_names)
         return self
 
@@ -459,7 +545,7 @@ class HipCurveFitSolver(CurveFitBase):
         self.params_ = {name: [float(popt[i, 0])] if n_pixels == 1 else popt[i] for i, name in enumerate(free_names)}
         self.diagnostics_ = {"pcov": (pcov[0] if n_pixels == 1 else pcov) if pcov is not None else None, "n_pixels": n_pixels,
                              "status": status, "nfev": res["nfev"], "cost": res["cost"]}
-        for key in ("p0_atom", "p0_cost", "p0_status"):  # a fit that started from the dictionary search (p0_grid) / the peel (p0_peel)
+        for key in ("p0_atom", "p0_cost", "p0_status", "p0_clipped"):  # a fit that started from p0_grid / p0_peel / p0_varpro
             if key in res:
                 self.diagnostics_[key] = res[key]
 
@@ -492,7 +578,19 @@ class HipCurveFitSolver(CurveFitBase):
                               out=out or None, **kw)
         return dict(res, p0_status=pe["status"])
 
-    def _run(self, xdata, ydata, p0, lo, hi, per_voxel, fixed_idx, fixed_vals, jac, grid=False, peel=False):
+    def _varpro_fit(self, xdata, ydata, p0, lo, hi, fixed_vals, device, kw, out=None):
+        """One shard with p0_varpro: the variable-projection estimate (a non-finite voxel: the shared p0), then the fit from these
+        per-voxel start values under the shared bounds.  A start on a bound is moved inside by the fit itself, as p0_peel's."""
+        out = out or {}
+        vp = api.varpro(self._kernel_model, xdata, ydata, self._varpro_nl_atoms, lo, hi, p0, fixed_idx=kw["fixed_idx"], fixed_vals=fixed_vals,
+                        sigma=self.sigma, device=device, **self._kernel_t1,
+                        out={"atom": out.get("p0_atom"), "cost": out.get("p0_cost"), "clipped": out.get("p0_clipped")})
+        tile = lambda a: np.ascontiguousarray(np.repeat(a[:, None], ydata.shape[0], axis=1))
+        res = self._batch_fit(self._kernel_model, xdata, ydata, vp["params"], tile(lo), tile(hi), fixed_vals=fixed_vals, device=device,
+                              out=out or None, **kw)
+        return dict(res, p0_atom=vp["atom"], p0_cost=vp["cost"], p0_clipped=vp["clipped"])
+
+    def _run(self, xdata, ydata, p0, lo, hi, per_voxel, fixed_idx, fixed_vals, jac, grid=False, peel=False, varpro=False):
         n_vox = ydata.shape[0]
         kw = dict(max_nfev=int(self.max_iter), ftol=float(self.tol), xtol=self.xtol, gtol=self.gtol, jac=jac,
                   fixed_idx=fixed_idx, sigma=self.sigma, absolute_sigma=self.absolute_sigma, **self._kernel_t1)
@@ -504,6 +602,8 @@ class HipCurveFitSolver(CurveFitBase):
                 return self._grid_fit(xdata, ydata, lo, hi, fixed_vals, self.device, kw)
             if peel:
                 return self._peel_fit(xdata, ydata, p0, lo, hi, self.device, kw)
+            if varpro:
+                return self._varpro_fit(xdata, ydata, p0, lo, hi, fixed_vals, self.device, kw)
             return self._batch_fit(self._kernel_model, xdata, ydata, p0, lo, hi, fixed_vals=fixed_vals,
                                    device=self.device, **kw)
         parts = _split(n_vox, n_dev)
@@ -517,6 +617,8 @@ class HipCurveFitSolver(CurveFitBase):
             full.update(p0_atom=np.empty(n_vox, np.int32), p0_cost=np.empty(n_vox, np.float64))
         if peel:
             full.update(p0_status=np.empty(n_vox, np.int8))
+        if varpro:
+            full.update(p0_atom=np.empty(n_vox, np.int32), p0_cost=np.empty(n_vox, np.float64), p0_clipped=np.empty(n_vox, np.int8))
 
         def work(k):
             a, b = parts[k]
@@ -532,6 +634,8 @@ class HipCurveFitSolver(CurveFitBase):
                     return self._grid_fit(xdata, ydata[sl], lo, hi, fv, dev_k, kw, out={key: v[sl] for key, v in full.items()})["popt"]
                 if peel:
                     return self._peel_fit(xdata, ydata[sl], p0, lo, hi, dev_k, kw, out={key: v[sl] for key, v in full.items()})["popt"]
+                if varpro:
+                    return self._varpro_fit(xdata, ydata[sl], p0, lo, hi, fv, dev_k, kw, out={key: v[sl] for key, v in full.items()})["popt"]
                 return self._batch_fit(self._kernel_model, xdata, ydata[sl], *pv, fixed_vals=fv,
                                        device=dev_k, out={key: v[sl] for key, v in full.items()}, **kw)["popt"]
 
@@ -562,6 +666,9 @@ class HipConstrainedCurveFitSolver(HipCurveFitSolver):
         if solver_kwargs.get("p0_peel") is not None:
             raise ValueError("p0_peel is not built for HipConstrainedCurveFitSolver: the peel estimate knows nothing of the constraint "
                              "f1 + f2 <= 1 and the constrained fit takes one shared start; use HipCurveFitSolver")
+        if solver_kwargs.get("p0_varpro") is not None:
+            raise ValueError("p0_varpro is not built for HipConstrainedCurveFitSolver: the projected amplitudes know nothing of the "
+                             "constraint f1 + f2 <= 1 and the constrained fit takes one shared start; use HipCurveFitSolver")
         if fraction_constraint and not getattr(model, "fit_reduced", False):  # constrained_curvefit.py:72-79
             raise ValueError("fraction_constraint=True requires fit_reduced=True. In reduced mode the signal is normalised to S0=1 "
                              "before fitting, so the hard constraint sum(f_i) <= 1 is physically meaningful. Use fit_reduced=True "
@@ -869,6 +976,100 @@ class HipBayesGridSolver(RefBaseSolver):
         self.diagnostics_ = {"posterior_sd": {n: res["sd"][i] for i, n in enumerate(names)},
                              "map": {n: res["map_p"][i] for i, n in enumerate(names)}, "map_atom": atom,
                              "log_evidence": res["log_evidence"], "ess": res["ess"], "n_pixels": n_pixels}
+        return self
+
+
+_VARPRO_MESSAGES = {-2: "array must not contain infs or NaNs"}
+
+
+class HipVarProSolver(RefBaseSolver):
+    """Variable-projection dictionary fit per voxel (VARPRO, separable least squares; pnx_curvefit_varpro_f64, include/pnx.h): only
+    the rates (and a free T1) are on a grid, the fractions and S0 of every voxel and atom come in closed form and are clipped into
+    `bounds`.  A coarse estimator over decades of rates without a per-voxel prior, and a start for the non-linear fit
+    (HipCurveFitSolver's `p0_varpro`).  Registered as `hip_varpro`; no counterpart in the reference, whose solver contract it keeps.
+
+    model: any of the seven layouts; shared fixed rates / T1 and the T1 / STEAM factor as the curve fit takes them; a fixed fraction
+    or a fixed S0 is refused.  `max_iter`, `tol` are accepted because the TOML loader always passes them.  Arguments:
+        rates: dict from the name of a non-linear parameter (D1, D2, D3, D, T1) to a sequence of values (TOML: arrays under
+            [Fitting.solver.rates]).  The atoms are the Cartesian product in `model.param_names` order, the last one fastest; a
+            non-linear parameter the dict does not name takes its scalar `p0`; every value inside `bounds`; at most 4096 atoms.
+        ordered: True (default) keeps only the atoms with D1 > D2 > D3.
+        bounds: {name: (lo, hi)} for every parameter, required: the box the amplitudes are clipped into; lo of S0 >= 0.
+        p0: {name: value}: the non-linear parameters `rates` does not name, and the default `fallback`.
+        fallback: {name: value} for every parameter, inside `bounds`: what a voxel with a non-finite signal reports.  Default: p0.
+        sigma: None, a scalar or (n_b,), as HipCurveFitSolver's.  device: HIP device index.
+    Not built, hence a ValueError: per-pixel fixed parameters, io_dtype or precision "float32".
+    Any other keyword (the reference's solver arguments: method, multi_threading, ...) is accepted and ignored.
+    After fit: params_ keyed by the model's names; diagnostics_ {"atom", "cost", "clipped", "n_pixels"}; pixel_results_ with
+    success = the voxel's signal was finite."""
+
+    def __init__(self, model: Any, rates=None, max_iter: int = 250, tol: float = 1e-8, p0: dict[str, float] | None = None,
+                 bounds: dict[str, tuple[float, float]] | None = None, ordered: bool = True, fallback: dict[str, float] | None = None,
+                 sigma=None, device: int = 0, io_dtype: str = "float64", precision: str = "float64", **ignored_reference_kwargs):
+        RefBaseSolver.__init__(self, model=model, max_iter=max_iter, tol=tol, verbose=bool(ignored_reference_kwargs.pop("verbose", False)))
+        self._kernel_model = kernel_model_key(model)
+        self._kernel_t1 = kernel_t1(model)
+        if _io_dtype(io_dtype) is not np.float64 or precision != "float64":
+            raise ValueError("HipVarProSolver is built for precision='float64' and io_dtype='float64': the variable projection reads and "
+                             "writes float64 arrays")
+        if rates is None:
+            raise ValueError("rates is required: a dict from the name of a non-linear parameter to a sequence of values")
+        names = list(model.param_names)
+        if bounds is None:
+            raise ValueError(f"bounds is required: {{name: (lo, hi)}} for every parameter of {names}")
+        _validate_parameter_names(bounds, names)
+        self.ordered = bool(ordered)
+        self.rates, self._nl_names, self._nl_atoms = _varpro_atoms("rates", model, self._kernel_model, p0, bounds, rates, self.ordered)
+        fallback = fallback if fallback is not None else p0
+        if fallback is None or [n for n in names if n not in fallback]:
+            raise ValueError(f"fallback (default: p0) must hold a value for every parameter of {names}: it is what a voxel with a "
+                             "non-finite signal reports")
+        for n in names:
+            if not bounds[n][0] <= float(fallback[n]) <= bounds[n][1]:
+                raise ValueError(f"fallback[{n!r}] = {fallback[n]} lies outside the bounds {tuple(bounds[n])} of {n}")
+        if "S0" in names and not bounds["S0"][0] >= 0:
+            raise ValueError(f"the lower bound of S0 must be >= 0 (the fraction bounds scale with S0), got {bounds['S0'][0]}")
+        self.sigma = None
+        if sigma is not None:
+            self.sigma = np.asarray(sigma, float)
+            if self.sigma.ndim > 1 and self.sigma.size != 1:
+                raise ValueError("HipVarProSolver implements a scalar or 1-D sigma (one standard deviation per b-value)")
+            self.sigma = self.sigma.reshape(-1)
+        self.p0 = p0
+        self.fallback = {n: float(fallback[n]) for n in names}
+        self.bounds = bounds
+        self.device = int(device)
+        self.io_dtype = np.float64
+        self.solver_kwargs = ignored_reference_kwargs
+
+    def fit(self, xdata: np.ndarray, ydata: np.ndarray, pixel_fixed_params=None, **fit_kwargs) -> "HipVarProSolver":
+        if pixel_fixed_params:
+            raise ValueError("HipVarProSolver is not built with per-pixel fixed parameters (pixel_fixed_params): the dictionary "
+                             "would differ from voxel to voxel")
+        self._reset_state()
+        xdata = np.asarray(xdata)
+        ydata = np.asarray(ydata)
+        _validate_data_shapes(xdata, ydata)
+        if ydata.ndim == 1:
+            ydata = ydata[np.newaxis, :]
+        if ydata.ndim > 2:
+            raise ValueError(f"ydata must be 1D or 2D array, but got shape {ydata.shape}.")
+        n_pixels = ydata.shape[0]
+        names = list(self.model.param_names)
+        all_names = list(self.model._all_param_names)
+        fixed = getattr(self.model, "fixed_params", None) or {}
+        fixed_idx = [i for i, n in enumerate(all_names) if n in fixed]
+        fixed_vals = np.array([float(fixed[all_names[i]]) for i in fixed_idx]) if fixed_idx else None
+        lo = np.array([self.bounds[n][0] for n in names], float)
+        hi = np.array([self.bounds[n][1] for n in names], float)
+        fb = np.array([self.fallback[n] for n in names], float)
+        res = api.varpro(self._kernel_model, xdata, ydata, self._nl_atoms, lo, hi, fb, fixed_idx=fixed_idx, fixed_vals=fixed_vals,
+                         sigma=self.sigma, device=self.device, **self._kernel_t1)
+        params, atom = res["params"], res["atom"]
+        self.pixel_results_ = PixelResultsView(params.T, None, atom >= 0,
+                                               lambda i, a=atom: None if a[i] >= 0 else _VARPRO_MESSAGES[-2])
+        self.params_ = {name: [float(params[i, 0])] if n_pixels == 1 else params[i] for i, name in enumerate(names)}
+        self.diagnostics_ = {"atom": atom, "cost": res["cost"], "clipped": res["clipped"], "n_pixels": n_pixels}
         return self
 
 
