@@ -479,6 +479,53 @@ PNX_API int pnx_curvefit_varpro_f64(const pnx_curvefit_opts *opts, int64_t n_vox
                             const double *nl_atoms, const double *fixed, const double *lo, const double *hi, const double *fallback,
                             double *p_out, int32_t *best, double *cost, int8_t *clipped, int mem, int device, void *stream);
 /*
+ * Posterior over the variable-projection dictionary: the Bayesian treatment of sums of exponentials in which the
+ * linear amplitudes are eliminated per atom (Bretthorst) and the posterior lives on the grid of the NON-LINEAR parameters only.
+ * The dictionary nl_atoms, the unit columns, the 1 / sigma weighting, the per-atom constants, the amplitude solve and the clip rule
+ * per class, the true cost c_g(v) = 0.5 ||y_w||^2 - c . a' + 0.5 a'^T M a' and every refusal are pnx_curvefit_varpro_f64's; there
+ * is no fallback argument.
+ *   log_prior (n_atoms,) host or NULL (uniform): every entry finite or -inf, at least one finite (PNX_ERR_INVALID otherwise);
+ *     an atom at -inf is excluded.
+ *   noise_sd > 0: known Gaussian noise sd in the units of the (sigma-weighted) signal; == 0: the noise scale is marginalised under
+ *     a Jeffreys prior; negative or non-finite: PNX_ERR_INVALID.
+ *   marginal_amplitudes 0 / 1 (anything else PNX_ERR_INVALID), see below.
+ * With n_lin the number of amplitudes solved per atom (K for the free and S0 classes, K - 1 for the sum-to-one layouts), N_g the
+ * matrix that solve inverts (M, or the difference system) and nu = n_b - n_lin, per voxel v and atom g, in fp64:
+ *   lw_g = log_prior_g + (marginal_amplitudes ? -0.5 log det N_g : 0), built once per call on the device; an atom whose N is not
+ *          positive definite in fp64 (the variable projection's a_hat = 0 atoms) gets lw = -inf when marginal_amplitudes is set;
+ *   l_g  = lw_g - c_g / noise_sd^2                              (known noise)
+ *   l_g  = lw_g - (nu / 2) log(max(c_g, tol_v))                 (marginalised)
+ *   tol_v = 4 n_b 2^-52 (||y_w||^2 + A^2 max_{g,j} ||phi_j||^2), the rounding bound of the expanded cost, with A the largest
+ *          ||a'||_1 the class's clip rule can return for the call's box, computed on the host:
+ *            free (mono, bi / tri full)  A = sum_j max(|lo_j|, |hi_j|) over the amplitudes (mono: S0);
+ *            reduced                     A = F = sum_{j<K} max(|lo_fj|, |hi_fj|) + max(|1 - sum_{j<K} lo_fj|, |1 - sum_{j<K} hi_fj|);
+ *            S0                          A = hi_S0 F   (lo_S0 >= 0 is required, so |S| <= hi_S0);
+ *   L = log sum_g exp(l_g);  W_g = exp(l_g - L);  padded and excluded atoms have weight 0.
+ *   mean[k] = sum_g W_g theta_kg;  theta_kg = nl_atoms[row, g] in a non-linear row; in a fraction / S0 row the reported linear
+ *     parameter of the pair (v, g): the clipped a' mapped as the variable projection maps it (f_j = a'_j / S kept inside the box);
+ *   sd[k] = sqrt(max(0, sum_g W_g (theta_kg - mean[k])^2)), accumulated by a weighted Welford / Chan merge (no E[x^2] - mean^2);
+ *   map_atom = argmax_g l_g, the lowest index among equal l;  map_p = that atom's rates / T1 copied bit for bit and its reported
+ *     linear parameters;  log_evidence = L - log sum_g exp(log_prior_g);  ess = (sum W)^2 / sum W^2 in [1, n_atoms];
+ *   clipped_mass = sum_g W_g [a clip was active at (v, g)]: the posterior share that rests on clipped amplitudes.
+ * marginal_amplitudes = 1: the weight is the exact marginal over unconstrained amplitudes under a flat prior -- Gaussian for known
+ *   noise, Student-t with nu degrees of freedom for marginalised noise -- wherever no clip is active.  Where a clip is active it is
+ *   a Laplace-style approximation at the clipped point: the cost of the clipped a' with the curvature term of the free solve.
+ *   marginal_amplitudes = 0 is the profile weight (the amplitudes at their clipped optimum, no Occam term).
+ * Known understatement: the sd of a linear row (a fraction, S0) is the between-atom spread of the clipped optimum only; the
+ *   conditional variance of the amplitudes given the rates is left out.
+ * A voxel with a non-finite (weighted) signal, and a voxel for which no atom has a finite l, gets NaN in every floating output
+ * and map_atom = -1; its neighbours are bit-identical to a run without it.
+ *   opts, b, y, nl_atoms, fixed, lo, hi: as pnx_curvefit_varpro_f64 takes them;
+ *   mean, sd, map_p (n_free, n_vox); map_atom (n_vox) int32; log_evidence, ess, clipped_mass (n_vox): out, host|device as `mem`;
+ *   all but mean may be NULL.  PNX_MEM_DEVICE only enqueues; PNX_MEM_HOST goes through the chunk ring.  The (n_vox, n_atoms)
+ *   matrix never reaches memory.
+ */
+PNX_API int pnx_curvefit_varpro_posterior_f64(const pnx_curvefit_opts *opts, int64_t n_vox, const double *b, const double *y, int n_atoms,
+                                      const double *nl_atoms, const double *fixed, const double *lo, const double *hi,
+                                      const double *log_prior, double noise_sd, int marginal_amplitudes, double *mean, double *sd,
+                                      int32_t *map_atom, double *map_p, double *log_evidence, double *ess, double *clipped_mass,
+                                      int mem, int device, void *stream);
+/*
  * Log-linear mono-exponential fit, ln S = ln S0 - b D by (weighted) linear least squares per voxel: the ADC
  * map, step 1 of a segmented IVIM fit, a cheap source of S0 / D start values.  A closed form over one pass of the data: a voxel
  * costs its signal row in and its results out.  Per voxel, in fp64, in the order written:

@@ -28,7 +28,7 @@ ABI_SYMBOLS = [
     "pnx_label_sums_f64", "pnx_release_staging", "pnx_queue_order_f64",
     "pnx_nnls_fit_stats_f64", "pnx_nnls_solve_peaks_stats_f64", "pnx_curvefit_predict_f64", "pnx_curvefit_fast_f32",
     "pnx_curvefit_simplex_f64", "pnx_ideal_bounds_simplex_f64", "pnx_curvefit_grid_start_f64",
-    "pnx_curvefit_grid_posterior_f64", "pnx_curvefit_varpro_f64",
+    "pnx_curvefit_grid_posterior_f64", "pnx_curvefit_varpro_f64", "pnx_curvefit_varpro_posterior_f64",
     "pnx_loglinear_f64", "pnx_loglinear_f32", "pnx_peel_f64", "pnx_peel_f32",
 ]
 
@@ -125,6 +125,10 @@ def load():
     lib.pnx_curvefit_varpro_f64.restype = C.c_int  # opts, n_vox, b, y, n_atoms, nl_atoms, fixed, lo, hi, fallback, p_out, best, cost, clipped
     lib.pnx_curvefit_varpro_f64.argtypes = [C.POINTER(CurvefitOpts), C.c_int64, dp, dp, C.c_int, dp, dp, dp, dp, dp, dp, vp, dp, vp,
                                             C.c_int, C.c_int, vp]
+    # the variable projection's inputs (no fallback), log_prior, noise_sd, marginal_amplitudes, mean, sd, map_atom, map_p, log_evidence, ess, clipped_mass
+    lib.pnx_curvefit_varpro_posterior_f64.restype = C.c_int
+    lib.pnx_curvefit_varpro_posterior_f64.argtypes = [C.POINTER(CurvefitOpts), C.c_int64, dp, dp, C.c_int, dp, dp, dp, dp, dp, C.c_double, C.c_int,
+                                                      dp, dp, vp, dp, dp, dp, dp, C.c_int, C.c_int, vp]
     lib.pnx_loglinear_f64.restype = C.c_int  # n_vox, n_b, b, use, weighting, n_reweight, clip, lo, hi, y, params, pcov, status, n_used, ss_res
     lib.pnx_loglinear_f64.argtypes = [C.c_int64, C.c_int, dp, vp, C.c_int, C.c_int, C.c_int, dp, dp, dp, dp, dp, vp, vp, dp,
                                       C.c_int, C.c_int, vp]

@@ -432,6 +432,68 @@ def varpro_device(opts, n_vox, b, y, nl_atoms, fixed, lo, hi, fallback, params, 
                                          stream))
 
 
+def varpro_posterior_slab_atoms(n_b, k):
+    """Atoms per LDS slab of the variable-projection posterior kernel (varpro_posterior_slab of csrc/pnx_varpro_posterior_args.hpp):
+    the variable projection's rule with k + 2 more values per atom (the log-weight and the k + 1 centred non-linear values)."""
+    kpad, k, width = (int(n_b) + 3) & ~3, int(k), 16
+    for w in range(16, 257, 16):
+        if k * kpad * (w if w & 16 else w + 16) + (k * (k + 1) + k + 2) * w <= 8192:
+            width = w
+    return width
+
+
+def varpro_posterior(model, b, y, nl_atoms, lo, hi, *, log_prior=None, noise_sd=0.0, marginal_amplitudes=True, fixed_idx=(), fixed_vals=None,
+                     sigma=None, t1_mode=0, tr=0., tm=0., device=0, out=None):
+    """Posterior of every voxel over a variable-projection dictionary on host (numpy) arrays (pnx_curvefit_varpro_posterior_f64;
+    method: include/pnx.h): only the rates (and a free T1) are on the grid, the fractions and S0 of every voxel and atom are
+    eliminated in closed form.  nl_atoms, lo, hi, fixed_idx / fixed_vals, sigma and the T1 factor as `varpro` takes them, and
+    log_prior: None (uniform) or (n_atoms,) log prior weights, finite or -inf (an atom at -inf is excluded);
+    noise_sd: > 0 a known Gaussian noise sd in the units of the (sigma-weighted) signal, 0 (default) marginalises the noise scale;
+    marginal_amplitudes: True (default) weighs an atom by the marginal over its amplitudes (the Occam term -0.5 log det N; a
+    Laplace-style approximation where a clip is active), False by the profile over them.
+    Returns dict(mean, sd, map_p (n_free, n_vox), map_atom (n_vox,) int32 (-1 for a non-finite signal, whose floating outputs are
+    NaN), log_evidence, ess, clipped_mass (n_vox,): the posterior share that rests on clipped amplitudes).  The sd of a fraction /
+    S0 row is the between-atom spread only (a known understatement).  `out`: optional dict of preallocated result arrays.
+    There is no `mem` keyword: as with `varpro` and `grid_posterior`, this function is the host-memory call (PNX_MEM_HOST, the
+    chunk ring) and `varpro_posterior_device` the device-memory one (PNX_MEM_DEVICE, enqueue only)."""
+    _lib.require_device()
+    b = np.ascontiguousarray(b, np.float64)
+    y = np.ascontiguousarray(np.atleast_2d(y), np.float64)
+    n_vox, n_b = y.shape
+    if b.shape != (n_b,):
+        raise ValueError(f"b has shape {b.shape}, expected ({n_b},)")
+    o, nl_atoms, lo, hi, _, fv = _varpro_args(model, n_b, nl_atoms, lo, hi, lo, fixed_idx, fixed_vals, sigma, t1_mode, tr, tm)
+    lp = _posterior_log_prior(log_prior, nl_atoms.shape[1])
+    n = o.n_free
+    res = {key: _out(out, key, (n, n_vox), np.float64) for key in ("mean", "sd", "map_p")}
+    res["map_atom"] = _out(out, "map_atom", (n_vox,), np.int32)
+    for key in ("log_evidence", "ess", "clipped_mass"):
+        res[key] = _out(out, key, (n_vox,), np.float64)
+    check(load().pnx_curvefit_varpro_posterior_f64(C.byref(o), n_vox, ptr(b), ptr(y), int(nl_atoms.shape[1]), ptr(nl_atoms), ptr(fv), ptr(lo),
+                                                   ptr(hi), ptr(lp), float(noise_sd), int(bool(marginal_amplitudes)), ptr(res["mean"]),
+                                                   ptr(res["sd"]), ptr(res["map_atom"]), ptr(res["map_p"]), ptr(res["log_evidence"]),
+                                                   ptr(res["ess"]), ptr(res["clipped_mass"]), MEM_HOST, int(device), None))
+    return res
+
+
+def varpro_posterior_device(opts, n_vox, b, y, nl_atoms, fixed, lo, hi, log_prior, noise_sd, marginal_amplitudes, mean, sd, map_atom, map_p,
+                            log_evidence, ess, clipped_mass, device, stream=None):
+    """Enqueue the variable-projection posterior on HBM-resident float64 torch tensors (asynchronous; caller synchronises):
+    y (n_vox, n_b), mean / sd / map_p (n_free, n_vox), map_atom (n_vox,) int32, log_evidence / ess / clipped_mass (n_vox,) on the
+    device, all but mean may be None; b, nl_atoms (n_nonlinear_free, n_atoms), shared fixed values, lo, hi and log_prior
+    (n_atoms,) or None are host arrays.  `opts` from make_opts."""
+    b, nl_atoms, lo, hi = (np.ascontiguousarray(a, np.float64) for a in (b, nl_atoms, lo, hi))
+    if fixed is not None:
+        fixed = np.ascontiguousarray(fixed, np.float64)
+    if nl_atoms.ndim != 2:
+        raise ValueError("nl_atoms must have shape (n_nonlinear_free, n_atoms)")
+    lp = _posterior_log_prior(log_prior, nl_atoms.shape[1])
+    check(load().pnx_curvefit_varpro_posterior_f64(C.byref(opts), int(n_vox), ptr(b), ptr(y), int(nl_atoms.shape[1]), ptr(nl_atoms), ptr(fixed),
+                                                   ptr(lo), ptr(hi), ptr(lp), float(noise_sd), int(bool(marginal_amplitudes)), ptr(mean), ptr(sd),
+                                                   ptr(map_atom), ptr(map_p), ptr(log_evidence), ptr(ess), ptr(clipped_mass), MEM_DEVICE,
+                                                   int(device), stream))
+
+
 LOGLINEAR_WEIGHTING = {"none": 0, "signal2": 1}  # w = 1 / w = y^2 (include/pnx.h)
 LOGLINEAR_MAX_REWEIGHT = 8  # kLogLinMaxReweight of csrc/pnx_loglin_args.hpp
 

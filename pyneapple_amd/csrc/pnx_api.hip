@@ -29,6 +29,7 @@
 #include "pnx_predict.hpp"
 #include "pnx_simplex.hpp"
 #include "pnx_varpro.hpp"
+#include "pnx_varpro_posterior.hpp"
 
 namespace pnx {
 
@@ -1322,6 +1323,52 @@ int pnx_curvefit_varpro_f64(const pnx_curvefit_opts *o, int64_t n_vox, const dou
     return ring_call(A, (size_t)n_vox, 3 << 18, device, st, [&](size_t n, const DevSet &S, hipStream_t s) {
         return varpro_match_device(D, (int64_t)n, S.d(VP_Y), S.d(VP_P), (int32_t *)S.dev[VP_BEST], S.d(VP_COST), (int8_t *)S.dev[VP_CLIP],
                                    dev->cus, s);
+    });
+}
+
+// ---- posterior over the variable-projection dictionary (kernels: pnx_varpro_posterior.hip, checks: pnx_varpro_posterior_args.hpp)
+int pnx_curvefit_varpro_posterior_f64(const pnx_curvefit_opts *o, int64_t n_vox, const double *b, const double *y, int n_atoms,
+                                      const double *nl_atoms, const double *fixed, const double *lo, const double *hi, const double *log_prior,
+                                      double noise_sd, int marginal_amplitudes, double *mean, double *sd, int32_t *map_atom, double *map_p,
+                                      double *log_evidence, double *ess, double *clipped_mass, int mem, int device, void *stream) {
+    if (!o) return set_error(PNX_ERR_INVALID, "opts is NULL");
+    pnx_curvefit_opts c = *o;  // as grid start: jac_mode and the tolerances are not looked at
+    c.jac_mode = PNX_JAC_ANALYTIC;
+    c.ftol = c.xtol = c.gtol = 0.0;
+    int rc = check_curvefit_opts(&c);
+    if (rc) return rc;
+    VarproLayout L;
+    VarproPosteriorHost H;
+    if ((rc = varpro_posterior_check_args(&c, n_vox, b, y, n_atoms, nl_atoms, fixed, lo, hi, log_prior, noise_sd, marginal_amplitudes, mean, mem,
+                                          &L, &H)))
+        return rc;
+    if (n_vox == 0) return PNX_OK;
+    DeviceInfo *dev;
+    if ((rc = use_device(device, &dev))) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    AsyncBuf dict_buf, post_buf;  // built once per call, stream-ordered, freed behind the work that reads them
+    VarproDict D;
+    VarproPosterior P;
+    if ((rc = dict_buf.alloc(varpro_dict_bytes(c.n_free, L.n_nl, L.k, n_atoms, c.n_b), st))) return rc;
+    if ((rc = post_buf.alloc(varpro_posterior_bytes(L.n_nl, n_atoms), st))) return rc;
+    if ((rc = varpro_dict_build(&c, L, b, n_atoms, nl_atoms, fixed, lo, dict_buf.p, &D, st))) return rc;  // no fallback: lo is not read back
+    if ((rc = varpro_posterior_prepare(D, H, log_prior, noise_sd, marginal_amplitudes, post_buf.p, &P, st))) return rc;
+    if (mem == PNX_MEM_DEVICE)
+        return varpro_posterior_device(D, P, n_vox, y, mean, sd, map_atom, map_p, log_evidence, ess, clipped_mass, dev->cus, st);
+    PNX_HIP(hipStreamSynchronize(st));  // the ring's streams read the dictionary: complete before the first chunk starts
+    enum { VQ_Y, VQ_MEAN, VQ_SD, VQ_ATOM, VQ_MAPP, VQ_LOGEV, VQ_ESS, VQ_CM };
+    ArrayTable A;
+    A.add(y, sizeof(double), c.n_b, false);
+    A.add(mean, sizeof(double), c.n_free, true).pmajor = true;
+    A.add(sd, sizeof(double), c.n_free, true).pmajor = true;
+    A.add(map_atom, sizeof(int32_t), 1, true);
+    A.add(map_p, sizeof(double), c.n_free, true).pmajor = true;
+    A.add(log_evidence, sizeof(double), 1, true);
+    A.add(ess, sizeof(double), 1, true);
+    A.add(clipped_mass, sizeof(double), 1, true);
+    return ring_call(A, (size_t)n_vox, 3 << 18, device, st, [&](size_t n, const DevSet &S, hipStream_t s) {
+        return varpro_posterior_device(D, P, (int64_t)n, S.d(VQ_Y), S.d(VQ_MEAN), S.d(VQ_SD), (int32_t *)S.dev[VQ_ATOM], S.d(VQ_MAPP),
+                                       S.d(VQ_LOGEV), S.d(VQ_ESS), S.d(VQ_CM), dev->cus, s);
     });
 }
 

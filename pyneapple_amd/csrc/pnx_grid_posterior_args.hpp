@@ -18,6 +18,26 @@ struct GridPosteriorHost {
     double centre[PNX_MAX_PARAMS] = {};  // per free parameter: mid-range of the admissible atoms (0 for a projected S0 row)
 };
 
+// The prior of a posterior over a dictionary (`who` in front of a message): NULL is uniform; every entry finite or -inf, at least
+// one finite.  *norm = log sum_g exp(log_prior_g) by a two-pass log-sum-exp, log(n_atoms) for the uniform prior.
+inline int posterior_check_log_prior(const char *who, int n_atoms, const double *log_prior, double *norm) {
+    if (!log_prior) {
+        *norm = std::log((double)n_atoms);
+        return PNX_OK;
+    }
+    double top = -HUGE_VAL;
+    for (int g = 0; g < n_atoms; ++g) {
+        const double l = log_prior[g];
+        if (std::isnan(l) || l == HUGE_VAL) return set_error(PNX_ERR_INVALID, "%s: log_prior[%d]=%g must be finite or -inf", who, g, l);
+        top = l > top ? l : top;
+    }
+    if (top == -HUGE_VAL) return set_error(PNX_ERR_INVALID, "%s: log_prior excludes every atom (all %d entries are -inf)", who, n_atoms);
+    double s = 0.0;
+    for (int g = 0; g < n_atoms; ++g) s += std::exp(log_prior[g] - top);
+    *norm = top + std::log(s);
+    return PNX_OK;
+}
+
 // grid_check_args (the refusals and the atom / bounds checks of grid start, unchanged), then the two new inputs.  Every refusal
 // names its argument.  `mean` takes the place of p0_out: the one output that may not be NULL.
 inline int grid_posterior_check_args(const pnx_curvefit_opts *o, int64_t n_vox, const double *b, const double *y, int n_atoms,
@@ -27,22 +47,7 @@ inline int grid_posterior_check_args(const pnx_curvefit_opts *o, int64_t n_vox, 
     if (!(noise_sd >= 0.0) || std::isinf(noise_sd))
         return set_error(PNX_ERR_INVALID, "grid posterior: noise_sd=%g must be finite and > 0 (known noise) or 0 (marginalised)", noise_sd);
     if (int rc = grid_check_args(o, n_vox, b, y, n_atoms, atoms, fixed, lo, hi, project_amplitude, mean, mem, &H->s0_row)) return rc;
-    // the prior: finite or -inf, at least one finite; its normaliser by a two-pass log-sum-exp
-    double top = -HUGE_VAL;
-    if (log_prior) {
-        for (int g = 0; g < n_atoms; ++g) {
-            const double l = log_prior[g];
-            if (std::isnan(l) || l == HUGE_VAL)
-                return set_error(PNX_ERR_INVALID, "grid posterior: log_prior[%d]=%g must be finite or -inf", g, l);
-            top = l > top ? l : top;
-        }
-        if (top == -HUGE_VAL) return set_error(PNX_ERR_INVALID, "grid posterior: log_prior excludes every atom (all %d entries are -inf)", n_atoms);
-        double s = 0.0;
-        for (int g = 0; g < n_atoms; ++g) s += std::exp(log_prior[g] - top);
-        H->log_prior_norm = top + std::log(s);
-    } else {
-        H->log_prior_norm = std::log((double)n_atoms);
-    }
+    if (int rc = posterior_check_log_prior("grid posterior", n_atoms, log_prior, &H->log_prior_norm)) return rc;
     // centres: min + (max - min) / 2 over the admissible atoms, exact when they all hold one value
     for (int k = 0; k < o->n_free; ++k) {
         double mn = HUGE_VAL, mx = -HUGE_VAL;

@@ -12,10 +12,10 @@ its constraint sum(f_i) <= 1, not in its algorithm (pnx_curvefit_simplex_f64).
 (pnx_loglinear_f64), with the reference's solver contract.  `HipPeelSolver` likewise: exponential peeling of the bi- and
 tri-exponential models (pnx_peel_f64).  `HipBayesGridSolver` likewise: posterior mean and sd over a parameter grid
 (pnx_curvefit_grid_posterior_f64).  `HipVarProSolver` likewise: rates on a grid, fractions and S0 in closed form
-(pnx_curvefit_varpro_f64).
+(pnx_curvefit_varpro_f64); `HipBayesVarProSolver` the posterior over that dictionary (pnx_curvefit_varpro_posterior_f64).
 
 Registered under the `pyneapple.solvers` entry-point group (pyproject.toml) as `hip_curvefit` / `hip_nnls` /
-`hip_constrained_curvefit` / `hip_loglinear` / `hip_peel` / `hip_bayes_grid` / `hip_varpro`;
+`hip_constrained_curvefit` / `hip_loglinear` / `hip_peel` / `hip_bayes_grid` / `hip_varpro` / `hip_bayes_varpro`;
 extra scalar keys of `[Fitting.solver]` arrive as keyword arguments (io/toml.py:328-338): `device`,
 `n_gpus`, `jacobian`.
 """
@@ -1070,6 +1070,113 @@ class HipVarProSolver(RefBaseSolver):
                                                lambda i, a=atom: None if a[i] >= 0 else _VARPRO_MESSAGES[-2])
         self.params_ = {name: [float(params[i, 0])] if n_pixels == 1 else params[i] for i, name in enumerate(names)}
         self.diagnostics_ = {"atom": atom, "cost": res["cost"], "clipped": res["clipped"], "n_pixels": n_pixels}
+        return self
+
+
+class HipBayesVarProSolver(RefBaseSolver):
+    """Bayesian fit per voxel over a variable-projection dictionary (pnx_curvefit_varpro_posterior_f64, include/pnx.h; Bretthorst's
+    treatment of sums of exponentials): only the rates (and a free T1) are on a grid, the fractions and S0 of every voxel and atom
+    are eliminated in closed form, and the posterior -- mean, standard deviation, evidence, effective sample size -- lives on the
+    rate grid alone: about 19 values per axis where HipBayesGridSolver's full grid has 4, and no per-voxel prior on fractions
+    and S0.  No iteration: the cost does not depend on the noise.  Registered as `hip_bayes_varpro`; no counterpart in the
+    reference, whose solver contract it keeps.
+
+    model: any of the seven layouts; shared fixed rates / T1 and the T1 / STEAM factor as the curve fit takes them; a fixed fraction
+    or a fixed S0 is refused.  `max_iter`, `tol` are accepted because the TOML loader always passes them.  Arguments:
+        rates, ordered, bounds, p0: as HipVarProSolver takes them (TOML: arrays under [Fitting.solver.rates]); at most 4096 atoms;
+            bounds is the box the amplitudes are clipped into; lo of S0 >= 0.
+        noise_sd: None / 0 (default) marginalises the noise scale under a Jeffreys prior; > 0 is a known Gaussian noise sd in the
+            units of the (sigma-weighted) signal.
+        log_prior: None (uniform) or (n_atoms,) log weights in the order of the atoms; -inf excludes an atom.
+        marginal_amplitudes: True (default) weighs an atom by the marginal over its amplitudes under a flat prior (the Occam term
+            -0.5 log det N); False by the profile over them.
+        sigma: None, a scalar or (n_b,), as HipCurveFitSolver's.  device: HIP device index.
+    Two stated approximations: where a clip into `bounds` is active the marginal weight is a Laplace-style approximation at the
+    clipped point (diagnostics_["clipped_mass"] says how much of the posterior rests on such atoms); and the sd of a fraction or of
+    S0 is the between-atom spread only -- the conditional variance of the amplitudes given the rates is left out, a known
+    understatement.
+    Not built, hence a ValueError: per-pixel fixed parameters (the dictionary would differ from voxel to voxel), io_dtype or
+    precision "float32".  Any other keyword (the reference's solver arguments: method, multi_threading, ...) is accepted and ignored.
+    After fit: params_ = the posterior mean keyed by the model's names; diagnostics_ {"posterior_sd", "map" (dicts name ->
+    (n_pixels,)), "map_atom", "log_evidence", "ess", "clipped_mass", "n_pixels"}; pixel_results_ with success = the voxel's signal
+    was finite."""
+
+    def __init__(self, model: Any, rates=None, max_iter: int = 250, tol: float = 1e-8, p0: dict[str, float] | None = None,
+                 bounds: dict[str, tuple[float, float]] | None = None, ordered: bool = True, noise_sd: float | None = None, log_prior=None,
+                 marginal_amplitudes: bool = True, sigma=None, device: int = 0, io_dtype: str = "float64", precision: str = "float64",
+                 **ignored_reference_kwargs):
+        RefBaseSolver.__init__(self, model=model, max_iter=max_iter, tol=tol, verbose=bool(ignored_reference_kwargs.pop("verbose", False)))
+        self._kernel_model = kernel_model_key(model)
+        self._kernel_t1 = kernel_t1(model)
+        if _io_dtype(io_dtype) is not np.float64 or precision != "float64":
+            raise ValueError("HipBayesVarProSolver is built for precision='float64' and io_dtype='float64': the posterior reads and "
+                             "writes float64 arrays and exponentiates in fp64")
+        if rates is None:
+            raise ValueError("rates is required: a dict from the name of a non-linear parameter to a sequence of values")
+        names = list(model.param_names)
+        if bounds is None:
+            raise ValueError(f"bounds is required: {{name: (lo, hi)}} for every parameter of {names}")
+        _validate_parameter_names(bounds, names)
+        self.ordered = bool(ordered)
+        self.rates, self._nl_names, self._nl_atoms = _varpro_atoms("rates", model, self._kernel_model, p0, bounds, rates, self.ordered)
+        if "S0" in names and not bounds["S0"][0] >= 0:
+            raise ValueError(f"the lower bound of S0 must be >= 0 (the fraction bounds scale with S0), got {bounds['S0'][0]}")
+        self.noise_sd = 0.0 if noise_sd is None else float(noise_sd)
+        if not (np.isfinite(self.noise_sd) and self.noise_sd >= 0.0):
+            raise ValueError(f"noise_sd must be None / 0 (marginalised) or a finite positive standard deviation, got {noise_sd!r}")
+        self.log_prior = None
+        if log_prior is not None:
+            lp = np.ascontiguousarray(log_prior, np.float64).reshape(-1)
+            if lp.shape != (self._nl_atoms.shape[1],):
+                raise ValueError(f"log_prior has {lp.size} entries for {self._nl_atoms.shape[1]} atoms (one per atom, in the order of the "
+                                 "atoms)")
+            if np.isnan(lp).any() or (lp == np.inf).any() or not np.isfinite(lp).any():
+                raise ValueError("log_prior entries must be finite or -inf, at least one of them finite")
+            self.log_prior = lp
+        self.marginal_amplitudes = bool(marginal_amplitudes)
+        self.sigma = None
+        if sigma is not None:
+            self.sigma = np.asarray(sigma, float)
+            if self.sigma.ndim > 1 and self.sigma.size != 1:
+                raise ValueError("HipBayesVarProSolver implements a scalar or 1-D sigma (one standard deviation per b-value)")
+            self.sigma = self.sigma.reshape(-1)
+        self.p0 = p0
+        self.bounds = bounds
+        self.device = int(device)
+        self.io_dtype = np.float64
+        self.solver_kwargs = ignored_reference_kwargs
+
+    def fit(self, xdata: np.ndarray, ydata: np.ndarray, pixel_fixed_params=None, **fit_kwargs) -> "HipBayesVarProSolver":
+        if pixel_fixed_params:
+            raise ValueError("HipBayesVarProSolver is not built with per-pixel fixed parameters (pixel_fixed_params): the dictionary "
+                             "would differ from voxel to voxel")
+        self._reset_state()
+        xdata = np.asarray(xdata)
+        ydata = np.asarray(ydata)
+        _validate_data_shapes(xdata, ydata)
+        if ydata.ndim == 1:
+            ydata = ydata[np.newaxis, :]
+        if ydata.ndim > 2:
+            raise ValueError(f"ydata must be 1D or 2D array, but got shape {ydata.shape}.")
+        n_pixels = ydata.shape[0]
+        names = list(self.model.param_names)
+        all_names = list(self.model._all_param_names)
+        fixed = getattr(self.model, "fixed_params", None) or {}
+        fixed_idx = [i for i, n in enumerate(all_names) if n in fixed]
+        fixed_vals = np.array([float(fixed[all_names[i]]) for i in fixed_idx]) if fixed_idx else None
+        lo = np.array([self.bounds[n][0] for n in names], float)
+        hi = np.array([self.bounds[n][1] for n in names], float)
+        res = api.varpro_posterior(self._kernel_model, xdata, ydata, self._nl_atoms, lo, hi, log_prior=self.log_prior, noise_sd=self.noise_sd,
+                                   marginal_amplitudes=self.marginal_amplitudes, fixed_idx=fixed_idx, fixed_vals=fixed_vals, sigma=self.sigma,
+                                   device=self.device, **self._kernel_t1)
+        mean, atom = res["mean"], res["map_atom"]
+        self.pixel_results_ = PixelResultsView(mean.T, None, atom >= 0,
+                                               lambda i, a=atom: None if a[i] >= 0 else _BAYES_MESSAGES[-2])
+        self.params_ = {name: [float(mean[i, 0])] if n_pixels == 1 else mean[i] for i, name in enumerate(names)}
+        self.diagnostics_ = {"posterior_sd": {n: res["sd"][i] for i, n in enumerate(names)},
+                             "map": {n: res["map_p"][i] for i, n in enumerate(names)}, "map_atom": atom,
+                             "log_evidence": res["log_evidence"], "ess": res["ess"], "clipped_mass": res["clipped_mass"],
+                             "n_pixels": n_pixels}
         return self
 
 
