@@ -440,6 +440,38 @@ PNX_API int pnx_curvefit_grid_posterior_f64(const pnx_curvefit_opts *opts, int64
                                     int32_t *map_atom, double *map_p, double *log_evidence, double *ess, int mem, int device,
                                     void *stream);
 /*
+ * The prior of pnx_curvefit_grid_posterior_f64 learned from the volume itself (empirical Bayes): the
+ * non-parametric maximum-likelihood mixture over the dictionary, by EM.  The arguments up to noise_sd, the weighting, the refusals
+ * and l_g are pnx_curvefit_grid_posterior_f64's.  With pi the current prior (log_prior_g = log pi_g inside l_g), one update is
+ *   L_v = log sum_g exp(l_g(v));  W_vg = exp(l_g(v) - L_v);  S_g = sum over the finite voxels of W_vg;
+ *   pi_g <- (S_g + pseudo_count) / (n_eff + pseudo_count n_adm)        n_adm: the atoms the start prior admits (finite entries)
+ * and log_prior_g <- log pi_g, -inf where pi_g == 0 and always -inf for an atom that started at -inf.  The (n_vox, n_atoms) matrix
+ * W never reaches memory; no sum uses an atomic, so a call is reproducible bit for bit on a given device.
+ *   log_prior (n_atoms,) host or NULL (uniform): the start, as the posterior takes it; it is normalised first,
+ *     log_prior - log sum exp(log_prior), and every reported prior sums to 1 over its finite entries -- so the sum of log_evidence
+ *     of a later posterior call under log_prior_out is the last entry of the trace;
+ *   n_iter in [1, 1000]: the most updates; pseudo_count finite, >= 0; rel_tol finite, >= 0 (PNX_ERR_INVALID otherwise, with a
+ *     message, before any device work);
+ *   log_prior_out (n_atoms,) host, not NULL: the prior after `done` updates;
+ *   loglik (n_iter + 1,) host or NULL: loglik[t] = sum over the finite voxels of L_v under the prior BEFORE update t, t = 0 .. done;
+ *     loglik[done] belongs to the returned prior (one more normaliser pass); entries past `done` are NaN;
+ *   n_iter_done: `done`.  After update t >= 1 the call stops when loglik[t] - loglik[t-1] <= rel_tol |loglik[t]|; rel_tol = 0 runs
+ *     all n_iter updates;
+ *   n_eff: the number of voxels with a finite (weighted) signal; the others take no part.  Without one the call returns PNX_OK
+ *     with the normalised start prior, done = 0 and loglik[0] = 0.
+ * The prior is learned from the voxels it will be applied to: it needs many more voxels than atoms carry weight, and a few dozen
+ * voxels over-fit.
+ *   y (n_vox, n_b) host|device as `mem`.  PNX_MEM_DEVICE: read in place.  PNX_MEM_HOST: uploaded once (pnx_upload's path) into a
+ *   stream-ordered buffer that stays for all iterations -- every pass reads the same signals, so there is no chunk ring;
+ *   PNX_ERR_NOMEM names the size and points to a sub-sample.  The outputs are small host arrays: for both `mem` values the call
+ *   SYNCHRONISES `stream` before it returns (once per iteration, for 16 bytes, and at the end).
+ */
+PNX_API int pnx_curvefit_grid_prior_em_f64(const pnx_curvefit_opts *opts, int64_t n_vox, const double *b, const double *y, int n_atoms,
+                                   const double *atoms, const double *fixed, const double *lo, const double *hi,
+                                   int project_amplitude, const double *log_prior, double noise_sd, int n_iter, double pseudo_count,
+                                   double rel_tol, double *log_prior_out, double *loglik, int *n_iter_done, int64_t *n_eff, int mem,
+                                   int device, void *stream);
+/*
  * Variable-projection dictionary fit (VARPRO, separable least squares): only the NON-LINEAR parameters of a
  * layout -- the K rates, and T1 where it is free -- are on the grid; the fractions and S0 of every voxel-atom pair come in closed
  * form.  Every layout is sum_j a_j phi_j(b) with K = 1 (mono), 2 (bi) or 3 (tri) unit columns phi_j = model(b; one-hot fractions,

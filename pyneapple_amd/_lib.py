@@ -28,7 +28,7 @@ ABI_SYMBOLS = [
     "pnx_label_sums_f64", "pnx_release_staging", "pnx_queue_order_f64",
     "pnx_nnls_fit_stats_f64", "pnx_nnls_solve_peaks_stats_f64", "pnx_curvefit_predict_f64", "pnx_curvefit_fast_f32",
     "pnx_curvefit_simplex_f64", "pnx_ideal_bounds_simplex_f64", "pnx_curvefit_grid_start_f64",
-    "pnx_curvefit_grid_posterior_f64", "pnx_curvefit_varpro_f64", "pnx_curvefit_varpro_posterior_f64",
+    "pnx_curvefit_grid_posterior_f64", "pnx_curvefit_grid_prior_em_f64", "pnx_curvefit_varpro_f64", "pnx_curvefit_varpro_posterior_f64",
     "pnx_loglinear_f64", "pnx_loglinear_f32", "pnx_peel_f64", "pnx_peel_f32",
 ]
 
@@ -122,6 +122,11 @@ def load():
     lib.pnx_curvefit_grid_posterior_f64.restype = C.c_int  # grid start's inputs, log_prior, noise_sd, mean, sd, map_atom, map_p, log_evidence, ess
     lib.pnx_curvefit_grid_posterior_f64.argtypes = [C.POINTER(CurvefitOpts), C.c_int64, dp, dp, C.c_int, dp, dp, dp, dp, C.c_int, dp, C.c_double,
                                                     dp, dp, vp, dp, dp, dp, C.c_int, C.c_int, vp]
+    # the posterior's inputs, n_iter, pseudo_count, rel_tol, log_prior_out, loglik, n_iter_done, n_eff
+    lib.pnx_curvefit_grid_prior_em_f64.restype = C.c_int
+    lib.pnx_curvefit_grid_prior_em_f64.argtypes = [C.POINTER(CurvefitOpts), C.c_int64, dp, dp, C.c_int, dp, dp, dp, dp, C.c_int, dp, C.c_double,
+                                                   C.c_int, C.c_double, C.c_double, dp, dp, C.POINTER(C.c_int), C.POINTER(C.c_int64),
+                                                   C.c_int, C.c_int, vp]
     lib.pnx_curvefit_varpro_f64.restype = C.c_int  # opts, n_vox, b, y, n_atoms, nl_atoms, fixed, lo, hi, fallback, p_out, best, cost, clipped
     lib.pnx_curvefit_varpro_f64.argtypes = [C.POINTER(CurvefitOpts), C.c_int64, dp, dp, C.c_int, dp, dp, dp, dp, dp, dp, vp, dp, vp,
                                             C.c_int, C.c_int, vp]

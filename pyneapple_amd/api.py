@@ -353,6 +353,73 @@ def grid_posterior_device(opts, n_vox, b, y, atoms, fixed, lo, hi, project_ampli
                                                  ptr(map_atom), ptr(map_p), ptr(log_evidence), ptr(ess), MEM_DEVICE, int(device), stream))
 
 
+def grid_prior_slab_atoms(n_b):
+    """Atoms per LDS slab of the two EM passes (grid_prior_slab of csrc/pnx_grid_prior_args.hpp): the posterior's slab at four
+    parameter rows -- the four wave-private rows of the accumulate pass take the place of the parameter values."""
+    return grid_posterior_slab_atoms(n_b, 4)
+
+
+def _prior_em_call(o, n_vox, b, y, atoms, fv, lo, hi, project_amplitude, lp, noise_sd, n_iter, pseudo_count, rel_tol, mem, device, stream):
+    n_iter = int(n_iter)
+    out = np.empty(atoms.shape[1], np.float64)
+    loglik = np.full(min(max(n_iter, 0), 1000) + 1, np.nan)  # outside 1..1000 the library refuses before it writes
+    done, n_eff = C.c_int(0), C.c_int64(0)
+    check(load().pnx_curvefit_grid_prior_em_f64(C.byref(o), int(n_vox), ptr(b), ptr(y), int(atoms.shape[1]), ptr(atoms), ptr(fv), ptr(lo),
+                                                ptr(hi), int(bool(project_amplitude)), ptr(lp), float(noise_sd), n_iter, float(pseudo_count),
+                                                float(rel_tol), ptr(out), ptr(loglik), C.byref(done), C.byref(n_eff), mem, int(device),
+                                                stream))
+    return dict(log_prior=out, loglik=loglik, n_iter=int(done.value), n_eff=int(n_eff.value))
+
+
+def grid_prior_em(model, b, y, atoms, lo, hi, *, log_prior=None, noise_sd=0.0, n_iter=20, pseudo_count=0.0, rel_tol=1e-6, fixed_idx=(),
+                  fixed_vals=None, sigma=None, project_amplitude=False, t1_mode=0, tr=0., tm=0., device=0):
+    """The prior of `grid_posterior` learned from the voxels themselves on host (numpy) arrays (pnx_curvefit_grid_prior_em_f64;
+    method: include/pnx.h): the maximum-likelihood mixture over the atoms by EM, pi_g <- mean over the finite voxels of their
+    posterior weight on atom g.  The arguments of `grid_posterior` (log_prior is the start: None is uniform, an atom at -inf stays
+    excluded), and
+    n_iter: the most updates, 1..1000;  pseudo_count >= 0: added to every admissible atom's weight sum (0: plain maximum likelihood);
+    rel_tol >= 0: stop once an update gains at most rel_tol |loglik| (0 runs all n_iter).
+    Returns dict(log_prior (n_atoms,) normalised -- ready for `grid_posterior(..., log_prior=...)` --, loglik (n_iter + 1,) the
+    log-likelihood of the volume under the prior before each update and under the returned one, NaN past n_iter, n_iter the updates
+    done, n_eff the voxels with a finite signal).  The prior needs many voxels: a few dozen over-fit."""
+    _lib.require_device()
+    b = np.ascontiguousarray(b, np.float64)
+    y = np.ascontiguousarray(np.atleast_2d(y), np.float64)
+    n_vox, n_b = y.shape
+    if b.shape != (n_b,):
+        raise ValueError(f"b has shape {b.shape}, expected ({n_b},)")
+    atoms, lo, hi = (np.ascontiguousarray(a, np.float64) for a in (atoms, lo, hi))
+    fv = None
+    if len(fixed_idx):
+        fv = np.ascontiguousarray(fixed_vals, np.float64)
+        if fv.ndim != 1:
+            raise ValueError("grid_prior_em takes shared fixed values (n_fixed,): per-voxel fixed maps are not built")
+    o = make_opts(model, n_b, fixed_idx, jac="analytic", t1_mode=t1_mode, tr=tr, tm=tm, sigma=sigma)
+    n = o.n_free
+    if atoms.ndim != 2 or atoms.shape[0] != n or lo.shape != (n,) or hi.shape != (n,):
+        raise ValueError(f"atoms must have shape ({n}, n_atoms), lo / hi ({n},)")
+    if fv is not None and fv.shape != (o.n_fixed,):
+        raise ValueError("fixed_vals has the wrong shape")
+    lp = _posterior_log_prior(log_prior, atoms.shape[1])
+    return _prior_em_call(o, n_vox, b, y, atoms, fv, lo, hi, project_amplitude, lp, noise_sd, n_iter, pseudo_count, rel_tol, MEM_HOST, device,
+                          None)
+
+
+def grid_prior_em_device(opts, n_vox, b, y, atoms, fixed, lo, hi, project_amplitude, log_prior, noise_sd, n_iter, pseudo_count, rel_tol,
+                         device, stream=None):
+    """`grid_prior_em` on an HBM-resident float64 torch tensor y (n_vox, n_b), read in place; b, atoms (n_free, n_atoms), shared fixed
+    values, lo, hi and log_prior (n_atoms,) or None are host arrays, `opts` from make_opts.  The results are small host arrays, so
+    unlike `grid_posterior_device` the call synchronises `stream` before it returns the same dict."""
+    b, atoms, lo, hi = (np.ascontiguousarray(a, np.float64) for a in (b, atoms, lo, hi))
+    if fixed is not None:
+        fixed = np.ascontiguousarray(fixed, np.float64)
+    if atoms.ndim != 2:
+        raise ValueError("atoms must have shape (n_free, n_atoms)")
+    lp = _posterior_log_prior(log_prior, atoms.shape[1])
+    return _prior_em_call(opts, n_vox, b, y, atoms, fixed, lo, hi, project_amplitude, lp, noise_sd, n_iter, pseudo_count, rel_tol, MEM_DEVICE,
+                          device, stream)
+
+
 VARPRO_COMPARTMENTS = {"mono": 1, "bi_reduced": 2, "bi_s0": 2, "bi_full": 2, "tri_reduced": 3, "tri_s0": 3, "tri_full": 3}
 
 

@@ -21,6 +21,7 @@
 #include "pnx_grid.hpp"
 #include "pnx_grid_args.hpp"
 #include "pnx_grid_posterior.hpp"
+#include "pnx_grid_prior.hpp"
 #include "pnx_host_pipeline.hpp"
 #include "pnx_launch.hpp"
 #include "pnx_loglin.hpp"
@@ -1289,6 +1290,68 @@ int pnx_curvefit_grid_posterior_f64(const pnx_curvefit_opts *o, int64_t n_vox, c
         return grid_posterior_device(D, P, (int64_t)n, S.d(GP_Y), S.d(GP_MEAN), S.d(GP_SD), (int32_t *)S.dev[GP_ATOM], S.d(GP_MAPP), S.d(GP_LOGEV),
                                      S.d(GP_ESS), dev->cus, s);
     });
+}
+
+// ---- the prior over the dictionary learned from the volume (kernels: pnx_grid_prior.hip, argument checks: pnx_grid_prior_args.hpp)
+int pnx_curvefit_grid_prior_em_f64(const pnx_curvefit_opts *o, int64_t n_vox, const double *b, const double *y, int n_atoms,
+                                   const double *atoms, const double *fixed, const double *lo, const double *hi, int project_amplitude,
+                                   const double *log_prior, double noise_sd, int n_iter, double pseudo_count, double rel_tol,
+                                   double *log_prior_out, double *loglik, int *n_iter_done, int64_t *n_eff, int mem, int device, void *stream) {
+    if (!o) return set_error(PNX_ERR_INVALID, "opts is NULL");
+    pnx_curvefit_opts c = *o;  // as grid start: jac_mode and the tolerances are not looked at
+    c.jac_mode = PNX_JAC_ANALYTIC;
+    c.ftol = c.xtol = c.gtol = 0.0;
+    int rc = check_curvefit_opts(&c);
+    if (rc) return rc;
+    GridPosteriorHost H;
+    if ((rc = grid_prior_check_args(&c, n_vox, b, y, n_atoms, atoms, fixed, lo, hi, project_amplitude, log_prior, noise_sd, n_iter, pseudo_count,
+                                    rel_tol, log_prior_out, mem, &H)))
+        return rc;
+    const int n_adm = grid_prior_start(n_atoms, log_prior, H.log_prior_norm, log_prior_out);  // the start, normalised
+    if (loglik) loglik[0] = 0.0;
+    if (n_vox == 0) {
+        grid_prior_report(n_iter, 0, 0, loglik, n_iter_done, n_eff);
+        return PNX_OK;
+    }
+    DeviceInfo *dev;
+    if ((rc = use_device(device, &dev))) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    AsyncBuf dict_buf, post_buf, work_buf, y_buf;  // stream-ordered, freed behind the work that reads them
+    GridDict D;
+    GridPosterior P;
+    GridPriorWork W;
+    if ((rc = dict_buf.alloc(grid_dict_bytes(c.n_free, n_atoms, c.n_b), st))) return rc;
+    if ((rc = post_buf.alloc(grid_posterior_bytes(c.n_free, n_atoms), st))) return rc;
+    if ((rc = work_buf.alloc(grid_prior_bytes(n_vox, n_atoms, dev->cus), st))) return rc;
+    if (mem == PNX_MEM_HOST) {  // every pass of every iteration reads the same signals: one upload, kept for the call
+        const size_t bytes = (size_t)n_vox * c.n_b * sizeof(double);
+        if (y_buf.alloc(bytes, st) != PNX_OK)
+            return set_error(PNX_ERR_NOMEM, "grid prior: no device memory for the %zu bytes of y (%lld voxels x %d), which stay resident for all "
+                                            "iterations: learn the prior from a sub-sample of the voxels", bytes, (long long)n_vox, c.n_b);
+        if ((rc = pnx_upload(y_buf.p, y, (int64_t)bytes, device, st, 0))) return rc;
+        y = (const double *)y_buf.p;
+    }
+    if ((rc = grid_dict_build(&c, b, n_atoms, atoms, fixed, lo, hi, H.s0_row, dict_buf.p, &D, st))) return rc;
+    if ((rc = grid_posterior_prepare(D, H, log_prior_out, noise_sd, post_buf.p, &P, st))) return rc;
+    grid_prior_carve(n_vox, n_atoms, dev->cus, work_buf.p, &W);
+    std::vector<double> trace((size_t)n_iter + 1, 0.0);
+    GridPriorStats stats = {0.0, 0};
+    int done = 0;
+    for (int t = 0;; ++t) {  // trace[t]: the log-likelihood under the prior before update t, the returned prior's at t = done
+        if ((rc = grid_prior_normalise(D, P, n_vox, y, W, st))) return rc;
+        PNX_HIP(hipMemcpyAsync(&stats, W.stats, sizeof(stats), hipMemcpyDeviceToHost, st));
+        PNX_HIP(hipStreamSynchronize(st));
+        trace[t] = stats.loglik;
+        done = t;
+        if (stats.n_finite == 0 || t == n_iter || grid_prior_converged(trace.data(), t, rel_tol)) break;
+        if ((rc = grid_prior_update(D, P, n_vox, y, W, pseudo_count, n_adm, st))) return rc;
+    }
+    PNX_HIP(hipMemcpyAsync(log_prior_out, P.lp, (size_t)n_atoms * sizeof(double), hipMemcpyDeviceToHost, st));
+    PNX_HIP(hipStreamSynchronize(st));
+    if (loglik)
+        for (int t = 0; t <= done; ++t) loglik[t] = trace[t];
+    grid_prior_report(n_iter, done, stats.n_finite, loglik, n_iter_done, n_eff);
+    return PNX_OK;
 }
 
 // ---- variable-projection dictionary fit (kernels: pnx_varpro.hip, argument checks: pnx_varpro_args.hpp) ---------------------
