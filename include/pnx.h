@@ -472,6 +472,39 @@ PNX_API int pnx_curvefit_grid_prior_em_f64(const pnx_curvefit_opts *opts, int64_
                                    double rel_tol, double *log_prior_out, double *loglik, int *n_iter_done, int64_t *n_eff, int mem,
                                    int device, void *stream);
 /*
+ * Marginal posterior of every free parameter over the dictionary, and credible-interval quantiles from it.  The
+ * arguments up to noise_sd, the weighting, the dictionary, a_g(v), c_g(v), tol_v, l_g and every refusal are
+ * pnx_curvefit_grid_posterior_f64's.  The atoms sit on a grid: along free parameter k every atom holds one of n_bins[k] values.
+ *   n_bins (n_free,) int32 host: the number of distinct grid values of each free parameter; 0: no marginal for that parameter.
+ *     B = sum n_bins must lie in [1, 128]; under project_amplitude the S0 row must hold 0 (its value is a_g(v), not a grid value);
+ *   bin_of (n_free, n_atoms) int32 host: the bin of atom g along parameter k, in [0, n_bins[k]); rows with n_bins[k] == 0 are
+ *     not read;
+ *   bin_value (B,) host: the grid value of every bin, parameter k's at offset off_k = sum_{i<k} n_bins[i], strictly ascending within
+ *     a parameter; every atom must satisfy atoms[k, g] == bin_value[off_k + bin_of[k, g]] exactly;
+ *   n_q in [0, 8], probs (n_q,) host, each in the open interval (0, 1).
+ * Every violation is PNX_ERR_INVALID with a message that names the first offender, before any device work.
+ * Per finite voxel v, in fp64:  L = log sum_g exp(l_g);  W_g = exp(l_g - L), exactly 0 for a padded or excluded atom;
+ *   marginal[off_k + j, v] = sum over the atoms with bin_of[k, g] == j of W_g      (not renormalised afterwards)
+ *   cdf_j = the running sum of marginal over j in bin order;  quantile[i, k, v] = bin_value of the first bin with
+ *     cdf_j >= probs[i], of the last bin of k when none reaches it (no interpolation), NaN for a parameter with n_bins[k] == 0;
+ *   log_evidence = L - log sum_g exp(log_prior_g), the posterior's (from the normaliser pass: equal within its rounding bound).
+ * A voxel with a non-finite (weighted) signal gets NaN in every output; its neighbours are not affected.
+ *   marginal (B, n_vox) bin-major, not NULL; quantile (n_q, n_free, n_vox), NULL only when n_q == 0; log_evidence (n_vox) or NULL:
+ *   out, host|device as `mem`.
+ * Two passes over the product y_v . s_g (the normaliser of pnx_curvefit_grid_prior_em_f64, then the weights times a 0/1 indicator
+ * matrix on the matrix cores); the (n_vox, n_atoms) matrix W never reaches memory.  No sum uses an atomic and every sum of a voxel
+ * depends on the order of the atoms only: results are bit-identical between two calls, between PNX_MEM_HOST and PNX_MEM_DEVICE,
+ * and whatever the number of voxels in the call.
+ *   PNX_MEM_DEVICE only enqueues.  PNX_MEM_HOST: y is uploaded once (pnx_upload's path) and the outputs come back from one
+ *   stream-ordered buffer (pnx_download's path), as pnx_curvefit_grid_prior_em_f64 stages its signals -- no chunk ring;
+ *   PNX_ERR_NOMEM names the sizes.
+ */
+PNX_API int pnx_curvefit_grid_marginals_f64(const pnx_curvefit_opts *opts, int64_t n_vox, const double *b, const double *y, int n_atoms,
+                                    const double *atoms, const double *fixed, const double *lo, const double *hi,
+                                    int project_amplitude, const double *log_prior, double noise_sd, const int32_t *n_bins,
+                                    const int32_t *bin_of, const double *bin_value, int n_q, const double *probs, double *marginal,
+                                    double *quantile, double *log_evidence, int mem, int device, void *stream);
+/*
  * Variable-projection dictionary fit (VARPRO, separable least squares): only the NON-LINEAR parameters of a
  * layout -- the K rates, and T1 where it is free -- are on the grid; the fractions and S0 of every voxel-atom pair come in closed
  * form.  Every layout is sum_j a_j phi_j(b) with K = 1 (mono), 2 (bi) or 3 (tri) unit columns phi_j = model(b; one-hot fractions,

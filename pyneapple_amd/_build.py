@@ -38,6 +38,8 @@ SOURCE_GROUPS = {
     "grid_posterior": ["pnx_grid_posterior.hip", "pnx_grid_posterior.hpp", "pnx_grid_posterior_args.hpp", "pnx_grid.hpp", "pnx_grid_args.hpp"],
     "grid_prior": ["pnx_grid_prior.hip", "pnx_grid_prior.hpp", "pnx_grid_prior_args.hpp", "pnx_grid_posterior.hpp",
                    "pnx_grid_posterior_args.hpp", "pnx_grid.hpp", "pnx_grid_args.hpp"],
+    "grid_marginal": ["pnx_grid_marginal.hip", "pnx_grid_marginal.hpp", "pnx_grid_marginal_args.hpp", "pnx_grid_prior.hpp",
+                      "pnx_grid_prior_args.hpp", "pnx_grid_posterior.hpp", "pnx_grid_posterior_args.hpp", "pnx_grid.hpp", "pnx_grid_args.hpp"],
     "varpro": ["pnx_varpro.hip", "pnx_varpro.hpp", "pnx_varpro_args.hpp", "pnx_grid_args.hpp", "pnx_predict.hpp"],
     "varpro_posterior": ["pnx_varpro_posterior.hip", "pnx_varpro_posterior.hpp", "pnx_varpro_posterior_args.hpp", "pnx_varpro.hpp",
                          "pnx_varpro_args.hpp", "pnx_grid_posterior_args.hpp", "pnx_grid_args.hpp"],
@@ -72,6 +74,7 @@ def _units():
              ("pnx_resize.o", "pnx_resize.hip", []), ("pnx_predict.o", "pnx_predict.hip", []),
              ("pnx_simplex.o", "pnx_simplex.hip", []), ("pnx_grid.o", "pnx_grid.hip", []),
              ("pnx_grid_posterior.o", "pnx_grid_posterior.hip", []), ("pnx_grid_prior.o", "pnx_grid_prior.hip", []),
+             ("pnx_grid_marginal.o", "pnx_grid_marginal.hip", []),
              ("pnx_varpro.o", "pnx_varpro.hip", []),
              ("pnx_varpro_posterior.o", "pnx_varpro_posterior.hip", []),
              ("pnx_loglin.o", "pnx_loglin.hip", []), ("pnx_peel.o", "pnx_peel.hip", []),
@@ -118,14 +121,16 @@ def _stale(unit, force: bool) -> bool:
         deps = [d for d in deps if "pnx_nnls" not in os.path.basename(d)]  # these units include no NNLS header
     if src == "pnx_varpro_posterior.hip":  # the args headers of its two parents and the slab rule
         deps = [d for d in deps if os.path.basename(d) in ("pnx_grid_args.hpp", "pnx_grid_posterior_args.hpp") or "pnx_grid" not in os.path.basename(d)]
-    elif src not in ("pnx_api.hip", "pnx_grid.hip", "pnx_grid_posterior.hip", "pnx_grid_prior.hip", "pnx_varpro.hip"):
+    elif src not in ("pnx_api.hip", "pnx_grid.hip", "pnx_grid_posterior.hip", "pnx_grid_prior.hip", "pnx_grid_marginal.hip", "pnx_varpro.hip"):
         deps = [d for d in deps if "pnx_grid" not in os.path.basename(d)]  # the dictionary search's headers: its units and the ABI's
     elif src == "pnx_varpro.hip":
         deps = [d for d in deps if os.path.basename(d) == "pnx_grid_args.hpp" or "pnx_grid" not in os.path.basename(d)]  # of those, the slab rule only
     elif src == "pnx_grid.hip":
         deps = [d for d in deps if "pnx_grid_posterior" not in os.path.basename(d)]  # the posterior's headers: its unit and the ABI's
-    if src not in ("pnx_api.hip", "pnx_grid_prior.hip"):
+    if src not in ("pnx_api.hip", "pnx_grid_prior.hip", "pnx_grid_marginal.hip"):
         deps = [d for d in deps if "pnx_grid_prior" not in os.path.basename(d)]  # the EM prior's headers: likewise
+    if src not in ("pnx_api.hip", "pnx_grid_marginal.hip"):
+        deps = [d for d in deps if "pnx_grid_marginal" not in os.path.basename(d)]  # the marginals' headers: likewise
     if src not in ("pnx_api.hip", "pnx_loglin.hip"):
         deps = [d for d in deps if "pnx_loglin" not in os.path.basename(d)]  # the log-linear fit's headers: likewise
     if src == "pnx_varpro.hip":

@@ -420,6 +420,130 @@ def grid_prior_em_device(opts, n_vox, b, y, atoms, fixed, lo, hi, project_amplit
                           device, stream)
 
 
+GRID_MARGINAL_MAX_BINS = 128  # kGridMarginalMaxBins of csrc/pnx_grid_marginal_args.hpp
+GRID_MARGINAL_MAX_PROBS = 8
+
+
+def grid_marginal_bins(atoms, skip_rows=()):
+    """The binning of `grid_marginals` derived from the atoms: per row k of atoms (n_free, n_atoms) np.unique(atoms[k],
+    return_inverse=True) -- the ascending distinct values and the bin of every atom among them; a Cartesian grid need not be
+    complete nor ordered.  skip_rows: rows without a marginal (n_bins = 0; the projected S0 row).  Returns (n_bins (n_free,) int32,
+    bin_of (n_free, n_atoms) int32, bin_value (B,) float64)."""
+    atoms = np.asarray(atoms, np.float64)
+    if atoms.ndim != 2:
+        raise ValueError("atoms must have shape (n_free, n_atoms)")
+    n_bins = np.zeros(atoms.shape[0], np.int32)
+    bin_of = np.zeros(atoms.shape, np.int32)
+    values = []
+    for k in range(atoms.shape[0]):
+        if k in skip_rows:
+            continue
+        val, inv = np.unique(atoms[k], return_inverse=True)
+        n_bins[k] = val.size
+        bin_of[k] = inv.reshape(-1)
+        values.append(val)
+    return n_bins, bin_of, np.concatenate(values) if values else np.zeros(0)
+
+
+def _marginal_bins(o, model, atoms, project_amplitude, bins):
+    """(n_bins, bin_of, bin_value) as contiguous arrays of the ABI's types: the caller's, or derived from the atoms."""
+    n = o.n_free
+    if bins is None:
+        skip = ()
+        if project_amplitude and "S0" in MODEL_PARAM_NAMES[model]:
+            pos = MODEL_PARAM_NAMES[model].index("S0")
+            skip = tuple(k for k in range(n) if o.free_idx[k] == pos)
+        bins = grid_marginal_bins(atoms, skip)
+    n_bins, bin_of, bin_value = bins
+    n_bins = np.ascontiguousarray(n_bins, np.int32)
+    bin_of = np.ascontiguousarray(bin_of, np.int32)
+    bin_value = np.ascontiguousarray(bin_value, np.float64)
+    if n_bins.shape != (n,) or bin_of.shape != atoms.shape or (n_bins < 0).any() or bin_value.shape != (int(n_bins.sum()),):
+        raise ValueError(f"bins must be (n_bins ({n},) >= 0, bin_of {atoms.shape}, bin_value (sum n_bins,))")
+    return n_bins, bin_of, bin_value
+
+
+def _marginal_probs(quantiles):
+    return np.ascontiguousarray([] if quantiles is None else quantiles, np.float64).reshape(-1)
+
+
+def _marginal_result(names, n_bins, bin_value, probs, marginal, quantile, log_evidence):
+    """The flat (B, n_vox) and (n_q, n_free, n_vox) outputs split per parameter with a marginal, keyed by its position among the
+    free parameters (or its name when `names` is given)."""
+    off = np.concatenate([[0], np.cumsum(n_bins)])
+    key = (lambda k: k) if names is None else (lambda k: names[k])
+    rows = [k for k in range(len(n_bins)) if n_bins[k]]
+    return dict(marginal={key(k): marginal[off[k]:off[k + 1]] for k in rows}, values={key(k): bin_value[off[k]:off[k + 1]] for k in rows},
+                quantiles={} if quantile is None else {key(k): quantile[:, k] for k in rows}, quantile_probs=probs, log_evidence=log_evidence)
+
+
+def grid_marginals(model, b, y, atoms, lo, hi, *, log_prior=None, noise_sd=0.0, bins=None, quantiles=(0.025, 0.5, 0.975), fixed_idx=(),
+                   fixed_vals=None, sigma=None, project_amplitude=False, t1_mode=0, tr=0., tm=0., device=0):
+    """Marginal posterior of every free parameter over a dictionary on host (numpy) arrays, and quantiles from it
+    (pnx_curvefit_grid_marginals_f64; method: include/pnx.h).  The arguments of `grid_posterior`, and
+    bins: None -- derived from the atoms by `grid_marginal_bins` (np.unique per parameter; no marginal for a projected S0) -- or
+        (n_bins (n_free,), bin_of (n_free, n_atoms), bin_value (sum n_bins,)) as the ABI takes them; at most 128 bins in all;
+    quantiles: up to 8 levels in the open interval (0, 1), or () / None for none.
+    Returns dict(marginal {k: (n_bins_k, n_vox)}, values {k: (n_bins_k,)} the ascending grid values, quantiles {k: (n_q, n_vox)}
+    -- the grid value of the first bin whose cumulative mass reaches the level, not interpolated --, keyed by the position k of the
+    parameter among the free ones (parameters without a marginal are absent), quantile_probs (n_q,), log_evidence (n_vox,)).  A
+    voxel with a non-finite signal holds NaN everywhere."""
+    _lib.require_device()
+    b = np.ascontiguousarray(b, np.float64)
+    y = np.ascontiguousarray(np.atleast_2d(y), np.float64)
+    n_vox, n_b = y.shape
+    if b.shape != (n_b,):
+        raise ValueError(f"b has shape {b.shape}, expected ({n_b},)")
+    atoms, lo, hi = (np.ascontiguousarray(a, np.float64) for a in (atoms, lo, hi))
+    fv = None
+    if len(fixed_idx):
+        fv = np.ascontiguousarray(fixed_vals, np.float64)
+        if fv.ndim != 1:
+            raise ValueError("grid_marginals takes shared fixed values (n_fixed,): per-voxel fixed maps are not built")
+    o = make_opts(model, n_b, fixed_idx, jac="analytic", t1_mode=t1_mode, tr=tr, tm=tm, sigma=sigma)
+    n = o.n_free
+    if atoms.ndim != 2 or atoms.shape[0] != n or lo.shape != (n,) or hi.shape != (n,):
+        raise ValueError(f"atoms must have shape ({n}, n_atoms), lo / hi ({n},)")
+    if fv is not None and fv.shape != (o.n_fixed,):
+        raise ValueError("fixed_vals has the wrong shape")
+    lp = _posterior_log_prior(log_prior, atoms.shape[1])
+    n_bins, bin_of, bin_value = _marginal_bins(o, model, atoms, project_amplitude, bins)
+    probs = _marginal_probs(quantiles)
+    marginal = np.empty((int(n_bins.sum()), n_vox), np.float64)
+    quantile = np.empty((probs.size, n, n_vox), np.float64)
+    log_evidence = np.empty(n_vox, np.float64)
+    check(load().pnx_curvefit_grid_marginals_f64(C.byref(o), n_vox, ptr(b), ptr(y), int(atoms.shape[1]), ptr(atoms), ptr(fv), ptr(lo), ptr(hi),
+                                                 int(bool(project_amplitude)), ptr(lp), float(noise_sd), ptr(n_bins), ptr(bin_of),
+                                                 ptr(bin_value), int(probs.size), ptr(probs) if probs.size else None, ptr(marginal),
+                                                 ptr(quantile) if probs.size else None, ptr(log_evidence), MEM_HOST, int(device), None))
+    return _marginal_result(None, n_bins, bin_value, probs, marginal, quantile, log_evidence)
+
+
+def grid_marginals_device(opts, n_vox, b, y, atoms, fixed, lo, hi, project_amplitude, log_prior, noise_sd, n_bins, bin_of, bin_value, probs,
+                          marginal, quantile, log_evidence, device, stream=None):
+    """Enqueue the marginals on HBM-resident float64 torch tensors (asynchronous; caller synchronises): y (n_vox, n_b), marginal
+    (sum n_bins, n_vox), quantile (n_q, n_free, n_vox) or None when probs is empty, log_evidence (n_vox,) or None on the device; b,
+    atoms (n_free, n_atoms), shared fixed values, lo, hi, log_prior (n_atoms,) or None, the binning (`grid_marginal_bins`) and probs
+    are host arrays.  `opts` from make_opts.  Returns the dict of `grid_marginals` over views of the caller's tensors."""
+    b, atoms, lo, hi = (np.ascontiguousarray(a, np.float64) for a in (b, atoms, lo, hi))
+    if fixed is not None:
+        fixed = np.ascontiguousarray(fixed, np.float64)
+    if atoms.ndim != 2:
+        raise ValueError("atoms must have shape (n_free, n_atoms)")
+    lp = _posterior_log_prior(log_prior, atoms.shape[1])
+    n_bins = np.ascontiguousarray(n_bins, np.int32)
+    bin_of = np.ascontiguousarray(bin_of, np.int32)
+    bin_value = np.ascontiguousarray(bin_value, np.float64)
+    probs = _marginal_probs(probs)
+    if n_bins.shape != (atoms.shape[0],) or bin_of.shape != atoms.shape or (n_bins < 0).any() or bin_value.shape != (int(n_bins.sum()),):
+        raise ValueError(f"the binning must be n_bins ({atoms.shape[0]},) >= 0, bin_of {atoms.shape}, bin_value (sum n_bins,)")
+    check(load().pnx_curvefit_grid_marginals_f64(C.byref(opts), int(n_vox), ptr(b), ptr(y), int(atoms.shape[1]), ptr(atoms), ptr(fixed), ptr(lo),
+                                                 ptr(hi), int(bool(project_amplitude)), ptr(lp), float(noise_sd), ptr(n_bins), ptr(bin_of),
+                                                 ptr(bin_value), int(probs.size), ptr(probs) if probs.size else None, ptr(marginal),
+                                                 ptr(quantile) if probs.size else None, ptr(log_evidence), MEM_DEVICE, int(device), stream))
+    return _marginal_result(None, n_bins, bin_value, probs, marginal, quantile if probs.size else None, log_evidence)
+
+
 VARPRO_COMPARTMENTS = {"mono": 1, "bi_reduced": 2, "bi_s0": 2, "bi_full": 2, "tri_reduced": 3, "tri_s0": 3, "tri_full": 3}
 
 

@@ -21,6 +21,7 @@
 #include "pnx_grid.hpp"
 #include "pnx_grid_args.hpp"
 #include "pnx_grid_posterior.hpp"
+#include "pnx_grid_marginal.hpp"
 #include "pnx_grid_prior.hpp"
 #include "pnx_host_pipeline.hpp"
 #include "pnx_launch.hpp"
@@ -1351,6 +1352,66 @@ int pnx_curvefit_grid_prior_em_f64(const pnx_curvefit_opts *o, int64_t n_vox, co
     if (loglik)
         for (int t = 0; t <= done; ++t) loglik[t] = trace[t];
     grid_prior_report(n_iter, done, stats.n_finite, loglik, n_iter_done, n_eff);
+    return PNX_OK;
+}
+
+// ---- per-parameter marginals of the grid posterior (kernels: pnx_grid_marginal.hip and the EM's normaliser pass, argument
+// checks: pnx_grid_marginal_args.hpp)
+int pnx_curvefit_grid_marginals_f64(const pnx_curvefit_opts *o, int64_t n_vox, const double *b, const double *y, int n_atoms,
+                                    const double *atoms, const double *fixed, const double *lo, const double *hi, int project_amplitude,
+                                    const double *log_prior, double noise_sd, const int32_t *n_bins, const int32_t *bin_of,
+                                    const double *bin_value, int n_q, const double *probs, double *marginal, double *quantile,
+                                    double *log_evidence, int mem, int device, void *stream) {
+    if (!o) return set_error(PNX_ERR_INVALID, "opts is NULL");
+    pnx_curvefit_opts c = *o;  // as grid start: jac_mode and the tolerances are not looked at
+    c.jac_mode = PNX_JAC_ANALYTIC;
+    c.ftol = c.xtol = c.gtol = 0.0;
+    int rc = check_curvefit_opts(&c);
+    if (rc) return rc;
+    GridPosteriorHost H;
+    GridMarginalHost M;
+    if ((rc = grid_marginal_check_args(&c, n_vox, b, y, n_atoms, atoms, fixed, lo, hi, project_amplitude, log_prior, noise_sd, n_bins, bin_of,
+                                       bin_value, n_q, probs, marginal, quantile, mem, &H, &M)))
+        return rc;
+    if (n_vox == 0) return PNX_OK;
+    DeviceInfo *dev;
+    if ((rc = use_device(device, &dev))) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    AsyncBuf dict_buf, post_buf, work_buf, marg_buf, y_buf, out_buf;  // stream-ordered, freed behind the work that reads them
+    GridDict D;
+    GridPosterior P;
+    GridPriorWork W;
+    GridMarginal G;
+    if ((rc = dict_buf.alloc(grid_dict_bytes(c.n_free, n_atoms, c.n_b), st))) return rc;
+    if ((rc = post_buf.alloc(grid_posterior_bytes(c.n_free, n_atoms), st))) return rc;
+    if ((rc = work_buf.alloc(grid_prior_bytes(n_vox, n_atoms, dev->cus), st))) return rc;
+    if ((rc = marg_buf.alloc(grid_marginal_bytes(c.n_free, n_atoms), st))) return rc;
+    const size_t B = (size_t)M.n_bins_total, nv = (size_t)n_vox;
+    const size_t marg_bytes = B * nv * sizeof(double), quant_bytes = (size_t)n_q * c.n_free * nv * sizeof(double), ev_bytes = nv * sizeof(double);
+    double *marg_d = marginal, *quant_d = n_q ? quantile : nullptr, *ev_d = log_evidence;
+    if (mem == PNX_MEM_HOST) {  // both passes read the same signals: one upload, the outputs in one buffer, as the EM call stages
+        const size_t y_bytes = nv * c.n_b * sizeof(double);
+        const size_t r256 = 255, o_marg = 0, o_quant = (marg_bytes + r256) & ~r256, o_ev = o_quant + ((quant_bytes + r256) & ~r256);
+        if (y_buf.alloc(y_bytes, st) != PNX_OK || out_buf.alloc(o_ev + ev_bytes, st) != PNX_OK)
+            return set_error(PNX_ERR_NOMEM, "grid marginals: no device memory for the %zu bytes of y and the %zu bytes of the outputs "
+                                            "(%lld voxels x %d b-values, %zu bins): call with fewer voxels at a time", y_bytes, o_ev + ev_bytes,
+                             (long long)n_vox, c.n_b, B);
+        if ((rc = pnx_upload(y_buf.p, y, (int64_t)y_bytes, device, st, 0))) return rc;
+        y = (const double *)y_buf.p;
+        marg_d = (double *)((char *)out_buf.p + o_marg);
+        quant_d = n_q ? (double *)((char *)out_buf.p + o_quant) : nullptr;
+        ev_d = log_evidence ? (double *)((char *)out_buf.p + o_ev) : nullptr;
+    }
+    if ((rc = grid_dict_build(&c, b, n_atoms, atoms, fixed, lo, hi, H.s0_row, dict_buf.p, &D, st))) return rc;
+    if ((rc = grid_posterior_prepare(D, H, log_prior, noise_sd, post_buf.p, &P, st))) return rc;
+    if ((rc = grid_marginal_prepare(D, M, bin_of, marg_buf.p, &G, st))) return rc;
+    grid_prior_carve(n_vox, n_atoms, dev->cus, work_buf.p, &W);
+    if ((rc = grid_prior_normalise(D, P, n_vox, y, W, st))) return rc;
+    if ((rc = grid_marginal_device(D, P, G, n_vox, y, W, bin_value, n_q, probs, marg_d, quant_d, ev_d, st))) return rc;
+    if (mem == PNX_MEM_DEVICE) return PNX_OK;
+    if ((rc = pnx_download(marginal, marg_d, (int64_t)marg_bytes, device, st, 0))) return rc;
+    if (quant_d && (rc = pnx_download(quantile, quant_d, (int64_t)quant_bytes, device, st, 0))) return rc;
+    if (ev_d && (rc = pnx_download(log_evidence, ev_d, (int64_t)ev_bytes, device, st, 0))) return rc;
     return PNX_OK;
 }
 

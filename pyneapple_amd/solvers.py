@@ -905,25 +905,35 @@ class HipBayesGridSolver(RefBaseSolver):
             uniform prior, while 37 voxels against 384 atoms fit their own noise and the gain is unreliable or gone (DESIGN.md
             4.1j); where the truths are uniform over the grid's ranges it does not help.  `self.log_prior` stays the caller's
             prior; the learned one is in diagnostics_ only.
+        marginals: None / False (default): nothing more.  True, or a dict {"quantiles": [0.025, 0.5, 0.975]} (TOML: a table
+            [Fitting.solver.marginals]; an unknown key is a ValueError; up to 8 levels inside (0, 1)): `fit` also reports the
+            marginal posterior of every gridded parameter over its grid values and these quantiles of it
+            (pnx_curvefit_grid_marginals_f64; the grid value of the first bin whose cumulative mass reaches the level, not
+            interpolated) -- under the learned table with `empirical_prior`.  A marginal with all its mass on one grid value says
+            that parameter's grid is too coarse; one with two humps says the mean estimates nothing.  At most 128 grid values in
+            all; a projected S0 has none (its value is fitted, not gridded).
     Not built, hence a ValueError: per-pixel fixed parameters (the dictionary would differ from voxel to voxel), io_dtype or
     precision "float32" (the posterior reads and writes float64 arrays and exponentiates in fp64).
     Any other keyword (the reference's solver arguments: method, multi_threading, ...) is accepted and ignored.
     After fit: params_ = the posterior mean keyed by the model's names; diagnostics_ {"posterior_sd", "map" (dicts name ->
     (n_pixels,)), "map_atom", "log_evidence", "ess", "n_pixels"} (no "pcov": the sd is the uncertainty; ess near 1 says the grid
     is too coarse for it), with empirical_prior also {"log_prior" (n_atoms,) the learned table, "prior_loglik" the EM's
-    log-likelihood trace, "prior_n_iter" the updates it ran, "prior_n_voxels" the voxels it learned from}; pixel_results_ with
-    success = the voxel's signal was finite."""
+    log-likelihood trace, "prior_n_iter" the updates it ran, "prior_n_voxels" the voxels it learned from}, with marginals also
+    {"marginal" {name: (n_bins, n_pixels)}, "marginal_values" {name: (n_bins,)}, "quantiles" {name: (n_q, n_pixels)},
+    "quantile_probs"} (a projected S0 is absent from the three dicts); pixel_results_ with success = the voxel's signal was finite."""
 
+    _MARGINALS_DEFAULTS = {"quantiles": (0.025, 0.5, 0.975)}
     _EMPIRICAL_PRIOR_DEFAULTS = {"n_iter": 20, "pseudo_count": 0.0, "rel_tol": 1e-6, "max_voxels": None}
 
     def __init__(self, model: Any, grid=None, max_iter: int = 250, tol: float = 1e-8, p0: dict[str, float] | None = None,
                  bounds: dict[str, tuple[float, float]] | None = None, noise_sd: float | None = None, log_prior=None, project=None,
                  sigma=None, device: int = 0, io_dtype: str = "float64", precision: str = "float64", empirical_prior=None,
-                 **ignored_reference_kwargs):
+                 marginals=None, **ignored_reference_kwargs):
         RefBaseSolver.__init__(self, model=model, max_iter=max_iter, tol=tol, verbose=bool(ignored_reference_kwargs.pop("verbose", False)))
         self._kernel_model = kernel_model_key(model)
         self._kernel_t1 = kernel_t1(model)
         self.empirical_prior = self._empirical_prior_options(empirical_prior)
+        self.marginals = self._marginals_options(marginals)
         if _io_dtype(io_dtype) is not np.float64 or precision != "float64":
             raise ValueError("HipBayesGridSolver is built for precision='float64' and io_dtype='float64': the posterior reads and writes "
                              "float64 arrays and exponentiates in fp64")
@@ -986,6 +996,26 @@ class HipBayesGridSolver(RefBaseSolver):
         return {"n_iter": int(n_iter), "pseudo_count": float(opt["pseudo_count"]), "rel_tol": float(opt["rel_tol"]),
                 "max_voxels": None if mv is None else int(mv)}
 
+    @classmethod
+    def _marginals_options(cls, value):
+        """None when off, else {"quantiles": tuple of levels}, checked."""
+        if value is None or value is False:
+            return None
+        if value is True:
+            value = {}
+        if not isinstance(value, dict):
+            raise ValueError(f"marginals must be None, a bool or a dict of {sorted(cls._MARGINALS_DEFAULTS)}, got {value!r}")
+        unknown = sorted(set(value) - set(cls._MARGINALS_DEFAULTS))
+        if unknown:
+            raise ValueError(f"marginals has unknown keys {unknown}; it takes {sorted(cls._MARGINALS_DEFAULTS)}")
+        try:
+            q = tuple(float(p) for p in np.asarray({**cls._MARGINALS_DEFAULTS, **value}["quantiles"], float).reshape(-1))
+        except (TypeError, ValueError):
+            raise ValueError(f"marginals quantiles must be a sequence of numbers, got {value['quantiles']!r}") from None
+        if len(q) > api.GRID_MARGINAL_MAX_PROBS or not all(0.0 < p < 1.0 for p in q):
+            raise ValueError(f"marginals quantiles must be at most {api.GRID_MARGINAL_MAX_PROBS} levels inside the open interval (0, 1), got {list(q)}")
+        return {"quantiles": q}
+
     def fit(self, xdata: np.ndarray, ydata: np.ndarray, pixel_fixed_params=None, **fit_kwargs) -> "HipBayesGridSolver":
         if pixel_fixed_params:
             raise ValueError("HipBayesGridSolver is not built with per-pixel fixed parameters (pixel_fixed_params): the dictionary "
@@ -1028,6 +1058,13 @@ class HipBayesGridSolver(RefBaseSolver):
         if learned is not None:
             self.diagnostics_.update({"log_prior": learned["log_prior"], "prior_loglik": learned["loglik"], "prior_n_iter": learned["n_iter"],
                                       "prior_n_voxels": learned["n_voxels"]})
+        if self.marginals:
+            mg = api.grid_marginals(self._kernel_model, xdata, ydata, self._atoms, lo, hi, log_prior=log_prior,
+                                    quantiles=self.marginals["quantiles"], **common)
+            self.diagnostics_.update({"marginal": {names[k]: m for k, m in mg["marginal"].items()},
+                                      "marginal_values": {names[k]: v for k, v in mg["values"].items()},
+                                      "quantiles": {names[k]: q for k, q in mg["quantiles"].items()},
+                                      "quantile_probs": mg["quantile_probs"]})
         return self
 
 
