@@ -37,8 +37,9 @@
  *     hand-over), chunk sizes of the host pipelines, trace output (PNX_HOST_TRACE; PNX_LAUNCH_TRACE: one stderr line per
  *     curve-fit launch -- model, free parameters, FD / PV / T1 / STREAM instantiation, n_b, waves per block, LDS bytes, grid --
  *     and per sweep call the kernel it chose: full-tile 16 / 32, generic, or full-tile then generic, the generic kernel with
- *     its block size and copy path) and the test hook PNX_NNLS_TEST_REJECT (forces rejected
- *     candidate columns in the NNLS block kernel) -- is read ONLY when the
+ *     its block size and copy path) and the test hooks PNX_NNLS_TEST_REJECT (forces rejected
+ *     candidate columns in the NNLS block kernel) and PNX_CF_TEAM=0 (the curve fit's drained waves keep their last voxel in
+ *     one lane instead of evaluating its rows as a team: same bits, longer tail) -- is read ONLY when the
  *     process was started with PNX_ENABLE_TEST_HOOKS=1 (looked at once, at the first query); the test-suite and the
  *     profiling scripts set it, bench.py and the plugin never do.
  */

@@ -223,6 +223,7 @@ static int curvefit_device(const pnx_curvefit_opts *o, int64_t n_vox, const doub
         a.stream_spins = sl->spins;
         a.phase = sl->phase;
     }
+    a.team = dev_env_int("PNX_CF_TEAM", 1, 0, 1);  // test hook: 0 keeps a drained wave's last voxel in its one lane (same bits, slower tail)
     a.order = sl ? nullptr : order;  // device-mode calls only (pnx_curvefit_opts::queue_order): a streamed launch completes its granules in index order
     a.y = y_d;
     a.popt = popt_d;

@@ -80,6 +80,8 @@ struct CurvefitArgs {
     int granule_shift;          // granule = 1 << granule_shift voxels
     unsigned int stream_spins;  // watermark polls before a lane gives up (ctl->timed_out = 1)
     int phase;                  // 0: fit + covariance epilogue, 1: fit only, 2: covariance epilogue only
+    int team;                   // 1: a drained wave evaluates its last voxel's rows across its lanes (team mode, see the kernel); 0 only
+                                // through the test hook PNX_CF_TEAM=0, so that one library gives both sides of a bit-for-bit comparison
     long long n_vox;
     int n_b;
     int per_voxel;
@@ -252,6 +254,13 @@ __device__ inline double exp_fast(double x) {
 #endif
 }
 
+// the value lane `src` (wave uniform) holds, in every lane: two v_readlane_b32
+__device__ inline double lane_bcast(double v, int src) {
+    const unsigned long long u = __builtin_bit_cast(unsigned long long, v);
+    const unsigned int lo = __builtin_amdgcn_readlane((int)(unsigned int)u, src), hi = __builtin_amdgcn_readlane((int)(unsigned int)(u >> 32), src);
+    return __builtin_bit_cast(double, ((unsigned long long)hi << 32) | lo);
+}
+
 // ---------------------------------------------------------------------------------------------
 // The kernel.  Block = WAVES wavefronts; LDS: b-values + per-wave signal tile y[row][lane].
 // ---------------------------------------------------------------------------------------------
@@ -368,9 +377,11 @@ __global__ void __launch_bounds__(64 * PNX_CF_BLOCK_WAVES, PNX_CF_WAVES_PER_SIMD
     }
 
 #ifdef PNX_CF_STAMP
-    unsigned long long seg[8] = {0, 0, 0, 0, 0, 0, 0, 0}, act[8] = {0, 0, 0, 0, 0, 0, 0, 0}, cnt[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    unsigned long long seg[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}, act[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}, cnt[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
     unsigned long long tl = __builtin_amdgcn_s_memtime();
-#define CFSTAMP(k) do { __builtin_amdgcn_s_waitcnt(0); const unsigned long long t_ = __builtin_amdgcn_s_memtime(); seg[k] += t_ - tl; tl = t_; } while (0)
+    bool cf_in_team = false;
+// (the stamps inside a team iteration are skipped: the whole iteration is booked under segment 8 behind it)
+#define CFSTAMP(k) do { __builtin_amdgcn_s_waitcnt(0); const unsigned long long t_ = __builtin_amdgcn_s_memtime(); if ((k) == 8 || !cf_in_team) { seg[k] += t_ - tl; tl = t_; } } while (0)
 #define CFACT(k, cond) do { act[k] += __popcll(__ballot(cond)); cnt[k] += 1; } while (0)
 #else
 #define CFSTAMP(k) do {} while (0)
@@ -473,9 +484,10 @@ __global__ void __launch_bounds__(64 * PNX_CF_BLOCK_WAVES, PNX_CF_WAVES_PER_SIMD
         // it, and a wave that never got a voxel does so here.
         if (!__ballot(state != ST_IDLE)) publish(true);
     }
-    for (;;) {
-        CFSTAMP(7);
-        if (state == ST_IDLE) break;
+    // One loop iteration as listed above.  team_c = false: every lane that is in the loop holds a voxel and walks its rows itself.
+    // team_c = true (team mode, below): all 64 lanes are here, lane `owner` holds the wave's last voxel, the others evaluate its rows.
+    auto iterate = [&](auto team_c, const int owner) __attribute__((always_inline)) {
+        constexpr bool TM = decltype(team_c)::value;
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // LDS-DMA signal tiles have landed
         CFSTAMP(0);
         CFACT(1, true);
@@ -485,6 +497,22 @@ __global__ void __launch_bounds__(64 * PNX_CF_BLOCK_WAVES, PNX_CF_WAVES_PER_SIMD
         double Rn[N][N], qn[N], gn[N], cost_new = 0;
         bool finite_f = true, yfinite = true;
         {
+            if constexpr (TM) {
+                // the evaluation point is the owner's: with it in every lane, the lines below give every lane the owner's pe, dxv
+                // and T1 factors.  (A helper is idle for good: its own copies are dead.)
+#pragma unroll
+                for (int k = 0; k < N; ++k) {
+                    xn[k] = lane_bcast(xn[k], owner);
+                    if (PV) {
+                        lb[k] = lane_bcast(lb[k], owner);
+                        ub[k] = lane_bcast(ub[k], owner);
+                    }
+                }
+                if (HASFIXED) {
+#pragma unroll
+                    for (int j = 0; j < NP; ++j) pfull[j] = lane_bcast(pfull[j], owner);
+                }
+            }
             double pe[NP];  // full parameter vector at the evaluation point
             if (HASFIXED) {
 #pragma unroll
@@ -520,7 +548,7 @@ __global__ void __launch_bounds__(64 * PNX_CF_BLOCK_WAVES, PNX_CF_WAVES_PER_SIMD
             double A1 = 1.0, eTM = 1.0, fac = 1.0, dfac = 0.0;
             if (T1) {
                 const bool steam = A.t1_mode == 2;
-                const double T1v = pe[NALL];
+                const double T1v = pe[T1 ? NALL : 0];
                 const double eTR = exp(-A.tr / T1v);
                 A1 = 1 - eTR;
                 eTM = steam ? exp(-A.tm / T1v) : 1.0;
@@ -551,8 +579,89 @@ __global__ void __launch_bounds__(64 * PNX_CF_BLOCK_WAVES, PNX_CF_WAVES_PER_SIMD
             //           and replaced by zeros.  A full block needs none of those selects and reads b and y as 16-byte pairs up
             //           front, which leaves it one basic block up to qr_merge's sig > 0 tests: the scheduler is free to
             //           interleave the exp chains of all its rows and to cover the LDS latency once per block.
-            auto row_block = [&](auto fastgz_c, auto usew_c, auto tail_c, const int i0) __attribute__((always_inline)) {
+            // The body of one row -- exp, model, Jacobian row, FD factor, 1 / sigma -- at row ii (b-value bb, signal yi): the residual
+            // in r0_out, the Jacobian row in jr.  One text for the lane that walks all rows of its own voxel (row_block) and for
+            // the lanes of a team, which take one row each of the owner's voxel (team_rows).
+            auto row_eval = [&](auto fastgz_c, auto usew_c, auto tail_c, const int ii, const double bb, const double yi, double &r0_out,
+                                double (&jr)[N]) __attribute__((always_inline)) {
                 constexpr bool FASTGZ = decltype(fastgz_c)::value, USEW = decltype(usew_c)::value, TAIL = decltype(tail_c)::value;
+                const double nb = -bb;
+                double E[NC];
+#pragma unroll
+                for (int c = 0; c < NC; ++c) E[c] = exp_fast(nb * pe[M::dpos(c)]);
+                const double base = M::signal(pe, E);
+                double r0 = (T1 ? base * A1 * eTM : base) - yi;
+                {
+                    double ja[NP];
+                    M::jac(pe, E, bb, ja);
+                    if (FD) {
+                        // SciPy's 2-point quotient (f(x + dx e_k) - f(x)) / dx in closed form.  The models are
+                        // linear in every parameter except the D_c, and for a D_c
+                        //   f(D_c + dx) - f(D_c) = w_c exp(-b D_c) (exp(-b dx) - 1),
+                        // so the quotient is the analytic column times g(z) = expm1(z)/z, z = -b dx: no second
+                        // exp per column, no cancellation, and SciPy's deterministic O(dx) bias (up to 1e-5
+                        // relative at b = 1200) -- which is what separates its iterates from an
+                        // analytic-Jacobian run -- is kept exactly.
+#pragma unroll
+                        for (int k = 0; k < NALL; ++k) {
+                            if (comp_of_param<MODEL>(k) >= 0) {
+                                const double z = nb * dxv[k];
+                                double gz;
+#if PNX_CF_FAST_EXP
+                                if (FASTGZ || PNX_LIKELY(fabs(z) < 2e-4))  // dx ~ 1.5e-8 max(1, |D|): the normal case; z^4 / 120 < 2e-17
+                                    gz = fma(z, fma(z, fma(z, 1.0 / 24, 1.0 / 6), 0.5), 1.0);
+                                else
+#endif
+                                if (fabs(z) < 1e-3)
+                                    gz = 1.0 + z * (0.5 + z * (1.0 / 6 + z * (1.0 / 24 + z * (1.0 / 120 + z * (1.0 / 720)))));
+                                else
+                                    gz = expm1(z) / z;
+                                ja[k] *= gz;
+                            }
+                        }
+                    }
+                    if (T1) {
+#pragma unroll
+                        for (int k = 0; k < NALL; ++k) ja[k] *= fac;
+                        ja[NP - 1] = base * dfac;
+                    }
+                    if (TAIL ? use_w : USEW) {  // transform * (f - y), transform[:, None] * jac (the 2-point quotient of scaled residuals)
+                        const double t = wsh[ii];
+                        r0 *= t;
+#pragma unroll
+                        for (int k = 0; k < NP; ++k) ja[k] *= t;
+                    }
+                    if (HASFIXED) {
+#pragma unroll
+                        for (int k = 0; k < N; ++k) {
+                            jr[k] = 0;
+#pragma unroll
+                            for (int j = 0; j < NP; ++j)
+                                jr[k] = (A.free_idx[k] == j) ? ja[j] : jr[k];
+                        }
+                    } else {
+#pragma unroll
+                        for (int k = 0; k < N; ++k) jr[k] = ja[k];
+                    }
+                }
+                r0_out = r0;
+            };
+            // What a finished row adds to the pass, in row order: cost, J^T f, and its line of the block that is merged next.
+            auto row_consume = [&](double (&brow)[N + 1], const bool live, const double r0, const double (&jr)[N]) __attribute__((always_inline)) {
+                const double rr = live ? r0 : 0.0;
+                finite_f = finite_f && isfinite(rr);
+                cost_new += rr * rr;
+#pragma unroll
+                for (int k = 0; k < N; ++k) {
+                    const double jk = live ? jr[k] : 0.0;
+                    gn[k] += jk * rr;
+                }
+#pragma unroll
+                for (int k = 0; k < N; ++k) brow[k] = live ? jr[CP(k)] : 0.0;  // factor column k = parameter CP(k)
+                brow[N] = rr;
+            };
+            auto row_block = [&](auto fastgz_c, auto usew_c, auto tail_c, const int i0) __attribute__((always_inline)) {
+                constexpr bool TAIL = decltype(tail_c)::value;
                 double blk[kRowBlk][N + 1];
                 double bv[TAIL ? 1 : kRowBlk], yv[TAIL ? 1 : kRowBlk];
                 if constexpr (!TAIL) {
@@ -571,79 +680,11 @@ __global__ void __launch_bounds__(64 * PNX_CF_BLOCK_WAVES, PNX_CF_WAVES_PER_SIMD
                     const bool live = !TAIL || (i0 + r < n_b);
                     const int ii = live ? i0 + r : 0;
                     const double bb = TAIL ? bsh[ii] : bv[TAIL ? 0 : r];
-                    const double nb = -bb;
                     const double yi = TAIL ? ysh[(ii >> 1) * 2 * kWave + (ii & 1)] : yv[TAIL ? 0 : r];
                     yfinite = yfinite && isfinite(yi);
-                    double E[NC];
-#pragma unroll
-                    for (int c = 0; c < NC; ++c) E[c] = exp_fast(nb * pe[M::dpos(c)]);
-                    const double base = M::signal(pe, E);
-                    double r0 = (T1 ? base * A1 * eTM : base) - yi;
-                    double jr[N];
-                    {
-                        double ja[NP];
-                        M::jac(pe, E, bb, ja);
-                        if (FD) {
-                            // SciPy's 2-point quotient (f(x + dx e_k) - f(x)) / dx in closed form.  The models are
-                            // linear in every parameter except the D_c, and for a D_c
-                            //   f(D_c + dx) - f(D_c) = w_c exp(-b D_c) (exp(-b dx) - 1),
-                            // so the quotient is the analytic column times g(z) = expm1(z)/z, z = -b dx: no second
-                            // exp per column, no cancellation, and SciPy's deterministic O(dx) bias (up to 1e-5
-                            // relative at b = 1200) -- which is what separates its iterates from an
-                            // analytic-Jacobian run -- is kept exactly.
-#pragma unroll
-                            for (int k = 0; k < NALL; ++k) {
-                                if (comp_of_param<MODEL>(k) >= 0) {
-                                    const double z = nb * dxv[k];
-                                    double gz;
-#if PNX_CF_FAST_EXP
-                                    if (FASTGZ || PNX_LIKELY(fabs(z) < 2e-4))  // dx ~ 1.5e-8 max(1, |D|): the normal case; z^4 / 120 < 2e-17
-                                        gz = fma(z, fma(z, fma(z, 1.0 / 24, 1.0 / 6), 0.5), 1.0);
-                                    else
-#endif
-                                    if (fabs(z) < 1e-3)
-                                        gz = 1.0 + z * (0.5 + z * (1.0 / 6 + z * (1.0 / 24 + z * (1.0 / 120 + z * (1.0 / 720)))));
-                                    else
-                                        gz = expm1(z) / z;
-                                    ja[k] *= gz;
-                                }
-                            }
-                        }
-                        if (T1) {
-#pragma unroll
-                            for (int k = 0; k < NALL; ++k) ja[k] *= fac;
-                            ja[NP - 1] = base * dfac;
-                        }
-                        if (TAIL ? use_w : USEW) {  // transform * (f - y), transform[:, None] * jac (the 2-point quotient of scaled residuals)
-                            const double t = wsh[ii];
-                            r0 *= t;
-#pragma unroll
-                            for (int k = 0; k < NP; ++k) ja[k] *= t;
-                        }
-                        if (HASFIXED) {
-#pragma unroll
-                            for (int k = 0; k < N; ++k) {
-                                jr[k] = 0;
-#pragma unroll
-                                for (int j = 0; j < NP; ++j)
-                                    if (A.free_idx[k] == j) jr[k] = ja[j];
-                            }
-                        } else {
-#pragma unroll
-                            for (int k = 0; k < N; ++k) jr[k] = ja[k];
-                        }
-                    }
-                    const double rr = live ? r0 : 0.0;
-                    finite_f = finite_f && isfinite(rr);
-                    cost_new += rr * rr;
-#pragma unroll
-                    for (int k = 0; k < N; ++k) {
-                        const double jk = live ? jr[k] : 0.0;
-                        gn[k] += jk * rr;
-                    }
-#pragma unroll
-                    for (int k = 0; k < N; ++k) blk[r][k] = live ? jr[CP(k)] : 0.0;  // factor column k = parameter CP(k)
-                    blk[r][N] = rr;
+                    double r0, jr[N];
+                    row_eval(fastgz_c, usew_c, tail_c, ii, bb, yi, r0, jr);
+                    row_consume(blk[r], live, r0, jr);
                 }
                 CFSTAMP(1);  // rows of the block: exp, model, Jacobian row, J^T f (diagnostic builds: -DPNX_CF_STAMP)
                 qr_merge<N, kRowBlk>(Rn, qn, blk);
@@ -669,7 +710,55 @@ __global__ void __launch_bounds__(64 * PNX_CF_BLOCK_WAVES, PNX_CF_WAVES_PER_SIMD
                     if (comp_of_param<MODEL>(k) >= 0) in_range = in_range && (fabs(bmax * dxv[k]) < 2e-4);
                 gz_cubic = __ballot(!in_range) == 0;
             }
-            if constexpr (kOneLoop) {
+            if constexpr (TM) {
+                // Team row pass: lane l evaluates rows l and l + 64 of the owner's voxel with the generic row body (per-row FD factor
+                // test, run-time use_w: the bits of the loops the owner would have picked) and leaves [jr | r] in the wave's
+                // signal tile, in the columns of idle lanes (the half of the tile the owner's column is not in).  Then every
+                // lane reads the rows back in index order -- same address in all lanes: a broadcast read -- and accumulates cost,
+                // J^T f and the QR factor exactly as row_block does; the owner's copy is the one that is used.  LDS operations of a
+                // wave execute in order and nothing here waits for another lane or wave: the fences only keep the compiler from
+                // moving the reads over the writes.
+                static_assert(N + 1 <= 8 && 2 * kWave == kMaxB, "a team row is 8 doubles; two rows per lane cover every n_b");
+                double *trow = ytile + (owner < kWave / 2 ? kWave : 0);  // row i: trow[(i >> 1) * 2 * kWave + (i & 1) * 8 + 0 .. N]
+                const double *yown = ytile + 2 * owner;
+                bool ybad = false;
+                __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+#pragma unroll
+                for (int h = 0; h < kMaxB / kWave; ++h) {
+                    if (h * kWave < n_b) {
+                        const int i = lane + h * kWave;
+                        const bool live = i < n_b;
+                        const int ii = live ? i : 0;
+                        const double yi = yown[(ii >> 1) * 2 * kWave + (ii & 1)];
+                        ybad = ybad || !isfinite(yi);
+                        double r0, jr[N];
+                        row_eval(BoolC<false>{}, BoolC<false>{}, BoolC<true>{}, ii, bsh[ii], yi, r0, jr);
+                        if (live) {
+                            double *tr = trow + (i >> 1) * 2 * kWave + (i & 1) * 8;
+#pragma unroll
+                            for (int k = 0; k < N; ++k) tr[k] = jr[k];
+                            tr[N] = r0;
+                        }
+                    }
+                }
+                yfinite = __ballot(ybad) == 0;
+                __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+                __builtin_amdgcn_wave_barrier();
+                for (int i0 = 0; i0 < n_b; i0 += kRowBlk) {
+                    double blk[kRowBlk][N + 1];
+#pragma unroll
+                    for (int r = 0; r < kRowBlk; ++r) {
+                        const bool live = i0 + r < n_b;
+                        const int ii = live ? i0 + r : 0;
+                        const double *tr = trow + (ii >> 1) * 2 * kWave + (ii & 1) * 8;
+                        double jr[N];
+#pragma unroll
+                        for (int k = 0; k < N; ++k) jr[k] = tr[k];
+                        row_consume(blk[r], live, tr[N], jr);
+                    }
+                    qr_merge<N, kRowBlk>(Rn, qn, blk);
+                }
+            } else if constexpr (kOneLoop) {
                 for (int i0 = 0; i0 < n_b; i0 += kRowBlk) row_block(BoolC<false>{}, BoolC<false>{}, BoolC<true>{}, i0);
             } else if (PNX_LIKELY(!use_w && (gz_cubic || !FD))) {
                 if constexpr (FD && PNX_CF_FAST_EXP)
@@ -685,6 +774,9 @@ __global__ void __launch_bounds__(64 * PNX_CF_BLOCK_WAVES, PNX_CF_WAVES_PER_SIMD
         }
 
         CFSTAMP(1);
+        if constexpr (TM) {
+            if (state == ST_IDLE) return;  // helpers: the scalar phases are the owner's
+        }
         // ------------------------------------------------------------------ phase D: accept / reject
         bool accepted = false;
         int final_status = 0;
@@ -815,7 +907,7 @@ __global__ void __launch_bounds__(64 * PNX_CF_BLOCK_WAVES, PNX_CF_WAVES_PER_SIMD
             const bool any_idle = __ballot(state == ST_IDLE) != 0;
             if (state == ST_IDLE) refill();
             if (any_idle) publish(false);
-        } else {
+        } else if constexpr (!TM) {  // (a team only forms behind a dry queue)
             if (state == ST_IDLE) refill();  // claim the next voxel now: its signal streams in behind phases B / C
         }
 
@@ -909,11 +1001,40 @@ __global__ void __launch_bounds__(64 * PNX_CF_BLOCK_WAVES, PNX_CF_WAVES_PER_SIMD
             step_norm = normn<N>(step);
             CFSTAMP(5);
         }
+    };
+    // Team mode (fp64, not streamed, N <= 5; the 6- and 7-parameter instantiations have no register to spare): a lane leaves the loop
+    // only after the queue has run dry, so a wave with kTeamMax lanes left in it is drained -- nothing will refill it -- and its
+    // other lanes wait behind the loop.  Such a wave leaves the loop as a whole and finishes its last voxel in the second loop,
+    // where the fifth of an evaluation that is independent across rows (exp, model, Jacobian row) runs one row per lane instead of
+    // one after the other in a single lane: the wave that everything waits for at the end of a launch gets there sooner.
+    // Every value is computed by the source expression the lone lane would have used, sums run in the same order: bit-identical.
+    constexpr bool kTeam = !STREAM && N <= 5;
+    constexpr int kTeamMax = 1;  // two to four owners served one after the other: not built
+    for (;;) {
+        CFSTAMP(7);
+        if (state == ST_IDLE) break;
+        if constexpr (kTeam) {
+            if (!PNX_LIKELY(__popcll(__ballot(1)) > kTeamMax || !A.team)) break;
+        }
+        iterate(BoolC<false>{}, 0);
+    }
+    if constexpr (kTeam) {
+        // all 64 lanes are back together here; no lane touches the queue or global memory again except the owner's result stores
+#ifdef PNX_CF_STAMP
+        cf_in_team = true;
+#endif
+        for (;;) {
+            const unsigned long long livem = __ballot(state != ST_IDLE);
+            if (!livem) break;
+            iterate(BoolC<true>{}, __ffsll(livem) - 1);
+            CFSTAMP(8);
+            CFACT(8, true);
+        }
     }
 #ifdef PNX_CF_STAMP
     if (threadIdx.x == 0 && blockIdx.x == 3)
-        printf("CFSTAMP refill=%llu pass_rows=%llu pass_qr_merge=%llu D+Blight=%llu final=%llu Bheavy=%llu C=%llu loop=%llu | iters=%llu idle_at_top=%.2f final=%.2f Bheavy=%.2f run=%.2f\n",
-               seg[0], seg[1], seg[6], seg[2], seg[3], seg[4], seg[5], seg[7], cnt[1], (double)act[0] / cnt[0], (double)act[3] / cnt[3],
+        printf("CFSTAMP refill=%llu pass_rows=%llu pass_qr_merge=%llu D+Blight=%llu final=%llu Bheavy=%llu C=%llu loop=%llu team=%llu | iters=%llu team_iters=%llu idle_at_top=%.2f final=%.2f Bheavy=%.2f run=%.2f\n",
+               seg[0], seg[1], seg[6], seg[2], seg[3], seg[4], seg[5], seg[7], seg[8], cnt[1], cnt[8], (double)act[0] / cnt[0], (double)act[3] / cnt[3],
                (double)act[4] / cnt[4], (double)act[5] / cnt[5]);
 #endif
 }
