@@ -592,6 +592,47 @@ PNX_API int pnx_curvefit_varpro_posterior_f64(const pnx_curvefit_opts *opts, int
                                       int32_t *map_atom, double *map_p, double *log_evidence, double *ess, double *clipped_mass,
                                       int mem, int device, void *stream);
 /*
+ * Marginal posterior of every free NON-LINEAR parameter (a rate, a free T1) over the variable-projection dictionary, credible-
+ * interval quantiles and a geometric posterior mean from it.  The arguments up to marginal_amplitudes, the
+ * weighting, the dictionary, the amplitude solve, the clip rule, c_g(v), tol_v, l_g and every refusal are
+ * pnx_curvefit_varpro_posterior_f64's.  The atoms sit on a grid: along a non-linear free parameter k every atom holds one of
+ * n_bins[k] values.
+ *   n_bins (n_free,) int32 host: the number of distinct grid values of each free parameter; 0: no marginal for that parameter.
+ *     n_bins[k] must be 0 for every linear row (a fraction, S0): its value belongs to the voxel-atom pair, not to the atom, and an
+ *     indicator that depends on the voxel is not a matrix product.  B = sum n_bins must lie in [1, 128];
+ *   bin_of (n_free, n_atoms) int32 host: the bin of atom g along parameter k, in [0, n_bins[k]); rows with n_bins[k] == 0 are
+ *     not read;
+ *   bin_value (B,) host: the grid value of every bin, parameter k's at offset off_k = sum_{i<k} n_bins[i], strictly ascending within
+ *     a parameter; every atom must satisfy nl_atoms[row_k, g] == bin_value[off_k + bin_of[k, g]] exactly (row_k: the row of
+ *     nl_atoms that holds free parameter k);
+ *   n_q in [0, 8], probs (n_q,) host, each in the open interval (0, 1).
+ * Every violation is PNX_ERR_INVALID (PNX_ERR_UNSUPPORTED where the posterior says so) with a message that names the first
+ * offender, before any device work.
+ * Per finite voxel v, in fp64:  L = log sum_g exp(l_g);  W_g = exp(l_g - L), exactly 0 for a padded or excluded atom;
+ *   marginal[off_k + j, v] = sum over the atoms with bin_of[k, g] == j of W_g      (not renormalised afterwards)
+ *   cdf_j = the running sum of marginal over j in bin order;  quantile[i, k, v] = bin_value of the first bin with
+ *     cdf_j >= probs[i], of the last bin of k when none reaches it (no interpolation), NaN for a parameter with n_bins[k] == 0;
+ *   geo_mean[k, v] = exp(sum_j marginal_j log bin_value_j / sum_j marginal_j): the posterior mean of log(parameter k), the natural
+ *     point estimate on a log-spaced axis; NaN for a parameter with n_bins[k] == 0 or with a bin value <= 0;
+ *   log_evidence = L - log sum_g exp(log_prior_g), the posterior's within its rounding bound.
+ * A voxel with a non-finite (weighted) signal, or without an admissible atom, gets NaN in every output; its neighbours are not
+ * affected.
+ *   marginal (B, n_vox) bin-major, not NULL; quantile (n_q, n_free, n_vox), NULL only when n_q == 0; geo_mean (n_free, n_vox) or
+ *   NULL; log_evidence (n_vox) or NULL: out, host|device as `mem`.
+ * One pass over the products Phi^T y: the weights are formed about a running maximum of l_g per voxel (the sums are rescaled when
+ * it moves) and summed per bin by a 0/1 indicator matrix on the matrix cores; the (n_vox, n_atoms) matrix W never reaches memory.
+ * No sum uses an atomic and every sum of a voxel depends on the order of the atoms only: results are bit-identical between two
+ * calls, between PNX_MEM_HOST and PNX_MEM_DEVICE, and whatever the number of voxels in the call.
+ *   PNX_MEM_DEVICE only enqueues.  PNX_MEM_HOST: y is uploaded once (pnx_upload's path) and the outputs come back from one
+ *   stream-ordered buffer (pnx_download's path), as pnx_curvefit_grid_marginals_f64 stages them -- no chunk ring; PNX_ERR_NOMEM
+ *   names the sizes.
+ */
+PNX_API int pnx_curvefit_varpro_marginals_f64(const pnx_curvefit_opts *opts, int64_t n_vox, const double *b, const double *y, int n_atoms,
+                                      const double *nl_atoms, const double *fixed, const double *lo, const double *hi,
+                                      const double *log_prior, double noise_sd, int marginal_amplitudes, const int32_t *n_bins,
+                                      const int32_t *bin_of, const double *bin_value, int n_q, const double *probs, double *marginal,
+                                      double *quantile, double *geo_mean, double *log_evidence, int mem, int device, void *stream);
+/*
  * Log-linear mono-exponential fit, ln S = ln S0 - b D by (weighted) linear least squares per voxel: the ADC
  * map, step 1 of a segmented IVIM fit, a cheap source of S0 / D start values.  A closed form over one pass of the data: a voxel
  * costs its signal row in and its results out.  Per voxel, in fp64, in the order written:

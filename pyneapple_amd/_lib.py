@@ -29,7 +29,7 @@ ABI_SYMBOLS = [
     "pnx_nnls_fit_stats_f64", "pnx_nnls_solve_peaks_stats_f64", "pnx_curvefit_predict_f64", "pnx_curvefit_fast_f32",
     "pnx_curvefit_simplex_f64", "pnx_ideal_bounds_simplex_f64", "pnx_curvefit_grid_start_f64",
     "pnx_curvefit_grid_posterior_f64", "pnx_curvefit_grid_prior_em_f64", "pnx_curvefit_varpro_f64", "pnx_curvefit_varpro_posterior_f64",
-    "pnx_curvefit_grid_marginals_f64",
+    "pnx_curvefit_grid_marginals_f64", "pnx_curvefit_varpro_marginals_f64",
     "pnx_loglinear_f64", "pnx_loglinear_f32", "pnx_peel_f64", "pnx_peel_f32",
 ]
 
@@ -139,6 +139,10 @@ def load():
     lib.pnx_curvefit_varpro_posterior_f64.restype = C.c_int
     lib.pnx_curvefit_varpro_posterior_f64.argtypes = [C.POINTER(CurvefitOpts), C.c_int64, dp, dp, C.c_int, dp, dp, dp, dp, dp, C.c_double, C.c_int,
                                                       dp, dp, vp, dp, dp, dp, dp, C.c_int, C.c_int, vp]
+    # the posterior's inputs, n_bins, bin_of, bin_value, n_q, probs, marginal, quantile, geo_mean, log_evidence
+    lib.pnx_curvefit_varpro_marginals_f64.restype = C.c_int
+    lib.pnx_curvefit_varpro_marginals_f64.argtypes = [C.POINTER(CurvefitOpts), C.c_int64, dp, dp, C.c_int, dp, dp, dp, dp, dp, C.c_double, C.c_int,
+                                                      vp, vp, dp, C.c_int, dp, dp, dp, dp, dp, C.c_int, C.c_int, vp]
     lib.pnx_loglinear_f64.restype = C.c_int  # n_vox, n_b, b, use, weighting, n_reweight, clip, lo, hi, y, params, pcov, status, n_used, ss_res
     lib.pnx_loglinear_f64.argtypes = [C.c_int64, C.c_int, dp, vp, C.c_int, C.c_int, C.c_int, dp, dp, dp, dp, dp, vp, vp, dp,
                                       C.c_int, C.c_int, vp]

@@ -685,6 +685,99 @@ def varpro_posterior_device(opts, n_vox, b, y, nl_atoms, fixed, lo, hi, log_prio
                                                    int(device), stream))
 
 
+def _varpro_marginal_bins(o, model, nl_atoms, bins):
+    """(n_bins, bin_of, bin_value) of `varpro_marginals` over ALL free parameters, as contiguous arrays of the ABI's types.  bins:
+    None -- `grid_marginal_bins(nl_atoms)`, one entry per row of nl_atoms, spread over the free parameters (a fraction or S0 holds
+    n_bins = 0 and a row of zeros in bin_of) -- or the caller's (n_bins (n_free,), bin_of (n_free, n_atoms), bin_value)."""
+    n, G = o.n_free, nl_atoms.shape[1]
+    if bins is None:
+        lin = {MODEL_PARAM_NAMES[model].index(name) for name in varpro_linear_names(model)}
+        rows = [k for k in range(n) if o.free_idx[k] not in lin]  # free parameter of every row of nl_atoms
+        nb, of, bin_value = grid_marginal_bins(nl_atoms)
+        n_bins, bin_of = np.zeros(n, np.int32), np.zeros((n, G), np.int32)
+        n_bins[rows], bin_of[rows] = nb, of
+        bins = (n_bins, bin_of, bin_value)
+    n_bins, bin_of, bin_value = bins
+    n_bins = np.ascontiguousarray(n_bins, np.int32)
+    bin_of = np.ascontiguousarray(bin_of, np.int32)
+    bin_value = np.ascontiguousarray(bin_value, np.float64)
+    if n_bins.shape != (n,) or bin_of.shape != (n, G) or (n_bins < 0).any() or bin_value.shape != (int(n_bins.sum()),):
+        raise ValueError(f"bins must be (n_bins ({n},) >= 0, bin_of ({n}, {G}), bin_value (sum n_bins,))")
+    return n_bins, bin_of, bin_value
+
+
+def _varpro_marginal_result(n_bins, bin_value, probs, marginal, quantile, geo_mean, log_evidence):
+    res = _marginal_result(None, n_bins, bin_value, probs, marginal, quantile, log_evidence)
+    res["geo_mean"] = {k: geo_mean[k] for k in range(len(n_bins)) if n_bins[k]}
+    return res
+
+
+def varpro_marginals(model, b, y, nl_atoms, lo, hi, *, log_prior=None, noise_sd=0.0, marginal_amplitudes=True, bins=None,
+                     quantiles=(0.025, 0.5, 0.975), fixed_idx=(), fixed_vals=None, sigma=None, t1_mode=0, tr=0., tm=0., device=0):
+    """Marginal posterior of every free rate (and a free T1) over a variable-projection dictionary on host (numpy) arrays, quantiles
+    and a geometric posterior mean from it (pnx_curvefit_varpro_marginals_f64; method: include/pnx.h).  The arguments of
+    `varpro_posterior`, and
+    bins: None -- derived from the atoms by `grid_marginal_bins(nl_atoms)` (np.unique per row; a fraction or S0 has no marginal: its
+        value belongs to the voxel-atom pair) -- or (n_bins (n_free,), bin_of (n_free, n_atoms), bin_value (sum n_bins,)) as the
+        ABI takes them, n_bins = 0 for every fraction and S0; at most 128 bins in all;
+    quantiles: up to 8 levels in the open interval (0, 1), or () / None for none.
+    Returns the dict of `grid_marginals` -- marginal {k: (n_bins_k, n_vox)}, values {k: (n_bins_k,)}, quantiles {k: (n_q, n_vox)},
+    keyed by the position k of the parameter among the free ones, quantile_probs, log_evidence (n_vox,) -- plus geo_mean
+    {k: (n_vox,)}: exp of the posterior mean of log(parameter k), NaN where a grid value is <= 0.  A voxel with a non-finite signal
+    holds NaN everywhere."""
+    _lib.require_device()
+    b = np.ascontiguousarray(b, np.float64)
+    y = np.ascontiguousarray(np.atleast_2d(y), np.float64)
+    n_vox, n_b = y.shape
+    if b.shape != (n_b,):
+        raise ValueError(f"b has shape {b.shape}, expected ({n_b},)")
+    o, nl_atoms, lo, hi, _, fv = _varpro_args(model, n_b, nl_atoms, lo, hi, lo, fixed_idx, fixed_vals, sigma, t1_mode, tr, tm)
+    lp = _posterior_log_prior(log_prior, nl_atoms.shape[1])
+    n = o.n_free
+    n_bins, bin_of, bin_value = _varpro_marginal_bins(o, model, nl_atoms, bins)
+    probs = _marginal_probs(quantiles)
+    marginal = np.empty((int(n_bins.sum()), n_vox), np.float64)
+    quantile = np.empty((probs.size, n, n_vox), np.float64)
+    geo_mean = np.empty((n, n_vox), np.float64)
+    log_evidence = np.empty(n_vox, np.float64)
+    check(load().pnx_curvefit_varpro_marginals_f64(C.byref(o), n_vox, ptr(b), ptr(y), int(nl_atoms.shape[1]), ptr(nl_atoms), ptr(fv), ptr(lo),
+                                                   ptr(hi), ptr(lp), float(noise_sd), int(bool(marginal_amplitudes)), ptr(n_bins), ptr(bin_of),
+                                                   ptr(bin_value), int(probs.size), ptr(probs) if probs.size else None, ptr(marginal),
+                                                   ptr(quantile) if probs.size else None, ptr(geo_mean), ptr(log_evidence), MEM_HOST,
+                                                   int(device), None))
+    return _varpro_marginal_result(n_bins, bin_value, probs, marginal, quantile, geo_mean, log_evidence)
+
+
+def varpro_marginals_device(opts, n_vox, b, y, nl_atoms, fixed, lo, hi, log_prior, noise_sd, marginal_amplitudes, n_bins, bin_of, bin_value,
+                            probs, marginal, quantile, geo_mean, log_evidence, device, stream=None):
+    """Enqueue the marginals on HBM-resident float64 torch tensors (asynchronous; caller synchronises): y (n_vox, n_b), marginal
+    (sum n_bins, n_vox), quantile (n_q, n_free, n_vox) or None when probs is empty, geo_mean (n_free, n_vox) or None, log_evidence
+    (n_vox,) or None on the device; b, nl_atoms (n_nonlinear_free, n_atoms), shared fixed values, lo, hi, log_prior (n_atoms,) or
+    None, the binning over all free parameters (n_bins (n_free,), bin_of (n_free, n_atoms), bin_value) and probs are host arrays.
+    `opts` from make_opts.  Returns the dict of `varpro_marginals` over views of the caller's tensors."""
+    b, nl_atoms, lo, hi = (np.ascontiguousarray(a, np.float64) for a in (b, nl_atoms, lo, hi))
+    if fixed is not None:
+        fixed = np.ascontiguousarray(fixed, np.float64)
+    if nl_atoms.ndim != 2:
+        raise ValueError("nl_atoms must have shape (n_nonlinear_free, n_atoms)")
+    lp = _posterior_log_prior(log_prior, nl_atoms.shape[1])
+    n_bins = np.ascontiguousarray(n_bins, np.int32)
+    bin_of = np.ascontiguousarray(bin_of, np.int32)
+    bin_value = np.ascontiguousarray(bin_value, np.float64)
+    probs = _marginal_probs(probs)
+    n = opts.n_free
+    if n_bins.shape != (n,) or bin_of.shape != (n, nl_atoms.shape[1]) or (n_bins < 0).any() or bin_value.shape != (int(n_bins.sum()),):
+        raise ValueError(f"the binning must be n_bins ({n},) >= 0, bin_of ({n}, {nl_atoms.shape[1]}), bin_value (sum n_bins,)")
+    check(load().pnx_curvefit_varpro_marginals_f64(C.byref(opts), int(n_vox), ptr(b), ptr(y), int(nl_atoms.shape[1]), ptr(nl_atoms), ptr(fixed),
+                                                   ptr(lo), ptr(hi), ptr(lp), float(noise_sd), int(bool(marginal_amplitudes)), ptr(n_bins),
+                                                   ptr(bin_of), ptr(bin_value), int(probs.size), ptr(probs) if probs.size else None,
+                                                   ptr(marginal), ptr(quantile) if probs.size else None, ptr(geo_mean), ptr(log_evidence),
+                                                   MEM_DEVICE, int(device), stream))
+    if geo_mean is None:
+        geo_mean = {k: None for k in range(n)}
+    return _varpro_marginal_result(n_bins, bin_value, probs, marginal, quantile if probs.size else None, geo_mean, log_evidence)
+
+
 LOGLINEAR_WEIGHTING = {"none": 0, "signal2": 1}  # w = 1 / w = y^2 (include/pnx.h)
 LOGLINEAR_MAX_REWEIGHT = 8  # kLogLinMaxReweight of csrc/pnx_loglin_args.hpp
 

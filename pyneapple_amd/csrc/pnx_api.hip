@@ -31,6 +31,7 @@
 #include "pnx_predict.hpp"
 #include "pnx_simplex.hpp"
 #include "pnx_varpro.hpp"
+#include "pnx_varpro_marginal.hpp"
 #include "pnx_varpro_posterior.hpp"
 
 namespace pnx {
@@ -1495,6 +1496,69 @@ int pnx_curvefit_varpro_posterior_f64(const pnx_curvefit_opts *o, int64_t n_vox,
         return varpro_posterior_device(D, P, (int64_t)n, S.d(VQ_Y), S.d(VQ_MEAN), S.d(VQ_SD), (int32_t *)S.dev[VQ_ATOM], S.d(VQ_MAPP),
                                        S.d(VQ_LOGEV), S.d(VQ_ESS), S.d(VQ_CM), dev->cus, s);
     });
+}
+
+// ---- per-parameter marginals of the posterior over the variable-projection dictionary (kernels: pnx_varpro_marginal.hip and the
+// posterior's preparation, argument checks: pnx_varpro_marginal_args.hpp)
+int pnx_curvefit_varpro_marginals_f64(const pnx_curvefit_opts *o, int64_t n_vox, const double *b, const double *y, int n_atoms,
+                                      const double *nl_atoms, const double *fixed, const double *lo, const double *hi, const double *log_prior,
+                                      double noise_sd, int marginal_amplitudes, const int32_t *n_bins, const int32_t *bin_of,
+                                      const double *bin_value, int n_q, const double *probs, double *marginal, double *quantile,
+                                      double *geo_mean, double *log_evidence, int mem, int device, void *stream) {
+    if (!o) return set_error(PNX_ERR_INVALID, "opts is NULL");
+    pnx_curvefit_opts c = *o;  // as grid start: jac_mode and the tolerances are not looked at
+    c.jac_mode = PNX_JAC_ANALYTIC;
+    c.ftol = c.xtol = c.gtol = 0.0;
+    int rc = check_curvefit_opts(&c);
+    if (rc) return rc;
+    VarproLayout L;
+    VarproPosteriorHost H;
+    GridMarginalHost M;
+    if ((rc = varpro_marginal_check_args(&c, n_vox, b, y, n_atoms, nl_atoms, fixed, lo, hi, log_prior, noise_sd, marginal_amplitudes, n_bins,
+                                         bin_of, bin_value, n_q, probs, marginal, quantile, mem, &L, &H, &M)))
+        return rc;
+    if (n_vox == 0) return PNX_OK;
+    DeviceInfo *dev;
+    if ((rc = use_device(device, &dev))) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    AsyncBuf dict_buf, post_buf, marg_buf, lv_buf, y_buf, out_buf;  // stream-ordered, freed behind the work that reads them
+    VarproDict D;
+    VarproPosterior P;
+    VarproMarginal G;
+    const size_t B = (size_t)M.n_bins_total, nv = (size_t)n_vox;
+    if ((rc = dict_buf.alloc(varpro_dict_bytes(c.n_free, L.n_nl, L.k, n_atoms, c.n_b), st))) return rc;
+    if ((rc = post_buf.alloc(varpro_posterior_bytes(L.n_nl, n_atoms), st))) return rc;
+    if ((rc = marg_buf.alloc(varpro_marginal_bytes(c.n_free, n_atoms), st))) return rc;
+    if ((rc = lv_buf.alloc(nv * sizeof(double), st))) return rc;
+    const size_t marg_bytes = B * nv * sizeof(double), quant_bytes = (size_t)n_q * c.n_free * nv * sizeof(double);
+    const size_t geo_bytes = (size_t)c.n_free * nv * sizeof(double), ev_bytes = nv * sizeof(double);
+    double *marg_d = marginal, *quant_d = n_q ? quantile : nullptr, *geo_d = geo_mean, *ev_d = log_evidence;
+    if (mem == PNX_MEM_HOST) {  // one upload of the signals, the outputs in one buffer, as pnx_curvefit_grid_marginals_f64 stages them
+        const size_t y_bytes = nv * c.n_b * sizeof(double);
+        const size_t r256 = 255, o_quant = (marg_bytes + r256) & ~r256, o_geo = o_quant + ((quant_bytes + r256) & ~r256);
+        const size_t o_ev = o_geo + ((geo_bytes + r256) & ~r256);
+        if (y_buf.alloc(y_bytes, st) != PNX_OK || out_buf.alloc(o_ev + ev_bytes, st) != PNX_OK)
+            return set_error(PNX_ERR_NOMEM, "varpro marginals: no device memory for the %zu bytes of y and the %zu bytes of the outputs "
+                                            "(%lld voxels x %d b-values, %zu bins): call with fewer voxels at a time", y_bytes, o_ev + ev_bytes,
+                             (long long)n_vox, c.n_b, B);
+        if ((rc = pnx_upload(y_buf.p, y, (int64_t)y_bytes, device, st, 0))) return rc;
+        y = (const double *)y_buf.p;
+        marg_d = (double *)out_buf.p;
+        quant_d = n_q ? (double *)((char *)out_buf.p + o_quant) : nullptr;
+        geo_d = geo_mean ? (double *)((char *)out_buf.p + o_geo) : nullptr;
+        ev_d = log_evidence ? (double *)((char *)out_buf.p + o_ev) : nullptr;
+    }
+    if ((rc = varpro_dict_build(&c, L, b, n_atoms, nl_atoms, fixed, lo, dict_buf.p, &D, st))) return rc;  // no fallback: lo is not read back
+    if ((rc = varpro_posterior_prepare(D, H, log_prior, noise_sd, marginal_amplitudes, post_buf.p, &P, st))) return rc;
+    if ((rc = varpro_marginal_prepare(D, M, bin_of, marg_buf.p, &G, st))) return rc;
+    if ((rc = varpro_marginal_device(D, P, G, n_vox, y, bin_value, n_q, probs, marg_d, (double *)lv_buf.p, quant_d, geo_d, ev_d, dev->cus, st)))
+        return rc;
+    if (mem == PNX_MEM_DEVICE) return PNX_OK;
+    if ((rc = pnx_download(marginal, marg_d, (int64_t)marg_bytes, device, st, 0))) return rc;
+    if (quant_d && (rc = pnx_download(quantile, quant_d, (int64_t)quant_bytes, device, st, 0))) return rc;
+    if (geo_d && (rc = pnx_download(geo_mean, geo_d, (int64_t)geo_bytes, device, st, 0))) return rc;
+    if (ev_d && (rc = pnx_download(log_evidence, ev_d, (int64_t)ev_bytes, device, st, 0))) return rc;
+    return PNX_OK;
 }
 
 int pnx_loglinear_f64(int64_t n_vox, int n_b, const double *b_host, const uint8_t *use_host, int weighting, int n_reweight, int clip,

@@ -21,6 +21,7 @@
 #include <cstring>
 
 #include "pnx_internal.hpp"
+#include "pnx_varpro_pair.hpp"
 #include "pnx_varpro_posterior.hpp"
 
 namespace pnx {
@@ -34,9 +35,6 @@ using f64x4 = __attribute__((ext_vector_type(4))) double;
     } while (0)
 
 static size_t up256(size_t n) { return (n + 255) & ~(size_t)255; }
-
-// packed index of the symmetric (i, j), as pnx_varpro.hip stores M
-__host__ __device__ constexpr int vpk(int i, int j) { return i >= j ? i * (i + 1) / 2 + j : j * (j + 1) / 2 + i; }
 
 // ---- per-atom inputs --------------------------------------------------------------------------------------------------------
 struct VpPrepArgs {
@@ -210,78 +208,8 @@ struct VpPostArgs {
     double lp_norm;
 };
 
-// The variable projection's amplitude solve and clip rule for one voxel-atom pair (pnx_varpro.hip varpro_match_kernel, the same
-// arithmetic in the same order): c = Phi^T y, M packed, I what the solve reads.  ap: the clipped amplitudes a'; q: the reported
-// linear parameters of the pair (f_j = a'_j / S kept inside the box for the S0 class); returns cost - 0.5 ||y||^2.
-// OPEN: this, and sym_logdet with the prep kernel's difference system above, are hand copies of expressions inside
-// varpro_match_kernel, spd_inverse and varpro_finish_kernel, made because this unit was not to touch pnx_varpro.hip.  That the
-// a_hat = 0 atoms of the variable projection are exactly the lw = -inf atoms here rests on the copies staying equal: whoever edits
-// either side edits both, until one device helper in a shared header serves the two units.
-template <int K, int CLS>
-__device__ inline double vp_solve(const double *c, const double *M, const double *I, const double *lo, const double *hi, double *q, bool *clipped) {
-    double ap[K];
-    bool clip = false;
-    if constexpr (CLS == kVarproReduced) {
-        constexpr int NN = (K - 1) * K / 2;
-        double tt[K], rest = 1.0;
-#pragma unroll
-        for (int i = 0; i < K - 1; ++i) tt[i] = (c[i] - c[K - 1]) - I[NN + i];
-#pragma unroll
-        for (int i = 0; i < K - 1; ++i) {
-            double ah = 0.0;
-#pragma unroll
-            for (int j = 0; j < K - 1; ++j) ah = fma(I[vpk(i, j)], tt[j], ah);
-            ap[i] = fmin(fmax(ah, lo[i]), hi[i]);
-            clip |= ap[i] != ah;
-            q[i] = ap[i];
-            rest -= ap[i];
-        }
-        ap[K - 1] = rest;
-        q[K - 1] = 0.0;
-    } else {
-        double ah[K], sum = 0.0;
-#pragma unroll
-        for (int i = 0; i < K; ++i) {
-            ah[i] = 0.0;
-#pragma unroll
-            for (int j = 0; j < K; ++j) ah[i] = fma(I[vpk(i, j)], c[j], ah[i]);
-            sum += ah[i];
-        }
-        if constexpr (CLS == kVarproFree) {
-#pragma unroll
-            for (int i = 0; i < K; ++i) {
-                ap[i] = fmin(fmax(ah[i], lo[i]), hi[i]);
-                clip |= ap[i] != ah[i];
-                q[i] = ap[i];
-            }
-        } else {  // S0 class: the amplitude sum first, the fraction bounds scale with it
-            const double S = fmin(fmax(sum, lo[K - 1]), hi[K - 1]);
-            clip |= S != sum;
-            double rest = S;
-#pragma unroll
-            for (int i = 0; i < K - 1; ++i) {
-                ap[i] = fmin(fmax(ah[i], lo[i] * S), hi[i] * S);
-                clip |= ap[i] != ah[i];
-                // f_j = a'_j / S; the quotient of a'_j = hi_fj S may round one ulp past hi_fj: kept inside the box
-                q[i] = S > 0.0 ? fmin(fmax(ap[i] / S, lo[i]), hi[i]) : lo[i];
-                rest -= ap[i];
-            }
-            ap[K - 1] = rest;
-            q[K - 1] = S;
-        }
-    }
-    double cc = 0.0;  // 0.5 a'^T M a' - c . a'
-#pragma unroll
-    for (int i = 0; i < K; ++i) {
-        double ma = 0.0;
-#pragma unroll
-        for (int j = 0; j < K; ++j) ma = fma(M[vpk(i, j)], ap[j], ma);
-        cc = fma(ap[i], fma(0.5, ma, -c[i]), cc);
-    }
-    *clipped = clip;
-    return cc;
-}
-
+// The amplitude solve and clip rule of one voxel-atom pair, vp_solve, is pnx_varpro_pair.hpp's: the marginals' kernel
+// (pnx_varpro_marginal.hip) weighs a pair by the same function.
 template <int NS, int K, int CLS>
 __global__ void __launch_bounds__(kVpPostWaves * 64) varpro_posterior_kernel(const VpPostArgs a) {
     constexpr int NM = K * (K + 1) / 2;

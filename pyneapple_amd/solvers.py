@@ -1186,17 +1186,28 @@ class HipBayesVarProSolver(RefBaseSolver):
     understatement.
     Not built, hence a ValueError: per-pixel fixed parameters (the dictionary would differ from voxel to voxel), io_dtype or
     precision "float32".  Any other keyword (the reference's solver arguments: method, multi_threading, ...) is accepted and ignored.
+        marginals: None / False (default): nothing more.  True, or a dict {"quantiles": [0.025, 0.5, 0.975]} (TOML: a table
+            [Fitting.solver.marginals]; HipBayesGridSolver's option, the same rules and messages): `fit` also reports the marginal
+            posterior of every free rate (and a free T1) over its grid values, these quantiles of it (the grid value of the first
+            bin whose cumulative mass reaches the level, not interpolated) and the geometric posterior mean exp E[log D]
+            (pnx_curvefit_varpro_marginals_f64) -- on a log-spaced rate axis the estimate the arithmetic mean drags upward.  At
+            most 128 grid values in all; a fraction or S0 has none (its value is solved per voxel and atom, not gridded).
     After fit: params_ = the posterior mean keyed by the model's names; diagnostics_ {"posterior_sd", "map" (dicts name ->
-    (n_pixels,)), "map_atom", "log_evidence", "ess", "clipped_mass", "n_pixels"}; pixel_results_ with success = the voxel's signal
-    was finite."""
+    (n_pixels,)), "map_atom", "log_evidence", "ess", "clipped_mass", "n_pixels"}, with marginals also {"marginal" {name: (n_bins,
+    n_pixels)}, "marginal_values" {name: (n_bins,)}, "quantiles" {name: (n_q, n_pixels)}, "quantile_probs", "geo_mean" {name:
+    (n_pixels,)}} (the rates and a free T1 only); pixel_results_ with success = the voxel's signal was finite."""
+
+    _MARGINALS_DEFAULTS = HipBayesGridSolver._MARGINALS_DEFAULTS
+    _marginals_options = classmethod(HipBayesGridSolver._marginals_options.__func__)  # one set of rules and messages
 
     def __init__(self, model: Any, rates=None, max_iter: int = 250, tol: float = 1e-8, p0: dict[str, float] | None = None,
                  bounds: dict[str, tuple[float, float]] | None = None, ordered: bool = True, noise_sd: float | None = None, log_prior=None,
                  marginal_amplitudes: bool = True, sigma=None, device: int = 0, io_dtype: str = "float64", precision: str = "float64",
-                 **ignored_reference_kwargs):
+                 marginals=None, **ignored_reference_kwargs):
         RefBaseSolver.__init__(self, model=model, max_iter=max_iter, tol=tol, verbose=bool(ignored_reference_kwargs.pop("verbose", False)))
         self._kernel_model = kernel_model_key(model)
         self._kernel_t1 = kernel_t1(model)
+        self.marginals = self._marginals_options(marginals)
         if _io_dtype(io_dtype) is not np.float64 or precision != "float64":
             raise ValueError("HipBayesVarProSolver is built for precision='float64' and io_dtype='float64': the posterior reads and "
                              "writes float64 arrays and exponentiates in fp64")
@@ -1266,6 +1277,15 @@ class HipBayesVarProSolver(RefBaseSolver):
                              "map": {n: res["map_p"][i] for i, n in enumerate(names)}, "map_atom": atom,
                              "log_evidence": res["log_evidence"], "ess": res["ess"], "clipped_mass": res["clipped_mass"],
                              "n_pixels": n_pixels}
+        if self.marginals:
+            mg = api.varpro_marginals(self._kernel_model, xdata, ydata, self._nl_atoms, lo, hi, log_prior=self.log_prior, noise_sd=self.noise_sd,
+                                      marginal_amplitudes=self.marginal_amplitudes, quantiles=self.marginals["quantiles"], fixed_idx=fixed_idx,
+                                      fixed_vals=fixed_vals, sigma=self.sigma, device=self.device, **self._kernel_t1)
+            self.diagnostics_.update({"marginal": {names[k]: m for k, m in mg["marginal"].items()},
+                                      "marginal_values": {names[k]: v for k, v in mg["values"].items()},
+                                      "quantiles": {names[k]: q for k, q in mg["quantiles"].items()},
+                                      "quantile_probs": mg["quantile_probs"],
+                                      "geo_mean": {names[k]: g for k, g in mg["geo_mean"].items()}})
         return self
 
 
