@@ -633,6 +633,40 @@ PNX_API int pnx_curvefit_varpro_marginals_f64(const pnx_curvefit_opts *opts, int
                                       const int32_t *bin_of, const double *bin_value, int n_q, const double *probs, double *marginal,
                                       double *quantile, double *geo_mean, double *log_evidence, int mem, int device, void *stream);
 /*
+ * The prior of pnx_curvefit_varpro_posterior_f64 learned from the volume itself (empirical Bayes): the
+ * non-parametric maximum-likelihood mixture over the rate dictionary, by EM.  The arguments up to marginal_amplitudes, the
+ * weighting, the dictionary, the amplitude solve, the clip rule, c_g(v), tol_v and every refusal are
+ * pnx_curvefit_varpro_posterior_f64's; the range rules and messages of n_iter, pseudo_count, rel_tol and log_prior_out, the
+ * normalisation of the start, loglik, the stopping rule, the NaN tail, n_eff and the synchronisation are
+ * pnx_curvefit_grid_prior_em_f64's.  Every refusal comes before any device work.  In fp64:
+ *   Likelihood.  The Occam term belongs to the likelihood, not to the learned table:
+ *     occ_g = marginal_amplitudes ? -0.5 log det N_g : 0;   lw_g = log pi_g + occ_g;   l_g(v) is the posterior's with this lw_g.
+ *   Admissible atoms.  An atom is admissible when its start log_prior is finite and occ_g is finite (a non-finite occ_g marks the
+ *     variable projection's a_hat = 0 atoms under marginal_amplitudes).  n_adm counts them.  A non-admissible atom has weight
+ *     exactly 0 and log_prior_out = -inf, always.
+ *   Voxels that take part.  A voxel takes part when its weighted signal is finite and at least one atom has a finite l.  n_eff
+ *     counts them.  The others change nothing: their neighbours are bit-identical to a run without them.
+ *   Update.  L_v = log sum_g exp l_g(v);  W_vg = exp(l_g(v) - L_v);  S_g = sum_v W_vg over the voxels that take part;
+ *     pi_g <- (S_g + pseudo_count) / (n_eff + pseudo_count n_adm);  log_prior_g <- log pi_g, -inf where pi_g == 0.
+ *   Memory and reproducibility.  The (n_vox, n_atoms) matrix W never reaches memory.  No sum uses an atomic.  Every sum has one
+ *     order for a given launch grid.  Two calls return the same bytes, PNX_MEM_HOST or PNX_MEM_DEVICE.
+ * The start is normalised over its finite entries, log_prior - log sum exp(log_prior), before occ_g is known: loglik[0] is the
+ * log-likelihood under that start with the inadmissible atoms at weight 0; from the first update on every reported prior sums to
+ * 1 over the admissible atoms, so the sum of log_evidence of a later posterior call under log_prior_out is loglik[done].
+ *   log_prior_out (n_atoms,) host, not NULL; loglik (n_iter + 1,) host or NULL; n_iter_done, n_eff: host or NULL.
+ *   Without a voxel that takes part the call returns PNX_OK with the start (n_vox == 0: the normalised start), done = 0 and
+ *   loglik[0] = 0.
+ *   y (n_vox, n_b) host|device as `mem`.  PNX_MEM_DEVICE: read in place.  PNX_MEM_HOST: uploaded once into a stream-ordered buffer
+ *   that stays for all passes -- no chunk ring; PNX_ERR_NOMEM names the size and points to a sub-sample.  For both `mem` values
+ *   the call SYNCHRONISES `stream` before it returns (once per update, for 16 bytes, and at the end).
+ * An update is two passes that both pay the K x K amplitude solve of every voxel-atom pair (the measured price).
+ */
+PNX_API int pnx_curvefit_varpro_prior_em_f64(const pnx_curvefit_opts *opts, int64_t n_vox, const double *b, const double *y, int n_atoms,
+                                     const double *nl_atoms, const double *fixed, const double *lo, const double *hi,
+                                     const double *log_prior, double noise_sd, int marginal_amplitudes, int n_iter,
+                                     double pseudo_count, double rel_tol, double *log_prior_out, double *loglik, int *n_iter_done,
+                                     int64_t *n_eff, int mem, int device, void *stream);
+/*
  * Log-linear mono-exponential fit, ln S = ln S0 - b D by (weighted) linear least squares per voxel: the ADC
  * map, step 1 of a segmented IVIM fit, a cheap source of S0 / D start values.  A closed form over one pass of the data: a voxel
  * costs its signal row in and its results out.  Per voxel, in fp64, in the order written:

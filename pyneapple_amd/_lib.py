@@ -29,7 +29,7 @@ ABI_SYMBOLS = [
     "pnx_nnls_fit_stats_f64", "pnx_nnls_solve_peaks_stats_f64", "pnx_curvefit_predict_f64", "pnx_curvefit_fast_f32",
     "pnx_curvefit_simplex_f64", "pnx_ideal_bounds_simplex_f64", "pnx_curvefit_grid_start_f64",
     "pnx_curvefit_grid_posterior_f64", "pnx_curvefit_grid_prior_em_f64", "pnx_curvefit_varpro_f64", "pnx_curvefit_varpro_posterior_f64",
-    "pnx_curvefit_grid_marginals_f64", "pnx_curvefit_varpro_marginals_f64",
+    "pnx_curvefit_grid_marginals_f64", "pnx_curvefit_varpro_marginals_f64", "pnx_curvefit_varpro_prior_em_f64",
     "pnx_loglinear_f64", "pnx_loglinear_f32", "pnx_peel_f64", "pnx_peel_f32",
 ]
 
@@ -139,6 +139,11 @@ def load():
     lib.pnx_curvefit_varpro_posterior_f64.restype = C.c_int
     lib.pnx_curvefit_varpro_posterior_f64.argtypes = [C.POINTER(CurvefitOpts), C.c_int64, dp, dp, C.c_int, dp, dp, dp, dp, dp, C.c_double, C.c_int,
                                                       dp, dp, vp, dp, dp, dp, dp, C.c_int, C.c_int, vp]
+    # the varpro posterior's inputs, n_iter, pseudo_count, rel_tol, log_prior_out, loglik, n_iter_done, n_eff
+    lib.pnx_curvefit_varpro_prior_em_f64.restype = C.c_int
+    lib.pnx_curvefit_varpro_prior_em_f64.argtypes = [C.POINTER(CurvefitOpts), C.c_int64, dp, dp, C.c_int, dp, dp, dp, dp, dp, C.c_double, C.c_int,
+                                                     C.c_int, C.c_double, C.c_double, dp, dp, C.POINTER(C.c_int), C.POINTER(C.c_int64),
+                                                     C.c_int, C.c_int, vp]
     # the posterior's inputs, n_bins, bin_of, bin_value, n_q, probs, marginal, quantile, geo_mean, log_evidence
     lib.pnx_curvefit_varpro_marginals_f64.restype = C.c_int
     lib.pnx_curvefit_varpro_marginals_f64.argtypes = [C.POINTER(CurvefitOpts), C.c_int64, dp, dp, C.c_int, dp, dp, dp, dp, dp, C.c_double, C.c_int,

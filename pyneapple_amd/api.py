@@ -685,6 +685,68 @@ def varpro_posterior_device(opts, n_vox, b, y, nl_atoms, fixed, lo, hi, log_prio
                                                    int(device), stream))
 
 
+def varpro_prior_slab_atoms(n_b, k):
+    """Atoms per LDS slab of the two EM passes over the variable-projection dictionary (varpro_prior_slab of
+    csrc/pnx_varpro_prior_args.hpp): the variable projection's rule with 5 more values per atom -- the log-weight and the four
+    wave-private rows of the accumulate pass, which take the place of the posterior's k + 1 centred non-linear values.  Equal to
+    `varpro_posterior_slab_atoms` at three compartments, at most as wide below (80 against 96 at two compartments and 32 b-values)."""
+    kpad, k, width = (int(n_b) + 3) & ~3, int(k), 16
+    for w in range(16, 257, 16):
+        if k * kpad * (w if w & 16 else w + 16) + (k * (k + 1) + 5) * w <= 8192:
+            width = w
+    return width
+
+
+def _varpro_prior_em_call(o, n_vox, b, y, nl_atoms, fv, lo, hi, lp, noise_sd, marginal_amplitudes, n_iter, pseudo_count, rel_tol, mem, device,
+                          stream):
+    n_iter = int(n_iter)
+    out = np.empty(nl_atoms.shape[1], np.float64)
+    loglik = np.full(min(max(n_iter, 0), 1000) + 1, np.nan)  # outside 1..1000 the library refuses before it writes
+    done, n_eff = C.c_int(0), C.c_int64(0)
+    check(load().pnx_curvefit_varpro_prior_em_f64(C.byref(o), int(n_vox), ptr(b), ptr(y), int(nl_atoms.shape[1]), ptr(nl_atoms), ptr(fv), ptr(lo),
+                                                  ptr(hi), ptr(lp), float(noise_sd), int(bool(marginal_amplitudes)), n_iter,
+                                                  float(pseudo_count), float(rel_tol), ptr(out), ptr(loglik), C.byref(done), C.byref(n_eff),
+                                                  mem, int(device), stream))
+    return dict(log_prior=out, loglik=loglik, n_iter=int(done.value), n_eff=int(n_eff.value))
+
+
+def varpro_prior_em(model, b, y, nl_atoms, lo, hi, *, log_prior=None, noise_sd=0.0, marginal_amplitudes=True, n_iter=20, pseudo_count=0.0,
+                    rel_tol=1e-6, fixed_idx=(), fixed_vals=None, sigma=None, t1_mode=0, tr=0., tm=0., device=0):
+    """The prior of `varpro_posterior` learned from the voxels themselves on host (numpy) arrays (pnx_curvefit_varpro_prior_em_f64;
+    method: include/pnx.h): the maximum-likelihood mixture over the rate atoms by EM, pi_g <- mean over the voxels that take part
+    of their posterior weight on atom g.  The Occam term of `marginal_amplitudes` belongs to the likelihood, not to the learned
+    table.  The arguments of `varpro_posterior` (log_prior is the start: None is uniform, an atom at -inf stays excluded, as does
+    an atom the variable projection cannot solve under marginal_amplitudes), and n_iter, pseudo_count, rel_tol as `grid_prior_em`
+    takes them.  Returns `grid_prior_em`'s dict: log_prior (n_atoms,) -- ready for `varpro_posterior(..., log_prior=...)` --,
+    loglik (n_iter + 1,), NaN past n_iter, n_iter the updates done, n_eff the voxels that took part.  The prior needs many voxels:
+    a few dozen over-fit."""
+    _lib.require_device()
+    b = np.ascontiguousarray(b, np.float64)
+    y = np.ascontiguousarray(np.atleast_2d(y), np.float64)
+    n_vox, n_b = y.shape
+    if b.shape != (n_b,):
+        raise ValueError(f"b has shape {b.shape}, expected ({n_b},)")
+    o, nl_atoms, lo, hi, _, fv = _varpro_args(model, n_b, nl_atoms, lo, hi, lo, fixed_idx, fixed_vals, sigma, t1_mode, tr, tm)
+    lp = _posterior_log_prior(log_prior, nl_atoms.shape[1])
+    return _varpro_prior_em_call(o, n_vox, b, y, nl_atoms, fv, lo, hi, lp, noise_sd, marginal_amplitudes, n_iter, pseudo_count, rel_tol, MEM_HOST,
+                                 device, None)
+
+
+def varpro_prior_em_device(opts, n_vox, b, y, nl_atoms, fixed, lo, hi, log_prior, noise_sd, marginal_amplitudes, n_iter, pseudo_count, rel_tol,
+                           device, stream=None):
+    """`varpro_prior_em` on an HBM-resident float64 torch tensor y (n_vox, n_b), read in place; b, nl_atoms (n_nonlinear_free,
+    n_atoms), shared fixed values, lo, hi and log_prior (n_atoms,) or None are host arrays, `opts` from make_opts.  The results are
+    small host arrays, so unlike `varpro_posterior_device` the call synchronises `stream` before it returns the same dict."""
+    b, nl_atoms, lo, hi = (np.ascontiguousarray(a, np.float64) for a in (b, nl_atoms, lo, hi))
+    if fixed is not None:
+        fixed = np.ascontiguousarray(fixed, np.float64)
+    if nl_atoms.ndim != 2:
+        raise ValueError("nl_atoms must have shape (n_nonlinear_free, n_atoms)")
+    lp = _posterior_log_prior(log_prior, nl_atoms.shape[1])
+    return _varpro_prior_em_call(opts, n_vox, b, y, nl_atoms, fixed, lo, hi, lp, noise_sd, marginal_amplitudes, n_iter, pseudo_count, rel_tol,
+                                 MEM_DEVICE, device, stream)
+
+
 def _varpro_marginal_bins(o, model, nl_atoms, bins):
     """(n_bins, bin_of, bin_value) of `varpro_marginals` over ALL free parameters, as contiguous arrays of the ABI's types.  bins:
     None -- `grid_marginal_bins(nl_atoms)`, one entry per row of nl_atoms, spread over the free parameters (a fraction or S0 holds

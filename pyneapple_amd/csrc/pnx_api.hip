@@ -33,6 +33,7 @@
 #include "pnx_varpro.hpp"
 #include "pnx_varpro_marginal.hpp"
 #include "pnx_varpro_posterior.hpp"
+#include "pnx_varpro_prior.hpp"
 
 namespace pnx {
 
@@ -1558,6 +1559,73 @@ int pnx_curvefit_varpro_marginals_f64(const pnx_curvefit_opts *o, int64_t n_vox,
     if (quant_d && (rc = pnx_download(quantile, quant_d, (int64_t)quant_bytes, device, st, 0))) return rc;
     if (geo_d && (rc = pnx_download(geo_mean, geo_d, (int64_t)geo_bytes, device, st, 0))) return rc;
     if (ev_d && (rc = pnx_download(log_evidence, ev_d, (int64_t)ev_bytes, device, st, 0))) return rc;
+    return PNX_OK;
+}
+
+// ---- the prior over the variable-projection dictionary learned from the volume (kernels: pnx_varpro_prior.hip and the posterior's
+// preparation, argument checks: pnx_varpro_prior_args.hpp; the host loop is pnx_curvefit_grid_prior_em_f64's)
+int pnx_curvefit_varpro_prior_em_f64(const pnx_curvefit_opts *o, int64_t n_vox, const double *b, const double *y, int n_atoms,
+                                     const double *nl_atoms, const double *fixed, const double *lo, const double *hi, const double *log_prior,
+                                     double noise_sd, int marginal_amplitudes, int n_iter, double pseudo_count, double rel_tol,
+                                     double *log_prior_out, double *loglik, int *n_iter_done, int64_t *n_eff, int mem, int device,
+                                     void *stream) {
+    if (!o) return set_error(PNX_ERR_INVALID, "opts is NULL");
+    pnx_curvefit_opts c = *o;  // as grid start: jac_mode and the tolerances are not looked at
+    c.jac_mode = PNX_JAC_ANALYTIC;
+    c.ftol = c.xtol = c.gtol = 0.0;
+    int rc = check_curvefit_opts(&c);
+    if (rc) return rc;
+    VarproLayout L;
+    VarproPosteriorHost H;
+    if ((rc = varpro_prior_check_args(&c, n_vox, b, y, n_atoms, nl_atoms, fixed, lo, hi, log_prior, noise_sd, marginal_amplitudes, n_iter,
+                                      pseudo_count, rel_tol, log_prior_out, mem, &L, &H)))
+        return rc;
+    grid_prior_start(n_atoms, log_prior, H.log_prior_norm, log_prior_out);  // the start, normalised; n_adm needs occ: on the device
+    if (loglik) loglik[0] = 0.0;
+    if (n_vox == 0) {
+        grid_prior_report(n_iter, 0, 0, loglik, n_iter_done, n_eff);
+        return PNX_OK;
+    }
+    DeviceInfo *dev;
+    if ((rc = use_device(device, &dev))) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    AsyncBuf dict_buf, post_buf, work_buf, y_buf;  // stream-ordered, freed behind the work that reads them
+    VarproDict D;
+    VarproPosterior P;
+    VarproPriorWork W;
+    if ((rc = dict_buf.alloc(varpro_dict_bytes(c.n_free, L.n_nl, L.k, n_atoms, c.n_b), st))) return rc;
+    if ((rc = post_buf.alloc(varpro_posterior_bytes(L.n_nl, n_atoms), st))) return rc;
+    if ((rc = work_buf.alloc(varpro_prior_bytes(n_vox, n_atoms, dev->cus), st))) return rc;
+    if (mem == PNX_MEM_HOST) {  // every pass of every iteration reads the same signals: one upload, kept for the call
+        const size_t bytes = (size_t)n_vox * c.n_b * sizeof(double);
+        if (y_buf.alloc(bytes, st) != PNX_OK)
+            return set_error(PNX_ERR_NOMEM, "varpro prior: no device memory for the %zu bytes of y (%lld voxels x %d), which stay resident for "
+                                            "all iterations: learn the prior from a sub-sample of the voxels", bytes, (long long)n_vox, c.n_b);
+        if ((rc = pnx_upload(y_buf.p, y, (int64_t)bytes, device, st, 0))) return rc;
+        y = (const double *)y_buf.p;
+    }
+    if ((rc = varpro_dict_build(&c, L, b, n_atoms, nl_atoms, fixed, lo, dict_buf.p, &D, st))) return rc;  // no fallback: lo is not read back
+    // without a prior the posterior's lw is the Occam term alone (0 with the profile weight): computed once per call
+    if ((rc = varpro_posterior_prepare(D, H, nullptr, noise_sd, marginal_amplitudes, post_buf.p, &P, st))) return rc;
+    varpro_prior_carve(n_vox, n_atoms, dev->cus, work_buf.p, &W);
+    if ((rc = varpro_prior_begin(D, P, log_prior_out, W, st))) return rc;
+    std::vector<double> trace((size_t)n_iter + 1, 0.0);
+    VarproPriorStats stats = {0.0, 0};
+    int done = 0;
+    for (int t = 0;; ++t) {  // trace[t]: the log-likelihood under the prior before update t, the returned prior's at t = done
+        if ((rc = varpro_prior_normalise(D, P, n_vox, y, W, st))) return rc;
+        PNX_HIP(hipMemcpyAsync(&stats, W.stats, sizeof(stats), hipMemcpyDeviceToHost, st));
+        PNX_HIP(hipStreamSynchronize(st));
+        trace[t] = stats.loglik;
+        done = t;
+        if (stats.n_finite == 0 || t == n_iter || grid_prior_converged(trace.data(), t, rel_tol)) break;
+        if ((rc = varpro_prior_update(D, P, n_vox, y, W, pseudo_count, st))) return rc;
+    }
+    PNX_HIP(hipMemcpyAsync(log_prior_out, W.lp, (size_t)n_atoms * sizeof(double), hipMemcpyDeviceToHost, st));
+    PNX_HIP(hipStreamSynchronize(st));
+    if (loglik)
+        for (int t = 0; t <= done; ++t) loglik[t] = trace[t];
+    grid_prior_report(n_iter, done, stats.n_finite, loglik, n_iter_done, n_eff);
     return PNX_OK;
 }
 

@@ -13,18 +13,25 @@ namespace pnx {
 
 constexpr int kGridPriorMaxIter = 1000;
 
-// The four arguments of the EM first (each refusal names its argument), then grid_posterior_check_args with log_prior_out in
+// The four arguments of an EM over a dictionary, each refusal naming its argument; `who` opens the message ("grid prior",
+// "varpro prior": pnx_varpro_prior_args.hpp applies the same rules).
+inline int prior_em_check_args(const char *who, int n_iter, double pseudo_count, double rel_tol, const double *log_prior_out) {
+    if (!log_prior_out) return set_error(PNX_ERR_INVALID, "%s: log_prior_out is NULL (the one output that is not optional)", who);
+    if (n_iter < 1 || n_iter > kGridPriorMaxIter)
+        return set_error(PNX_ERR_INVALID, "%s: n_iter=%d out of range [1,%d]", who, n_iter, kGridPriorMaxIter);
+    if (!(pseudo_count >= 0.0) || std::isinf(pseudo_count))
+        return set_error(PNX_ERR_INVALID, "%s: pseudo_count=%g must be finite and >= 0", who, pseudo_count);
+    if (!(rel_tol >= 0.0) || std::isinf(rel_tol)) return set_error(PNX_ERR_INVALID, "%s: rel_tol=%g must be finite and >= 0", who, rel_tol);
+    return PNX_OK;
+}
+
+// The four arguments of the EM first (prior_em_check_args), then grid_posterior_check_args with log_prior_out in
 // the place of `mean`: the posterior's refusals, weighting and prior rules hold unchanged.  H->log_prior_norm normalises the start.
 inline int grid_prior_check_args(const pnx_curvefit_opts *o, int64_t n_vox, const double *b, const double *y, int n_atoms,
                                  const double *atoms, const double *fixed, const double *lo, const double *hi, int project_amplitude,
                                  const double *log_prior, double noise_sd, int n_iter, double pseudo_count, double rel_tol,
                                  const double *log_prior_out, int mem, GridPosteriorHost *H) {
-    if (!log_prior_out) return set_error(PNX_ERR_INVALID, "grid prior: log_prior_out is NULL (the one output that is not optional)");
-    if (n_iter < 1 || n_iter > kGridPriorMaxIter)
-        return set_error(PNX_ERR_INVALID, "grid prior: n_iter=%d out of range [1,%d]", n_iter, kGridPriorMaxIter);
-    if (!(pseudo_count >= 0.0) || std::isinf(pseudo_count))
-        return set_error(PNX_ERR_INVALID, "grid prior: pseudo_count=%g must be finite and >= 0", pseudo_count);
-    if (!(rel_tol >= 0.0) || std::isinf(rel_tol)) return set_error(PNX_ERR_INVALID, "grid prior: rel_tol=%g must be finite and >= 0", rel_tol);
+    if (int rc = prior_em_check_args("grid prior", n_iter, pseudo_count, rel_tol, log_prior_out)) return rc;
     return grid_posterior_check_args(o, n_vox, b, y, n_atoms, atoms, fixed, lo, hi, project_amplitude, log_prior, noise_sd, log_prior_out, mem, H);
 }
 

@@ -1192,21 +1192,31 @@ class HipBayesVarProSolver(RefBaseSolver):
             bin whose cumulative mass reaches the level, not interpolated) and the geometric posterior mean exp E[log D]
             (pnx_curvefit_varpro_marginals_f64) -- on a log-spaced rate axis the estimate the arithmetic mean drags upward.  At
             most 128 grid values in all; a fraction or S0 has none (its value is solved per voxel and atom, not gridded).
+        empirical_prior: None / False (default): the posterior under `log_prior`, as before.  True, or a dict with any of
+            {"n_iter": 20, "pseudo_count": 0.0, "rel_tol": 1e-6, "max_voxels": None} (TOML: a table [Fitting.solver.empirical_prior];
+            HipBayesGridSolver's option, the same rules and messages): `fit` first learns the prior over the rate atoms from the
+            volume by EM (pnx_curvefit_varpro_prior_em_f64; `log_prior` is its start, the Occam term of `marginal_amplitudes` stays
+            in the likelihood) on ydata[::ceil(n / max_voxels)], then reports the posterior -- and the marginals -- under the
+            learned table.  It needs many voxels: a few dozen over-fit.
     After fit: params_ = the posterior mean keyed by the model's names; diagnostics_ {"posterior_sd", "map" (dicts name ->
     (n_pixels,)), "map_atom", "log_evidence", "ess", "clipped_mass", "n_pixels"}, with marginals also {"marginal" {name: (n_bins,
     n_pixels)}, "marginal_values" {name: (n_bins,)}, "quantiles" {name: (n_q, n_pixels)}, "quantile_probs", "geo_mean" {name:
-    (n_pixels,)}} (the rates and a free T1 only); pixel_results_ with success = the voxel's signal was finite."""
+    (n_pixels,)}} (the rates and a free T1 only), with empirical_prior also {"log_prior" (n_atoms,) the learned table, "prior_loglik"
+    the EM's log-likelihood trace, "prior_n_iter", "prior_n_voxels"}; pixel_results_ with success = the voxel's signal was finite."""
 
     _MARGINALS_DEFAULTS = HipBayesGridSolver._MARGINALS_DEFAULTS
     _marginals_options = classmethod(HipBayesGridSolver._marginals_options.__func__)  # one set of rules and messages
+    _EMPIRICAL_PRIOR_DEFAULTS = HipBayesGridSolver._EMPIRICAL_PRIOR_DEFAULTS
+    _empirical_prior_options = classmethod(HipBayesGridSolver._empirical_prior_options.__func__)  # likewise
 
     def __init__(self, model: Any, rates=None, max_iter: int = 250, tol: float = 1e-8, p0: dict[str, float] | None = None,
                  bounds: dict[str, tuple[float, float]] | None = None, ordered: bool = True, noise_sd: float | None = None, log_prior=None,
                  marginal_amplitudes: bool = True, sigma=None, device: int = 0, io_dtype: str = "float64", precision: str = "float64",
-                 marginals=None, **ignored_reference_kwargs):
+                 marginals=None, empirical_prior=None, **ignored_reference_kwargs):
         RefBaseSolver.__init__(self, model=model, max_iter=max_iter, tol=tol, verbose=bool(ignored_reference_kwargs.pop("verbose", False)))
         self._kernel_model = kernel_model_key(model)
         self._kernel_t1 = kernel_t1(model)
+        self.empirical_prior = self._empirical_prior_options(empirical_prior)
         self.marginals = self._marginals_options(marginals)
         if _io_dtype(io_dtype) is not np.float64 or precision != "float64":
             raise ValueError("HipBayesVarProSolver is built for precision='float64' and io_dtype='float64': the posterior reads and "
@@ -1266,7 +1276,18 @@ class HipBayesVarProSolver(RefBaseSolver):
         fixed_vals = np.array([float(fixed[all_names[i]]) for i in fixed_idx]) if fixed_idx else None
         lo = np.array([self.bounds[n][0] for n in names], float)
         hi = np.array([self.bounds[n][1] for n in names], float)
-        res = api.varpro_posterior(self._kernel_model, xdata, ydata, self._nl_atoms, lo, hi, log_prior=self.log_prior, noise_sd=self.noise_sd,
+        log_prior, learned = self.log_prior, None
+        if self.empirical_prior:
+            ep = self.empirical_prior
+            step = 1 if ep["max_voxels"] is None else -(-n_pixels // ep["max_voxels"])
+            sample = ydata[::step]
+            learned = api.varpro_prior_em(self._kernel_model, xdata, sample, self._nl_atoms, lo, hi, log_prior=self.log_prior,
+                                          noise_sd=self.noise_sd, marginal_amplitudes=self.marginal_amplitudes, n_iter=ep["n_iter"],
+                                          pseudo_count=ep["pseudo_count"], rel_tol=ep["rel_tol"], fixed_idx=fixed_idx, fixed_vals=fixed_vals,
+                                          sigma=self.sigma, device=self.device, **self._kernel_t1)
+            learned["n_voxels"] = sample.shape[0]
+            log_prior = learned["log_prior"]
+        res = api.varpro_posterior(self._kernel_model, xdata, ydata, self._nl_atoms, lo, hi, log_prior=log_prior, noise_sd=self.noise_sd,
                                    marginal_amplitudes=self.marginal_amplitudes, fixed_idx=fixed_idx, fixed_vals=fixed_vals, sigma=self.sigma,
                                    device=self.device, **self._kernel_t1)
         mean, atom = res["mean"], res["map_atom"]
@@ -1277,8 +1298,11 @@ class HipBayesVarProSolver(RefBaseSolver):
                              "map": {n: res["map_p"][i] for i, n in enumerate(names)}, "map_atom": atom,
                              "log_evidence": res["log_evidence"], "ess": res["ess"], "clipped_mass": res["clipped_mass"],
                              "n_pixels": n_pixels}
+        if learned is not None:
+            self.diagnostics_.update({"log_prior": learned["log_prior"], "prior_loglik": learned["loglik"], "prior_n_iter": learned["n_iter"],
+                                      "prior_n_voxels": learned["n_voxels"]})
         if self.marginals:
-            mg = api.varpro_marginals(self._kernel_model, xdata, ydata, self._nl_atoms, lo, hi, log_prior=self.log_prior, noise_sd=self.noise_sd,
+            mg = api.varpro_marginals(self._kernel_model, xdata, ydata, self._nl_atoms, lo, hi, log_prior=log_prior, noise_sd=self.noise_sd,
                                       marginal_amplitudes=self.marginal_amplitudes, quantiles=self.marginals["quantiles"], fixed_idx=fixed_idx,
                                       fixed_vals=fixed_vals, sigma=self.sigma, device=self.device, **self._kernel_t1)
             self.diagnostics_.update({"marginal": {names[k]: m for k, m in mg["marginal"].items()},
