@@ -473,6 +473,60 @@ PNX_API int pnx_curvefit_grid_prior_em_f64(const pnx_curvefit_opts *opts, int64_
                                    double rel_tol, double *log_prior_out, double *loglik, int *n_iter_done, int64_t *n_eff, int mem,
                                    int device, void *stream);
 /*
+ * pnx_curvefit_grid_posterior_f64 with one prior row per segmentation label.  Every argument of that call, its
+ * weighting, refusals and outputs, and
+ *   n_classes in [1, 16] (PNX_ERR_INVALID otherwise);
+ *   labels (n_vox,) int32, host|device as `mem`: the row of the table voxel v is judged under;
+ *   log_prior (n_classes, n_atoms) row-major, host, or NULL (every row uniform): every entry finite or -inf; rows may exclude
+ *     different atoms; every row needs at least one finite entry -- otherwise PNX_ERR_INVALID with a message that names the row,
+ *     before any device work.
+ * Per voxel v, with c = labels[v]:
+ *   l_g(v) = log_prior[c, g] - ...           everything right of the prior term is pnx_curvefit_grid_posterior_f64's, term for term;
+ *   log_evidence_v = L_v - log sum_g exp(log_prior[c, g]);  a pair whose table entry is -inf has weight exactly 0.
+ * Labels may live on the device and are not validated on the host: a voxel whose label lies outside [0, n_classes) is treated
+ * exactly as a voxel with a non-finite signal -- NaN in every floating output, map_atom = -1 -- and its neighbours are
+ * bit-identical to a run without it.  This is how a caller marks background (label -1).
+ * Every sum of a voxel depends on the order of the atoms only: a voxel's outputs are the bytes pnx_curvefit_grid_posterior_f64
+ * returns for it under log_prior[c, :] whenever the rows admit the same atoms (the moments are accumulated about the mid-range of
+ * the atoms that ANY row admits; with rows that exclude different atoms mean and sd agree within the posterior's rounding bound
+ * taken over that range).  With n_classes == 1 and every label 0 the call returns the unlabelled call's bytes.
+ * PNX_MEM_DEVICE only enqueues; PNX_MEM_HOST goes through the chunk ring, the labels beside the signals.
+ */
+PNX_API int pnx_curvefit_grid_posterior_classes_f64(const pnx_curvefit_opts *opts, int64_t n_vox, const double *b, const double *y,
+                                    int n_atoms, const double *atoms, const double *fixed, const double *lo, const double *hi,
+                                    int project_amplitude, int n_classes, const int32_t *labels, const double *log_prior,
+                                    double noise_sd, double *mean, double *sd, int32_t *map_atom, double *map_p, double *log_evidence,
+                                    double *ess, int mem, int device, void *stream);
+/*
+ * pnx_curvefit_grid_prior_em_f64 with one prior row per segmentation label, all rows learned in one pass pair over the volume
+ * (DESIGN.md 4.1n).  n_classes, labels and log_prior (n_classes, n_atoms) as pnx_curvefit_grid_posterior_classes_f64 takes
+ * them, with its l_g, its refusals and its rule for a label outside [0, n_classes): such a voxel takes no part.  Every row of the
+ * start is normalised first.  One update, per class c:
+ *   S_cg = sum of W_vg over the voxels of class c that take part (finite signal, label in range);
+ *   pi_cg <- (S_cg + pseudo_count) / (n_eff_c + pseudo_count n_adm_c)      n_adm_c: the finite entries of row c of the start
+ * and log_prior[c, g] <- log pi_cg; an entry that started at -inf stays there; a class without a voxel that takes part keeps its
+ * normalised start row.
+ *   log_prior_out (n_classes, n_atoms) host, not NULL;
+ *   loglik (n_iter + 1,) host or NULL: the sum over the classes, in class order, of
+ *   loglik_class (n_iter + 1, n_classes) host or NULL: per class the sum of L_v over its voxels that take part, under the table
+ *     before update t; entries past `done` are NaN in both;
+ *   n_iter_done: `done`; the stopping rule is pnx_curvefit_grid_prior_em_f64's, applied to loglik (the sum);
+ *   n_eff (n_classes,) int64 host or NULL: per class the voxels that take part.  Without any the call returns PNX_OK with the
+ *     normalised start, done = 0 and loglik[0] = 0.
+ * No floating-point atomics; every sum has one order for a given launch grid: two calls return the same bytes, PNX_MEM_HOST or
+ * PNX_MEM_DEVICE; the (n_vox, n_atoms) matrix W never reaches memory.  With n_classes == 1 and every label 0 the call returns the
+ * bytes of pnx_curvefit_grid_prior_em_f64.  The accumulate pass separates the classes that meet in a strip of 16 voxels in a
+ * loop over the classes present there: a label map sorted by class pays for one class per strip (DESIGN.md 4.1n has the cost).
+ *   y, labels host|device as `mem`; PNX_MEM_HOST uploads both once for all iterations (no chunk ring; PNX_ERR_NOMEM names the
+ *   size).  For both `mem` values the call SYNCHRONISES `stream` before it returns.
+ */
+PNX_API int pnx_curvefit_grid_prior_em_classes_f64(const pnx_curvefit_opts *opts, int64_t n_vox, const double *b, const double *y,
+                                   int n_atoms, const double *atoms, const double *fixed, const double *lo, const double *hi,
+                                   int project_amplitude, int n_classes, const int32_t *labels, const double *log_prior,
+                                   double noise_sd, int n_iter, double pseudo_count, double rel_tol, double *log_prior_out,
+                                   double *loglik, double *loglik_class, int *n_iter_done, int64_t *n_eff, int mem, int device,
+                                   void *stream);
+/*
  * Marginal posterior of every free parameter over the dictionary, and credible-interval quantiles from it.  The
  * arguments up to noise_sd, the weighting, the dictionary, a_g(v), c_g(v), tol_v, l_g and every refusal are
  * pnx_curvefit_grid_posterior_f64's.  The atoms sit on a grid: along free parameter k every atom holds one of n_bins[k] values.

@@ -38,6 +38,8 @@ SOURCE_GROUPS = {
     "grid_posterior": ["pnx_grid_posterior.hip", "pnx_grid_posterior.hpp", "pnx_grid_posterior_args.hpp", "pnx_grid.hpp", "pnx_grid_args.hpp"],
     "grid_prior": ["pnx_grid_prior.hip", "pnx_grid_prior.hpp", "pnx_grid_prior_args.hpp", "pnx_grid_posterior.hpp",
                    "pnx_grid_posterior_args.hpp", "pnx_grid.hpp", "pnx_grid_args.hpp"],
+    "grid_class": ["pnx_grid_class.hip", "pnx_grid_class.hpp", "pnx_grid_class_args.hpp", "pnx_grid_prior_args.hpp", "pnx_grid_posterior.hpp",
+                   "pnx_grid_posterior_args.hpp", "pnx_grid.hpp", "pnx_grid_args.hpp"],
     "grid_marginal": ["pnx_grid_marginal.hip", "pnx_grid_marginal.hpp", "pnx_grid_marginal_args.hpp", "pnx_grid_prior.hpp",
                       "pnx_grid_prior_args.hpp", "pnx_grid_posterior.hpp", "pnx_grid_posterior_args.hpp", "pnx_grid.hpp", "pnx_grid_args.hpp"],
     "varpro": ["pnx_varpro.hip", "pnx_varpro.hpp", "pnx_varpro_args.hpp", "pnx_grid_args.hpp", "pnx_predict.hpp"],
@@ -80,7 +82,7 @@ def _units():
              ("pnx_resize.o", "pnx_resize.hip", []), ("pnx_predict.o", "pnx_predict.hip", []),
              ("pnx_simplex.o", "pnx_simplex.hip", []), ("pnx_grid.o", "pnx_grid.hip", []),
              ("pnx_grid_posterior.o", "pnx_grid_posterior.hip", []), ("pnx_grid_prior.o", "pnx_grid_prior.hip", []),
-             ("pnx_grid_marginal.o", "pnx_grid_marginal.hip", []),
+             ("pnx_grid_marginal.o", "pnx_grid_marginal.hip", []), ("pnx_grid_class.o", "pnx_grid_class.hip", []),
              ("pnx_varpro.o", "pnx_varpro.hip", []),
              ("pnx_varpro_posterior.o", "pnx_varpro_posterior.hip", []),
              ("pnx_varpro_marginal.o", "pnx_varpro_marginal.hip", []),
@@ -131,13 +133,17 @@ def _stale(unit, force: bool) -> bool:
         deps = [d for d in deps if os.path.basename(d) in ("pnx_grid_args.hpp", "pnx_grid_posterior_args.hpp") or "pnx_grid" not in os.path.basename(d)]
     elif src in ("pnx_varpro_marginal.hip", "pnx_varpro_prior.hip"):  # of the dictionary search's headers, the HIP-free argument halves only
         deps = [d for d in deps if os.path.basename(d).endswith("_args.hpp") or "pnx_grid" not in os.path.basename(d)]
-    elif src not in ("pnx_api.hip", "pnx_grid.hip", "pnx_grid_posterior.hip", "pnx_grid_prior.hip", "pnx_grid_marginal.hip", "pnx_varpro.hip"):
+    elif src not in ("pnx_api.hip", "pnx_grid.hip", "pnx_grid_posterior.hip", "pnx_grid_prior.hip", "pnx_grid_marginal.hip", "pnx_grid_class.hip",
+                     "pnx_varpro.hip"):
         deps = [d for d in deps if "pnx_grid" not in os.path.basename(d)]  # the dictionary search's headers: its units and the ABI's
     elif src == "pnx_varpro.hip":
         deps = [d for d in deps if os.path.basename(d) == "pnx_grid_args.hpp" or "pnx_grid" not in os.path.basename(d)]  # of those, the slab rule only
     elif src == "pnx_grid.hip":
         deps = [d for d in deps if "pnx_grid_posterior" not in os.path.basename(d)]  # the posterior's headers: its unit and the ABI's
-    if src not in ("pnx_api.hip", "pnx_grid_prior.hip", "pnx_grid_marginal.hip", "pnx_varpro_marginal.hip", "pnx_varpro_prior.hip"):
+    if src not in ("pnx_api.hip", "pnx_grid_class.hip"):
+        deps = [d for d in deps if "pnx_grid_class" not in os.path.basename(d)]  # the per-label prior's headers: its unit and the ABI's
+    if src not in ("pnx_api.hip", "pnx_grid_prior.hip", "pnx_grid_marginal.hip", "pnx_grid_class.hip", "pnx_varpro_marginal.hip",
+                   "pnx_varpro_prior.hip"):
         deps = [d for d in deps if "pnx_grid_prior" not in os.path.basename(d)]  # the EM prior's headers: likewise
     if src not in ("pnx_api.hip", "pnx_grid_marginal.hip", "pnx_varpro_marginal.hip"):
         deps = [d for d in deps if "pnx_grid_marginal" not in os.path.basename(d)]  # the marginals' headers: likewise

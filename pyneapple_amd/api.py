@@ -420,6 +420,142 @@ def grid_prior_em_device(opts, n_vox, b, y, atoms, fixed, lo, hi, project_amplit
                           device, stream)
 
 
+GRID_MAX_CLASSES = 16  # kGridMaxClasses of csrc/pnx_grid_class_args.hpp
+
+
+def grid_class_slab_atoms(n_b, n_classes, extra):
+    """Atoms per LDS slab of the per-label kernels (grid_class_slab of csrc/pnx_grid_class_args.hpp): the widest multiple of 16, at
+    most 256, whose dictionary rows and 2 + n_classes + extra values per atom fit 64 KB.  extra: n_free for the posterior,
+    4 n_classes (the wave-private rows per class) for both EM passes."""
+    kpad, width = (int(n_b) + 3) & ~3, 16
+    for w in range(16, 257, 16):
+        if kpad * (w if w & 16 else w + 16) + (2 + int(n_classes) + int(extra)) * w <= 8192:
+            width = w
+    return width
+
+
+def _class_table(log_prior, n_classes, n_atoms):
+    n_classes = int(n_classes)
+    if not 1 <= n_classes <= GRID_MAX_CLASSES:
+        raise ValueError(f"n_classes={n_classes} out of range [1, {GRID_MAX_CLASSES}]")
+    if log_prior is None:
+        return None
+    lp = np.ascontiguousarray(log_prior, np.float64)
+    if lp.shape != (n_classes, n_atoms):
+        raise ValueError(f"log_prior has shape {lp.shape}, expected ({n_classes}, {n_atoms}): one row per class, one entry per atom")
+    return lp
+
+
+def _class_host_inputs(who, model, b, y, atoms, lo, hi, labels, fixed_idx, fixed_vals, sigma, t1_mode, tr, tm):
+    b = np.ascontiguousarray(b, np.float64)
+    y = np.ascontiguousarray(np.atleast_2d(y), np.float64)
+    n_vox, n_b = y.shape
+    if b.shape != (n_b,):
+        raise ValueError(f"b has shape {b.shape}, expected ({n_b},)")
+    atoms, lo, hi = (np.ascontiguousarray(a, np.float64) for a in (atoms, lo, hi))
+    fv = None
+    if len(fixed_idx):
+        fv = np.ascontiguousarray(fixed_vals, np.float64)
+        if fv.ndim != 1:
+            raise ValueError(f"{who} takes shared fixed values (n_fixed,): per-voxel fixed maps are not built")
+    o = make_opts(model, n_b, fixed_idx, jac="analytic", t1_mode=t1_mode, tr=tr, tm=tm, sigma=sigma)
+    n = o.n_free
+    if atoms.ndim != 2 or atoms.shape[0] != n or lo.shape != (n,) or hi.shape != (n,):
+        raise ValueError(f"atoms must have shape ({n}, n_atoms), lo / hi ({n},)")
+    if fv is not None and fv.shape != (o.n_fixed,):
+        raise ValueError("fixed_vals has the wrong shape")
+    lab = np.asarray(labels)
+    if lab.shape != (n_vox,) or lab.dtype.kind not in "iu":
+        raise ValueError(f"labels must be {n_vox} integers (one per voxel), got shape {lab.shape} and dtype {lab.dtype}")
+    lab = np.ascontiguousarray(np.where((lab < 0) | (lab > np.iinfo(np.int32).max), -1, lab), np.int32)
+    return o, n_vox, b, y, atoms, fv, lo, hi, lab
+
+
+def grid_posterior_classes(model, b, y, atoms, lo, hi, labels, n_classes, *, log_prior=None, noise_sd=0.0, fixed_idx=(), fixed_vals=None,
+                           sigma=None, project_amplitude=False, t1_mode=0, tr=0., tm=0., device=0, out=None):
+    """`grid_posterior` with one prior row per segmentation label on host (numpy) arrays (pnx_curvefit_grid_posterior_classes_f64;
+    method: include/pnx.h).  The arguments of `grid_posterior`, and
+    labels (n_vox,) integers: the row of the table each voxel is judged under; a label outside [0, n_classes) -- background, -1 by
+        convention -- gives the voxel NaN outputs and map_atom -1, as a non-finite signal does;
+    n_classes: 1..16;  log_prior: None (every row uniform) or (n_classes, n_atoms), finite or -inf, every row with a finite entry.
+    Returns the dict of `grid_posterior`."""
+    _lib.require_device()
+    o, n_vox, b, y, atoms, fv, lo, hi, lab = _class_host_inputs("grid_posterior_classes", model, b, y, atoms, lo, hi, labels, fixed_idx,
+                                                                fixed_vals, sigma, t1_mode, tr, tm)
+    n = o.n_free
+    lp = _class_table(log_prior, n_classes, atoms.shape[1])
+    res = {key: _out(out, key, (n, n_vox), np.float64) for key in ("mean", "sd", "map_p")}
+    res["map_atom"] = _out(out, "map_atom", (n_vox,), np.int32)
+    res["log_evidence"] = _out(out, "log_evidence", (n_vox,), np.float64)
+    res["ess"] = _out(out, "ess", (n_vox,), np.float64)
+    check(load().pnx_curvefit_grid_posterior_classes_f64(C.byref(o), n_vox, ptr(b), ptr(y), int(atoms.shape[1]), ptr(atoms), ptr(fv), ptr(lo),
+                                                         ptr(hi), int(bool(project_amplitude)), int(n_classes), ptr(lab), ptr(lp),
+                                                         float(noise_sd), ptr(res["mean"]), ptr(res["sd"]), ptr(res["map_atom"]),
+                                                         ptr(res["map_p"]), ptr(res["log_evidence"]), ptr(res["ess"]), MEM_HOST, int(device),
+                                                         None))
+    return res
+
+
+def grid_posterior_classes_device(opts, n_vox, b, y, atoms, fixed, lo, hi, project_amplitude, labels, n_classes, log_prior, noise_sd, mean,
+                                  sd, map_atom, map_p, log_evidence, ess, device, stream=None):
+    """Enqueue `grid_posterior_classes` on HBM-resident torch tensors (asynchronous; caller synchronises): the tensors of
+    `grid_posterior_device` and labels (n_vox,) int32 on the device; log_prior (n_classes, n_atoms) or None is a host array."""
+    b, atoms, lo, hi = (np.ascontiguousarray(a, np.float64) for a in (b, atoms, lo, hi))
+    if fixed is not None:
+        fixed = np.ascontiguousarray(fixed, np.float64)
+    if atoms.ndim != 2:
+        raise ValueError("atoms must have shape (n_free, n_atoms)")
+    lp = _class_table(log_prior, n_classes, atoms.shape[1])
+    check(load().pnx_curvefit_grid_posterior_classes_f64(C.byref(opts), int(n_vox), ptr(b), ptr(y), int(atoms.shape[1]), ptr(atoms), ptr(fixed),
+                                                         ptr(lo), ptr(hi), int(bool(project_amplitude)), int(n_classes), ptr(labels), ptr(lp),
+                                                         float(noise_sd), ptr(mean), ptr(sd), ptr(map_atom), ptr(map_p), ptr(log_evidence),
+                                                         ptr(ess), MEM_DEVICE, int(device), stream))
+
+
+def _prior_em_classes_call(o, n_vox, b, y, atoms, fv, lo, hi, project_amplitude, labels, n_classes, lp, noise_sd, n_iter, pseudo_count,
+                           rel_tol, mem, device, stream):
+    n_iter, n_classes = int(n_iter), int(n_classes)
+    out = np.empty((n_classes, atoms.shape[1]), np.float64)
+    n_t = min(max(n_iter, 0), 1000) + 1  # outside 1..1000 the library refuses before it writes
+    loglik, loglik_class = np.full(n_t, np.nan), np.full((n_t, n_classes), np.nan)
+    done, n_eff = C.c_int(0), np.zeros(n_classes, np.int64)
+    check(load().pnx_curvefit_grid_prior_em_classes_f64(C.byref(o), int(n_vox), ptr(b), ptr(y), int(atoms.shape[1]), ptr(atoms), ptr(fv),
+                                                        ptr(lo), ptr(hi), int(bool(project_amplitude)), n_classes, ptr(labels), ptr(lp),
+                                                        float(noise_sd), n_iter, float(pseudo_count), float(rel_tol), ptr(out), ptr(loglik),
+                                                        ptr(loglik_class), C.byref(done), ptr(n_eff), mem, int(device), stream))
+    return dict(log_prior=out, loglik=loglik, loglik_class=loglik_class, n_iter=int(done.value), n_eff=n_eff)
+
+
+def grid_prior_em_classes(model, b, y, atoms, lo, hi, labels, n_classes, *, log_prior=None, noise_sd=0.0, n_iter=20, pseudo_count=0.0,
+                          rel_tol=1e-6, fixed_idx=(), fixed_vals=None, sigma=None, project_amplitude=False, t1_mode=0, tr=0., tm=0., device=0):
+    """`grid_prior_em` with one prior row per segmentation label, every row learned from its own voxels in one pass pair over the
+    volume (pnx_curvefit_grid_prior_em_classes_f64; method: include/pnx.h).  The arguments of `grid_prior_em`, labels and n_classes as
+    `grid_posterior_classes` takes them (a label outside [0, n_classes) takes no part), log_prior None or (n_classes, n_atoms): the
+    start.  Returns dict(log_prior (n_classes, n_atoms) every row normalised -- ready for `grid_posterior_classes` --, loglik
+    (n_iter + 1,) the sum over the classes, loglik_class (n_iter + 1, n_classes), n_iter the updates done, n_eff (n_classes,) the
+    voxels of each class that took part; a class without one keeps its normalised start row)."""
+    _lib.require_device()
+    o, n_vox, b, y, atoms, fv, lo, hi, lab = _class_host_inputs("grid_prior_em_classes", model, b, y, atoms, lo, hi, labels, fixed_idx,
+                                                                fixed_vals, sigma, t1_mode, tr, tm)
+    lp = _class_table(log_prior, n_classes, atoms.shape[1])
+    return _prior_em_classes_call(o, n_vox, b, y, atoms, fv, lo, hi, project_amplitude, lab, n_classes, lp, noise_sd, n_iter, pseudo_count,
+                                  rel_tol, MEM_HOST, device, None)
+
+
+def grid_prior_em_classes_device(opts, n_vox, b, y, atoms, fixed, lo, hi, project_amplitude, labels, n_classes, log_prior, noise_sd, n_iter,
+                                 pseudo_count, rel_tol, device, stream=None):
+    """`grid_prior_em_classes` on HBM-resident torch tensors y (n_vox, n_b) float64 and labels (n_vox,) int32, read in place; the
+    other arguments are host arrays, `opts` from make_opts.  Synchronises `stream` before it returns the same dict."""
+    b, atoms, lo, hi = (np.ascontiguousarray(a, np.float64) for a in (b, atoms, lo, hi))
+    if fixed is not None:
+        fixed = np.ascontiguousarray(fixed, np.float64)
+    if atoms.ndim != 2:
+        raise ValueError("atoms must have shape (n_free, n_atoms)")
+    lp = _class_table(log_prior, n_classes, atoms.shape[1])
+    return _prior_em_classes_call(opts, n_vox, b, y, atoms, fixed, lo, hi, project_amplitude, labels, n_classes, lp, noise_sd, n_iter,
+                                  pseudo_count, rel_tol, MEM_DEVICE, device, stream)
+
+
 GRID_MARGINAL_MAX_BINS = 128  # kGridMarginalMaxBins of csrc/pnx_grid_marginal_args.hpp
 GRID_MARGINAL_MAX_PROBS = 8
 

@@ -20,6 +20,7 @@
 #include "pnx_curvefit_kernel.hpp"
 #include "pnx_grid.hpp"
 #include "pnx_grid_args.hpp"
+#include "pnx_grid_class.hpp"
 #include "pnx_grid_posterior.hpp"
 #include "pnx_grid_marginal.hpp"
 #include "pnx_grid_prior.hpp"
@@ -1355,6 +1356,141 @@ int pnx_curvefit_grid_prior_em_f64(const pnx_curvefit_opts *o, int64_t n_vox, co
     if (loglik)
         for (int t = 0; t <= done; ++t) loglik[t] = trace[t];
     grid_prior_report(n_iter, done, stats.n_finite, loglik, n_iter_done, n_eff);
+    return PNX_OK;
+}
+
+// ---- one prior row per segmentation label (kernels: pnx_grid_class.hip, argument checks: pnx_grid_class_args.hpp) ------------
+int pnx_curvefit_grid_posterior_classes_f64(const pnx_curvefit_opts *o, int64_t n_vox, const double *b, const double *y, int n_atoms,
+                                            const double *atoms, const double *fixed, const double *lo, const double *hi,
+                                            int project_amplitude, int n_classes, const int32_t *labels, const double *log_prior,
+                                            double noise_sd, double *mean, double *sd, int32_t *map_atom, double *map_p,
+                                            double *log_evidence, double *ess, int mem, int device, void *stream) {
+    if (!o) return set_error(PNX_ERR_INVALID, "opts is NULL");
+    pnx_curvefit_opts c = *o;  // as grid start: jac_mode and the tolerances are not looked at
+    c.jac_mode = PNX_JAC_ANALYTIC;
+    c.ftol = c.xtol = c.gtol = 0.0;
+    int rc = check_curvefit_opts(&c);
+    if (rc) return rc;
+    GridPosteriorHost H;
+    GridClassHost K;
+    if ((rc = grid_class_posterior_check_args(&c, n_vox, b, y, n_atoms, atoms, fixed, lo, hi, project_amplitude, n_classes, labels, log_prior,
+                                              noise_sd, mean, mem, &H, &K)))
+        return rc;
+    if (n_vox == 0) return PNX_OK;
+    DeviceInfo *dev;
+    if ((rc = use_device(device, &dev))) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    AsyncBuf dict_buf, post_buf, table_buf;  // built once per call, stream-ordered, freed behind the work that reads them
+    GridDict D;
+    GridPosterior P;
+    GridClassTable T;
+    if ((rc = dict_buf.alloc(grid_dict_bytes(c.n_free, n_atoms, c.n_b), st))) return rc;
+    if ((rc = post_buf.alloc(grid_posterior_bytes(c.n_free, n_atoms), st))) return rc;
+    if ((rc = table_buf.alloc(grid_class_table_bytes(n_classes, n_atoms), st))) return rc;
+    if ((rc = grid_dict_build(&c, b, n_atoms, atoms, fixed, lo, hi, H.s0_row, dict_buf.p, &D, st))) return rc;
+    if ((rc = grid_posterior_prepare(D, H, nullptr, noise_sd, post_buf.p, &P, st))) return rc;  // theta about H.centre, the floor
+    if ((rc = grid_class_table_prepare(D, K, n_classes, log_prior, table_buf.p, &T, st))) return rc;
+    if (mem == PNX_MEM_DEVICE)
+        return grid_class_posterior_device(D, P, T, n_vox, y, labels, mean, sd, map_atom, map_p, log_evidence, ess, dev->cus, st);
+    PNX_HIP(hipStreamSynchronize(st));  // the ring's streams read the dictionary: complete before the first chunk starts
+    enum { GC_Y, GC_LAB, GC_MEAN, GC_SD, GC_ATOM, GC_MAPP, GC_LOGEV, GC_ESS };
+    ArrayTable A;
+    A.add(y, sizeof(double), c.n_b, false);
+    A.add(labels, sizeof(int32_t), 1, false);
+    A.add(mean, sizeof(double), c.n_free, true).pmajor = true;
+    A.add(sd, sizeof(double), c.n_free, true).pmajor = true;
+    A.add(map_atom, sizeof(int32_t), 1, true);
+    A.add(map_p, sizeof(double), c.n_free, true).pmajor = true;
+    A.add(log_evidence, sizeof(double), 1, true);
+    A.add(ess, sizeof(double), 1, true);
+    return ring_call(A, (size_t)n_vox, 3 << 18, device, st, [&](size_t n, const DevSet &S, hipStream_t s) {
+        return grid_class_posterior_device(D, P, T, (int64_t)n, S.d(GC_Y), (const int32_t *)S.dev[GC_LAB], S.d(GC_MEAN), S.d(GC_SD),
+                                           (int32_t *)S.dev[GC_ATOM], S.d(GC_MAPP), S.d(GC_LOGEV), S.d(GC_ESS), dev->cus, s);
+    });
+}
+
+int pnx_curvefit_grid_prior_em_classes_f64(const pnx_curvefit_opts *o, int64_t n_vox, const double *b, const double *y, int n_atoms,
+                                           const double *atoms, const double *fixed, const double *lo, const double *hi,
+                                           int project_amplitude, int n_classes, const int32_t *labels, const double *log_prior,
+                                           double noise_sd, int n_iter, double pseudo_count, double rel_tol, double *log_prior_out,
+                                           double *loglik, double *loglik_class, int *n_iter_done, int64_t *n_eff, int mem, int device,
+                                           void *stream) {
+    if (!o) return set_error(PNX_ERR_INVALID, "opts is NULL");
+    pnx_curvefit_opts c = *o;  // as grid start: jac_mode and the tolerances are not looked at
+    c.jac_mode = PNX_JAC_ANALYTIC;
+    c.ftol = c.xtol = c.gtol = 0.0;
+    int rc = check_curvefit_opts(&c);
+    if (rc) return rc;
+    GridPosteriorHost H;
+    GridClassHost K;
+    if ((rc = grid_class_prior_check_args(&c, n_vox, b, y, n_atoms, atoms, fixed, lo, hi, project_amplitude, n_classes, labels, log_prior,
+                                          noise_sd, n_iter, pseudo_count, rel_tol, log_prior_out, mem, &H, &K)))
+        return rc;
+    grid_class_start(n_classes, n_atoms, log_prior, K, log_prior_out);  // the start, every row normalised
+    for (int cl = 0; cl < n_classes; ++cl) K.norm[cl] = 0.0;           // and so is the table every pass reads
+    if (loglik) loglik[0] = 0.0;
+    if (loglik_class)
+        for (int cl = 0; cl < n_classes; ++cl) loglik_class[cl] = 0.0;
+    if (n_vox == 0) {
+        grid_class_report(n_iter, 0, n_classes, nullptr, loglik, loglik_class, n_iter_done, n_eff);
+        return PNX_OK;
+    }
+    DeviceInfo *dev;
+    if ((rc = use_device(device, &dev))) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    AsyncBuf dict_buf, post_buf, table_buf, work_buf, y_buf, lab_buf;  // stream-ordered, freed behind the work that reads them
+    GridDict D;
+    GridPosterior P;
+    GridClassTable T;
+    GridClassWork W;
+    if ((rc = dict_buf.alloc(grid_dict_bytes(c.n_free, n_atoms, c.n_b), st))) return rc;
+    if ((rc = post_buf.alloc(grid_posterior_bytes(c.n_free, n_atoms), st))) return rc;
+    if ((rc = table_buf.alloc(grid_class_table_bytes(n_classes, n_atoms), st))) return rc;
+    if ((rc = work_buf.alloc(grid_class_prior_bytes(n_vox, n_atoms, n_classes, dev->cus), st))) return rc;
+    if (mem == PNX_MEM_HOST) {  // every pass of every iteration reads the same signals and labels: one upload, kept for the call
+        const size_t bytes = (size_t)n_vox * c.n_b * sizeof(double), lbytes = (size_t)n_vox * sizeof(int32_t);
+        if (y_buf.alloc(bytes, st) != PNX_OK || lab_buf.alloc(lbytes, st) != PNX_OK)
+            return set_error(PNX_ERR_NOMEM, "grid prior: no device memory for the %zu bytes of y and labels (%lld voxels x %d), which stay "
+                                            "resident for all iterations: learn the prior from a sub-sample of the voxels",
+                             bytes + lbytes, (long long)n_vox, c.n_b);
+        if ((rc = pnx_upload(y_buf.p, y, (int64_t)bytes, device, st, 0))) return rc;
+        if ((rc = pnx_upload(lab_buf.p, labels, (int64_t)lbytes, device, st, 0))) return rc;
+        y = (const double *)y_buf.p;
+        labels = (const int32_t *)lab_buf.p;
+    }
+    if ((rc = grid_dict_build(&c, b, n_atoms, atoms, fixed, lo, hi, H.s0_row, dict_buf.p, &D, st))) return rc;
+    if ((rc = grid_posterior_prepare(D, H, nullptr, noise_sd, post_buf.p, &P, st))) return rc;
+    if ((rc = grid_class_table_prepare(D, K, n_classes, log_prior_out, table_buf.p, &T, st))) return rc;
+    grid_class_prior_carve(n_vox, n_atoms, n_classes, dev->cus, work_buf.p, &W);
+    std::vector<double> trace((size_t)n_iter + 1, 0.0), trace_class(((size_t)n_iter + 1) * n_classes, 0.0);
+    GridClassStats stats;
+    memset(&stats, 0, sizeof(stats));
+    int done = 0;
+    for (int t = 0;; ++t) {  // trace[t]: the log-likelihood under the table before update t, the returned table's at t = done
+        if ((rc = grid_class_prior_normalise(D, P, T, n_vox, y, labels, W, st))) return rc;
+        PNX_HIP(hipMemcpyAsync(&stats, W.stats, sizeof(stats), hipMemcpyDeviceToHost, st));
+        PNX_HIP(hipStreamSynchronize(st));
+        trace[t] = stats.loglik;
+        long long total = 0;
+        for (int cl = 0; cl < n_classes; ++cl) {
+            trace_class[(size_t)t * n_classes + cl] = stats.loglik_class[cl];
+            total += stats.n_finite[cl];
+        }
+        done = t;
+        if (total == 0 || t == n_iter || grid_prior_converged(trace.data(), t, rel_tol)) break;
+        if ((rc = grid_class_prior_update(D, P, T, n_vox, y, labels, W, pseudo_count, K.n_adm, st))) return rc;
+    }
+    PNX_HIP(hipMemcpy2DAsync(log_prior_out, (size_t)n_atoms * sizeof(double), T.lp, (size_t)D.gp * sizeof(double),
+                             (size_t)n_atoms * sizeof(double), (size_t)n_classes, hipMemcpyDeviceToHost, st));
+    PNX_HIP(hipStreamSynchronize(st));
+    for (int t = 0; t <= done; ++t) {
+        if (loglik) loglik[t] = trace[t];
+        if (loglik_class)
+            for (int cl = 0; cl < n_classes; ++cl) loglik_class[(size_t)t * n_classes + cl] = trace_class[(size_t)t * n_classes + cl];
+    }
+    int64_t finite[kGridMaxClasses];
+    for (int cl = 0; cl < n_classes; ++cl) finite[cl] = stats.n_finite[cl];
+    grid_class_report(n_iter, done, n_classes, finite, loglik, loglik_class, n_iter_done, n_eff);
     return PNX_OK;
 }
 

@@ -891,7 +891,8 @@ class HipBayesGridSolver(RefBaseSolver):
         noise_sd: None / 0 (default) marginalises the noise scale under a Jeffreys prior; > 0 is a known Gaussian noise sd in the
             units of the (sigma-weighted) signal.
         log_prior: None (uniform) or (n_atoms,) log weights in the order of the atoms (itertools.product over `model.param_names`);
-            -inf excludes an atom.
+            -inf excludes an atom.  Or (n_classes, n_atoms), n_classes <= 16: one row per segmentation label
+            (pnx_curvefit_grid_posterior_classes_f64); `fit` then needs `labels`, and row c serves the voxels whose label is c.
         project: fit the amplitude S0 per voxel and atom, clipped to its bounds, instead of taking it from the grid.  Default:
             True exactly when the model has a free S0 (as p0_grid_project).
         sigma: None, a scalar or (n_b,), as HipCurveFitSolver's.  device: HIP device index.
@@ -905,6 +906,13 @@ class HipBayesGridSolver(RefBaseSolver):
             uniform prior, while 37 voxels against 384 atoms fit their own noise and the gain is unreliable or gone (DESIGN.md
             4.1j); where the truths are uniform over the grid's ranges it does not help.  `self.log_prior` stays the caller's
             prior; the learned one is in diagnostics_ only.
+            "per_label": True (TOML: [Fitting.solver.empirical_prior] per_label = true) learns one table per segmentation label
+            instead (pnx_curvefit_grid_prior_em_classes_f64: the narrow-population case, per tissue): `fit` needs `labels`
+            (n_pixels,) integers -- HipPixelWiseFitter passes segmentation[mask] --, maps the distinct non-negative label values of
+            the call to rows 0..C-1 in ascending order (diagnostics_["prior_labels"]; more than 16 of them is a ValueError; a
+            negative label is background: NaN results, success False) and starts every row from `log_prior` (a 2-D `log_prior`
+            must then have C rows).  Each label needs as many voxels as a whole volume does for the single table.  Not built with
+            per-label priors: `marginals` and max_voxels (a ValueError that says so), hip_bayes_varpro, neighbourhood (MRF) priors.
         marginals: None / False (default): nothing more.  True, or a dict {"quantiles": [0.025, 0.5, 0.975]} (TOML: a table
             [Fitting.solver.marginals]; an unknown key is a ValueError; up to 8 levels inside (0, 1)): `fit` also reports the
             marginal posterior of every gridded parameter over its grid values and these quantiles of it
@@ -918,12 +926,15 @@ class HipBayesGridSolver(RefBaseSolver):
     After fit: params_ = the posterior mean keyed by the model's names; diagnostics_ {"posterior_sd", "map" (dicts name ->
     (n_pixels,)), "map_atom", "log_evidence", "ess", "n_pixels"} (no "pcov": the sd is the uncertainty; ess near 1 says the grid
     is too coarse for it), with empirical_prior also {"log_prior" (n_atoms,) the learned table, "prior_loglik" the EM's
-    log-likelihood trace, "prior_n_iter" the updates it ran, "prior_n_voxels" the voxels it learned from}, with marginals also
+    log-likelihood trace, "prior_n_iter" the updates it ran, "prior_n_voxels" the voxels it learned from} -- with per_label
+    "log_prior" is (C, n_atoms), "prior_loglik" (n_iter + 1, C) with its sum over the labels in "prior_loglik_total", and
+    {"prior_n_eff" (C,), "prior_labels" the label value of every row} come with them --, with marginals also
     {"marginal" {name: (n_bins, n_pixels)}, "marginal_values" {name: (n_bins,)}, "quantiles" {name: (n_q, n_pixels)},
     "quantile_probs"} (a projected S0 is absent from the three dicts); pixel_results_ with success = the voxel's signal was finite."""
 
     _MARGINALS_DEFAULTS = {"quantiles": (0.025, 0.5, 0.975)}
     _EMPIRICAL_PRIOR_DEFAULTS = {"n_iter": 20, "pseudo_count": 0.0, "rel_tol": 1e-6, "max_voxels": None}
+    _EMPIRICAL_PRIOR_PER_LABEL = {"per_label": False}  # reported among the options only when it is on
 
     def __init__(self, model: Any, grid=None, max_iter: int = 250, tol: float = 1e-8, p0: dict[str, float] | None = None,
                  bounds: dict[str, tuple[float, float]] | None = None, noise_sd: float | None = None, log_prior=None, project=None,
@@ -953,12 +964,16 @@ class HipBayesGridSolver(RefBaseSolver):
             raise ValueError(f"noise_sd must be None / 0 (marginalised) or a finite positive standard deviation, got {noise_sd!r}")
         self.log_prior = None
         if log_prior is not None:
-            lp = np.ascontiguousarray(log_prior, np.float64).reshape(-1)
-            if lp.shape != (self._atoms.shape[1],):
+            lp = np.ascontiguousarray(log_prior, np.float64)
+            if lp.ndim == 2 and lp.shape[1] == self._atoms.shape[1] and lp.shape[0] > api.GRID_MAX_CLASSES:
+                raise ValueError(f"log_prior has {lp.shape[0]} rows: at most {api.GRID_MAX_CLASSES} classes (labels) are built")
+            if not (lp.ndim == 2 and lp.shape[0] >= 2 and lp.shape[1] == self._atoms.shape[1]):  # (1, n_atoms) is the one table, as before
+                lp = lp.reshape(-1)
+            if lp.ndim == 1 and lp.shape != (self._atoms.shape[1],):
                 raise ValueError(f"log_prior has {lp.size} entries for {self._atoms.shape[1]} atoms (one per atom, in the order of "
                                  "itertools.product over model.param_names)")
-            if np.isnan(lp).any() or (lp == np.inf).any() or not np.isfinite(lp).any():
-                raise ValueError("log_prior entries must be finite or -inf, at least one of them finite")
+            if np.isnan(lp).any() or (lp == np.inf).any() or not np.isfinite(lp).any(axis=-1).all():
+                raise ValueError("log_prior entries must be finite or -inf, at least one of them finite" + (" in every row" if lp.ndim == 2 else ""))
             self.log_prior = lp
         self.sigma = None
         if sigma is not None:
@@ -971,6 +986,19 @@ class HipBayesGridSolver(RefBaseSolver):
         self.device = int(device)
         self.io_dtype = np.float64
         self.solver_kwargs = ignored_reference_kwargs
+        per_label = bool(self.empirical_prior and self.empirical_prior.get("per_label"))
+        if self.needs_labels and self.marginals:
+            raise ValueError("HipBayesGridSolver: marginals are not built with per-label priors (a 2-D log_prior or empirical_prior "
+                             "per_label): pnx_curvefit_grid_marginals_f64 takes one prior table")
+        if per_label and self.empirical_prior["max_voxels"]:
+            raise ValueError("empirical_prior max_voxels is not built with per_label: every label learns from all of its voxels")
+        if self.empirical_prior and not per_label and self.log_prior is not None and self.log_prior.ndim == 2:
+            raise ValueError("empirical_prior with a 2-D log_prior needs per_label: a single learned table has no single row to start from")
+
+    @property
+    def needs_labels(self) -> bool:
+        """True when `fit` needs `labels`: a 2-D log_prior, or empirical_prior with per_label."""
+        return bool((self.log_prior is not None and self.log_prior.ndim == 2) or (self.empirical_prior and self.empirical_prior.get("per_label")))
 
     @classmethod
     def _empirical_prior_options(cls, value):
@@ -981,10 +1009,13 @@ class HipBayesGridSolver(RefBaseSolver):
             value = {}
         if not isinstance(value, dict):
             raise ValueError(f"empirical_prior must be None, a bool or a dict of {sorted(cls._EMPIRICAL_PRIOR_DEFAULTS)}, got {value!r}")
-        unknown = sorted(set(value) - set(cls._EMPIRICAL_PRIOR_DEFAULTS))
+        known = {**cls._EMPIRICAL_PRIOR_DEFAULTS, **getattr(cls, "_EMPIRICAL_PRIOR_PER_LABEL", {})}  # the grid solver's own option
+        unknown = sorted(set(value) - set(known))
         if unknown:
             raise ValueError(f"empirical_prior has unknown keys {unknown}; it takes {sorted(cls._EMPIRICAL_PRIOR_DEFAULTS)}")
-        opt = {**cls._EMPIRICAL_PRIOR_DEFAULTS, **value}
+        opt = {"per_label": False, **known, **value}
+        if not isinstance(opt["per_label"], (bool, np.bool_)):
+            raise ValueError(f"empirical_prior per_label must be a bool, got {opt['per_label']!r}")
         n_iter, mv = opt["n_iter"], opt["max_voxels"]
         if isinstance(n_iter, bool) or int(n_iter) != n_iter or not 1 <= n_iter <= 1000:
             raise ValueError(f"empirical_prior n_iter must be an integer in [1, 1000], got {n_iter!r}")
@@ -993,8 +1024,11 @@ class HipBayesGridSolver(RefBaseSolver):
                 raise ValueError(f"empirical_prior {key} must be finite and >= 0, got {opt[key]!r}")
         if mv is not None and (isinstance(mv, bool) or int(mv) != mv or mv < 1):
             raise ValueError(f"empirical_prior max_voxels must be None or a positive integer, got {mv!r}")
-        return {"n_iter": int(n_iter), "pseudo_count": float(opt["pseudo_count"]), "rel_tol": float(opt["rel_tol"]),
-                "max_voxels": None if mv is None else int(mv)}
+        res = {"n_iter": int(n_iter), "pseudo_count": float(opt["pseudo_count"]), "rel_tol": float(opt["rel_tol"]),
+               "max_voxels": None if mv is None else int(mv)}
+        if opt["per_label"]:
+            res["per_label"] = True
+        return res
 
     @classmethod
     def _marginals_options(cls, value):
@@ -1016,7 +1050,53 @@ class HipBayesGridSolver(RefBaseSolver):
             raise ValueError(f"marginals quantiles must be at most {api.GRID_MARGINAL_MAX_PROBS} levels inside the open interval (0, 1), got {list(q)}")
         return {"quantiles": q}
 
-    def fit(self, xdata: np.ndarray, ydata: np.ndarray, pixel_fixed_params=None, **fit_kwargs) -> "HipBayesGridSolver":
+    @staticmethod
+    def label_rows(labels, n_pixels):
+        """(distinct non-negative label values ascending, row of every voxel as int32 with -1 for a negative label)."""
+        lab = np.asarray(labels)
+        if lab.dtype.kind == "f" and lab.size and np.isfinite(lab).all() and (lab == np.round(lab)).all():
+            lab = lab.astype(np.int64)  # a segmentation read from an image file is often stored as floats
+        if lab.shape != (n_pixels,) or lab.dtype.kind not in "iu":
+            raise ValueError(f"labels must be {n_pixels} integers (one per pixel), got shape {lab.shape} and dtype {lab.dtype}")
+        values = np.unique(lab[lab >= 0])
+        if values.size > api.GRID_MAX_CLASSES:
+            raise ValueError(f"labels hold {values.size} distinct non-negative values: more than {api.GRID_MAX_CLASSES} classes are "
+                             "not built (merge labels, or fit the tissues in separate calls)")
+        rows = np.where(lab >= 0, np.searchsorted(values, np.maximum(lab, 0)), -1).astype(np.int32)
+        return values, rows
+
+    def _fit_labelled(self, xdata, ydata, labels, lo, hi, common):
+        """(posterior result, learned or None) under one prior row per label."""
+        n_pixels = ydata.shape[0]
+        if labels is None:
+            raise ValueError("HipBayesGridSolver: labels (n_pixels,) is required with a 2-D log_prior or empirical_prior per_label")
+        per_label = bool(self.empirical_prior and self.empirical_prior.get("per_label"))
+        table = self.log_prior
+        if per_label:
+            values, rows = self.label_rows(labels, n_pixels)
+            n_classes = max(int(values.size), 1)
+            if table is not None and table.ndim == 2 and table.shape[0] != n_classes:
+                raise ValueError(f"log_prior has {table.shape[0]} rows for the {n_classes} distinct labels of this call")
+            if table is not None and table.ndim == 1:
+                table = np.ascontiguousarray(np.broadcast_to(table, (n_classes, table.size)))
+        else:  # the caller's table: label c is row c, anything else is background
+            n_classes = table.shape[0]
+            lab = np.asarray(labels)
+            if lab.shape != (n_pixels,) or lab.dtype.kind not in "iuf":
+                raise ValueError(f"labels must be {n_pixels} integers (one per pixel), got shape {lab.shape} and dtype {lab.dtype}")
+            rows = np.where((lab >= 0) & (lab < n_classes) & (lab == np.floor(lab)), lab, -1).astype(np.int32)
+        learned = None
+        if per_label:
+            ep = self.empirical_prior
+            learned = api.grid_prior_em_classes(self._kernel_model, xdata, ydata, self._atoms, lo, hi, rows, n_classes, log_prior=table,
+                                                n_iter=ep["n_iter"], pseudo_count=ep["pseudo_count"], rel_tol=ep["rel_tol"], **common)
+            learned["n_voxels"] = n_pixels
+            learned["labels"] = values
+            table = learned["log_prior"]
+        res = api.grid_posterior_classes(self._kernel_model, xdata, ydata, self._atoms, lo, hi, rows, n_classes, log_prior=table, **common)
+        return res, learned
+
+    def fit(self, xdata: np.ndarray, ydata: np.ndarray, pixel_fixed_params=None, labels=None, **fit_kwargs) -> "HipBayesGridSolver":
         if pixel_fixed_params:
             raise ValueError("HipBayesGridSolver is not built with per-pixel fixed parameters (pixel_fixed_params): the dictionary "
                              "would differ from voxel to voxel")
@@ -1039,7 +1119,9 @@ class HipBayesGridSolver(RefBaseSolver):
         common = dict(noise_sd=self.noise_sd, fixed_idx=fixed_idx, fixed_vals=fixed_vals, sigma=self.sigma, project_amplitude=self.project,
                       device=self.device, **self._kernel_t1)
         log_prior, learned = self.log_prior, None
-        if self.empirical_prior:
+        if self.needs_labels:
+            res, learned = self._fit_labelled(xdata, ydata, labels, lo, hi, common)
+        elif self.empirical_prior:
             ep = self.empirical_prior
             step = 1 if ep["max_voxels"] is None else -(-n_pixels // ep["max_voxels"])
             sample = ydata[::step]
@@ -1047,7 +1129,8 @@ class HipBayesGridSolver(RefBaseSolver):
                                         pseudo_count=ep["pseudo_count"], rel_tol=ep["rel_tol"], **common)
             learned["n_voxels"] = sample.shape[0]
             log_prior = learned["log_prior"]
-        res = api.grid_posterior(self._kernel_model, xdata, ydata, self._atoms, lo, hi, log_prior=log_prior, **common)
+        if not self.needs_labels:
+            res = api.grid_posterior(self._kernel_model, xdata, ydata, self._atoms, lo, hi, log_prior=log_prior, **common)
         mean, atom = res["mean"], res["map_atom"]
         self.pixel_results_ = PixelResultsView(mean.T, None, atom >= 0,
                                                lambda i, a=atom: None if a[i] >= 0 else _BAYES_MESSAGES[-2])
@@ -1058,6 +1141,9 @@ class HipBayesGridSolver(RefBaseSolver):
         if learned is not None:
             self.diagnostics_.update({"log_prior": learned["log_prior"], "prior_loglik": learned["loglik"], "prior_n_iter": learned["n_iter"],
                                       "prior_n_voxels": learned["n_voxels"]})
+            if "labels" in learned:
+                self.diagnostics_.update({"prior_loglik": learned["loglik_class"], "prior_loglik_total": learned["loglik"],
+                                          "prior_n_eff": learned["n_eff"], "prior_labels": [int(v) for v in learned["labels"]]})
         if self.marginals:
             mg = api.grid_marginals(self._kernel_model, xdata, ydata, self._atoms, lo, hi, log_prior=log_prior,
                                     quantiles=self.marginals["quantiles"], **common)
