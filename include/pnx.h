@@ -721,6 +721,65 @@ PNX_API int pnx_curvefit_varpro_prior_em_f64(const pnx_curvefit_opts *opts, int6
                                      double pseudo_count, double rel_tol, double *log_prior_out, double *loglik, int *n_iter_done,
                                      int64_t *n_eff, int mem, int device, void *stream);
 /*
+ * pnx_curvefit_varpro_posterior_f64 with one prior row per segmentation label.  Every argument of that call, its
+ * weighting, refusals and outputs (clipped_mass included), and
+ *   n_classes in [1, 16] (PNX_ERR_INVALID otherwise);
+ *   labels (n_vox,) int32, host|device as `mem`: the row of the table voxel v is judged under;
+ *   log_prior (n_classes, n_atoms) row-major, host, or NULL (every row uniform): every entry finite or -inf (NaN or +inf is
+ *     PNX_ERR_INVALID and names log_prior[c, g]); rows may exclude different atoms; every row needs at least one finite entry --
+ *     otherwise PNX_ERR_INVALID with a message that names the row, before any device work.
+ * Per voxel v, with c = labels[v]:
+ *   occ_g = marginal_amplitudes ? -0.5 log det N_g : 0, shared by all classes and built once per call on the device;
+ *   lw_cg = log_prior[c, g] + occ_g;   l_g(v) is pnx_curvefit_varpro_posterior_f64's, term for term, with lw taken from row c;
+ *   log_evidence_v = L_v - log sum_g exp(log_prior[c, g]);  a pair whose lw is -inf has weight exactly 0.
+ * An atom whose occ_g is not finite is inadmissible in every row; a voxel whose row has no atom with a finite l is reported as the
+ * unlabelled call reports it (NaN, map_atom = -1).
+ * Labels may live on the device and are not validated on the host: a voxel whose label lies outside [0, n_classes) is treated
+ * exactly as a voxel with a non-finite signal -- NaN in every floating output, map_atom = -1 -- and its neighbours are
+ * bit-identical to a run without it.  This is how a caller marks background (label -1).
+ * Every sum of a voxel depends on the order of the atoms only: a voxel's outputs are the bytes
+ * pnx_curvefit_varpro_posterior_f64 returns for it under log_prior[c, :] whenever the rows admit the same atoms.  The moments of
+ * the non-linear rows are accumulated about the mid-range of the atoms that ANY row admits (linear rows about 0): with rows that
+ * exclude different atoms mean and sd of the non-linear rows agree within the posterior's rounding bound taken over that range,
+ * every other output stays byte-equal.  With n_classes == 1 and every label 0 the call returns the unlabelled call's bytes.
+ * PNX_MEM_DEVICE only enqueues; PNX_MEM_HOST goes through the chunk ring, the labels beside the signals.
+ */
+PNX_API int pnx_curvefit_varpro_posterior_classes_f64(const pnx_curvefit_opts *opts, int64_t n_vox, const double *b, const double *y,
+                                      int n_atoms, const double *nl_atoms, const double *fixed, const double *lo, const double *hi,
+                                      int n_classes, const int32_t *labels, const double *log_prior, double noise_sd,
+                                      int marginal_amplitudes, double *mean, double *sd, int32_t *map_atom, double *map_p,
+                                      double *log_evidence, double *ess, double *clipped_mass, int mem, int device, void *stream);
+/*
+ * pnx_curvefit_varpro_prior_em_f64 with one prior row per segmentation label, all rows learned in one pass pair over the volume
+ * (DESIGN.md 4.1o).  n_classes, labels and log_prior (n_classes, n_atoms) as pnx_curvefit_varpro_posterior_classes_f64 takes
+ * them, with its lw_cg, its refusals and its rule for a label outside [0, n_classes): such a voxel takes no part.  Every row of
+ * the start is normalised first.  One update, per class c:
+ *   n_adm_c: the atoms with a finite start entry in row c and a finite occ_g; every other entry of row c is -inf, always;
+ *   S_cg = sum of W_vg over the voxels of class c that take part (finite signal, label in range, an atom with a finite l);
+ *   pi_cg <- (S_cg + pseudo_count) / (n_eff_c + pseudo_count n_adm_c)
+ * and log_prior[c, g] <- log pi_cg; an entry at -inf stays there; a class without a voxel that takes part keeps its normalised
+ * start row (a class whose finite entries all sit on atoms without a finite occ_g has none).
+ *   log_prior_out (n_classes, n_atoms) host, not NULL;
+ *   loglik (n_iter + 1,) host or NULL: the sum over the classes, in class order, of
+ *   loglik_class (n_iter + 1, n_classes) host or NULL: per class the sum of L_v over its voxels that take part, under the table
+ *     before update t; entries past `done` are NaN in both;
+ *   n_iter_done: `done`; the stopping rule is pnx_curvefit_varpro_prior_em_f64's, applied to loglik (the sum);
+ *   n_eff (n_classes,) int64 host or NULL: per class the voxels that take part.  Without any the call returns PNX_OK with the
+ *     normalised start, done = 0 and loglik[0] = 0.
+ * No atomics; every sum has one order for a given launch grid: two calls return the same bytes, PNX_MEM_HOST or PNX_MEM_DEVICE;
+ * the (n_vox, n_atoms) matrix W never reaches memory.  With n_classes == 1 and every label 0 the call returns the bytes of
+ * pnx_curvefit_varpro_prior_em_f64.  The accumulate pass separates the classes that meet in a strip of 16 voxels in a loop over
+ * the classes present there: a label map sorted by class pays for one class per strip (DESIGN.md 4.1o has the cost).
+ *   y, labels host|device as `mem`; PNX_MEM_HOST uploads both once for all iterations (no chunk ring; PNX_ERR_NOMEM names the
+ *   size).  For both `mem` values the call SYNCHRONISES `stream` before it returns.
+ */
+PNX_API int pnx_curvefit_varpro_prior_em_classes_f64(const pnx_curvefit_opts *opts, int64_t n_vox, const double *b, const double *y,
+                                     int n_atoms, const double *nl_atoms, const double *fixed, const double *lo, const double *hi,
+                                     int n_classes, const int32_t *labels, const double *log_prior, double noise_sd,
+                                     int marginal_amplitudes, int n_iter, double pseudo_count, double rel_tol, double *log_prior_out,
+                                     double *loglik, double *loglik_class, int *n_iter_done, int64_t *n_eff, int mem, int device,
+                                     void *stream);
+/*
  * Log-linear mono-exponential fit, ln S = ln S0 - b D by (weighted) linear least squares per voxel: the ADC
  * map, step 1 of a segmented IVIM fit, a cheap source of S0 / D start values.  A closed form over one pass of the data: a voxel
  * costs its signal row in and its results out.  Per voxel, in fp64, in the order written:

@@ -51,6 +51,10 @@ SOURCE_GROUPS = {
     "varpro_prior": ["pnx_varpro_prior.hip", "pnx_varpro_prior.hpp", "pnx_varpro_prior_args.hpp", "pnx_varpro_pair.hpp",
                      "pnx_varpro_posterior.hpp", "pnx_varpro_posterior_args.hpp", "pnx_varpro.hpp", "pnx_varpro_args.hpp",
                      "pnx_grid_prior_args.hpp", "pnx_grid_posterior_args.hpp", "pnx_grid_args.hpp"],
+    "varpro_class": ["pnx_varpro_class.hip", "pnx_varpro_class.hpp", "pnx_varpro_class_args.hpp", "pnx_varpro_prior_args.hpp",
+                     "pnx_varpro_pair.hpp", "pnx_varpro_posterior.hpp", "pnx_varpro_posterior_args.hpp", "pnx_varpro.hpp",
+                     "pnx_varpro_args.hpp", "pnx_grid_class_args.hpp", "pnx_grid_prior_args.hpp", "pnx_grid_posterior_args.hpp",
+                     "pnx_grid_args.hpp"],
     "loglin": ["pnx_loglin.hip", "pnx_loglin.hpp", "pnx_loglin_args.hpp", "pnx_tile.hpp"],
     "peel": ["pnx_peel.hip", "pnx_peel.hpp", "pnx_peel_args.hpp", "pnx_tile.hpp"],
     # the host boundary (streamed path, chunk ring, deferred NNLS hand-over, peak tables): host-mode / PCIe-inclusive figures and
@@ -87,6 +91,7 @@ def _units():
              ("pnx_varpro_posterior.o", "pnx_varpro_posterior.hip", []),
              ("pnx_varpro_marginal.o", "pnx_varpro_marginal.hip", []),
              ("pnx_varpro_prior.o", "pnx_varpro_prior.hip", []),
+             ("pnx_varpro_class.o", "pnx_varpro_class.hip", []),
              ("pnx_loglin.o", "pnx_loglin.hip", []), ("pnx_peel.o", "pnx_peel.hip", []),
              ("pnx_curvefit_f32.o", "pnx_curvefit_f32.hip", CURVEFIT_FLAGS)]
     for m in range(N_MODELS):
@@ -131,7 +136,7 @@ def _stale(unit, force: bool) -> bool:
         deps = [d for d in deps if "pnx_nnls" not in os.path.basename(d)]  # these units include no NNLS header
     if src == "pnx_varpro_posterior.hip":  # the args headers of its two parents and the slab rule
         deps = [d for d in deps if os.path.basename(d) in ("pnx_grid_args.hpp", "pnx_grid_posterior_args.hpp") or "pnx_grid" not in os.path.basename(d)]
-    elif src in ("pnx_varpro_marginal.hip", "pnx_varpro_prior.hip"):  # of the dictionary search's headers, the HIP-free argument halves only
+    elif src in ("pnx_varpro_marginal.hip", "pnx_varpro_prior.hip", "pnx_varpro_class.hip"):  # of the dictionary search's headers, the HIP-free argument halves only
         deps = [d for d in deps if os.path.basename(d).endswith("_args.hpp") or "pnx_grid" not in os.path.basename(d)]
     elif src not in ("pnx_api.hip", "pnx_grid.hip", "pnx_grid_posterior.hip", "pnx_grid_prior.hip", "pnx_grid_marginal.hip", "pnx_grid_class.hip",
                      "pnx_varpro.hip"):
@@ -140,10 +145,10 @@ def _stale(unit, force: bool) -> bool:
         deps = [d for d in deps if os.path.basename(d) == "pnx_grid_args.hpp" or "pnx_grid" not in os.path.basename(d)]  # of those, the slab rule only
     elif src == "pnx_grid.hip":
         deps = [d for d in deps if "pnx_grid_posterior" not in os.path.basename(d)]  # the posterior's headers: its unit and the ABI's
-    if src not in ("pnx_api.hip", "pnx_grid_class.hip"):
+    if src not in ("pnx_api.hip", "pnx_grid_class.hip", "pnx_varpro_class.hip"):
         deps = [d for d in deps if "pnx_grid_class" not in os.path.basename(d)]  # the per-label prior's headers: its unit and the ABI's
     if src not in ("pnx_api.hip", "pnx_grid_prior.hip", "pnx_grid_marginal.hip", "pnx_grid_class.hip", "pnx_varpro_marginal.hip",
-                   "pnx_varpro_prior.hip"):
+                   "pnx_varpro_prior.hip", "pnx_varpro_class.hip"):
         deps = [d for d in deps if "pnx_grid_prior" not in os.path.basename(d)]  # the EM prior's headers: likewise
     if src not in ("pnx_api.hip", "pnx_grid_marginal.hip", "pnx_varpro_marginal.hip"):
         deps = [d for d in deps if "pnx_grid_marginal" not in os.path.basename(d)]  # the marginals' headers: likewise
@@ -151,9 +156,11 @@ def _stale(unit, force: bool) -> bool:
         deps = [d for d in deps if "pnx_loglin" not in os.path.basename(d)]  # the log-linear fit's headers: likewise
     if src == "pnx_varpro.hip":  # the posterior's headers and the pair function: the posterior's and the marginals' units, the ABI's
         deps = [d for d in deps if "pnx_varpro_posterior" not in os.path.basename(d) and "pnx_varpro_pair" not in os.path.basename(d)]
-    elif src not in ("pnx_api.hip", "pnx_varpro_posterior.hip", "pnx_varpro_marginal.hip", "pnx_varpro_prior.hip"):
+    elif src not in ("pnx_api.hip", "pnx_varpro_posterior.hip", "pnx_varpro_marginal.hip", "pnx_varpro_prior.hip", "pnx_varpro_class.hip"):
         deps = [d for d in deps if "pnx_varpro" not in os.path.basename(d)]  # the variable-projection fit's headers: likewise
-    if src not in ("pnx_api.hip", "pnx_varpro_prior.hip"):
+    if src not in ("pnx_api.hip", "pnx_varpro_class.hip"):
+        deps = [d for d in deps if "pnx_varpro_class" not in os.path.basename(d)]  # the varpro per-label prior's headers: likewise
+    if src not in ("pnx_api.hip", "pnx_varpro_prior.hip", "pnx_varpro_class.hip"):
         deps = [d for d in deps if "pnx_varpro_prior" not in os.path.basename(d)]  # the varpro EM prior's headers: likewise
     if src not in ("pnx_api.hip", "pnx_varpro_marginal.hip"):
         deps = [d for d in deps if "pnx_varpro_marginal" not in os.path.basename(d)]  # the varpro marginals' headers: likewise

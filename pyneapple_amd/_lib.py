@@ -32,6 +32,7 @@ ABI_SYMBOLS = [
     "pnx_curvefit_grid_marginals_f64", "pnx_curvefit_varpro_marginals_f64", "pnx_curvefit_varpro_prior_em_f64",
     "pnx_loglinear_f64", "pnx_loglinear_f32", "pnx_peel_f64", "pnx_peel_f32",
     "pnx_curvefit_grid_posterior_classes_f64", "pnx_curvefit_grid_prior_em_classes_f64",
+    "pnx_curvefit_varpro_posterior_classes_f64", "pnx_curvefit_varpro_prior_em_classes_f64",
 ]
 
 
@@ -153,6 +154,14 @@ def load():
     lib.pnx_curvefit_varpro_prior_em_f64.argtypes = [C.POINTER(CurvefitOpts), C.c_int64, dp, dp, C.c_int, dp, dp, dp, dp, dp, C.c_double, C.c_int,
                                                      C.c_int, C.c_double, C.c_double, dp, dp, C.POINTER(C.c_int), C.POINTER(C.c_int64),
                                                      C.c_int, C.c_int, vp]
+    # the unlabelled varpro calls' arguments with n_classes, labels in front of log_prior (n_classes, n_atoms); the EM's loglik_class behind loglik
+    lib.pnx_curvefit_varpro_posterior_classes_f64.restype = C.c_int
+    lib.pnx_curvefit_varpro_posterior_classes_f64.argtypes = [C.POINTER(CurvefitOpts), C.c_int64, dp, dp, C.c_int, dp, dp, dp, dp, C.c_int, vp, dp,
+                                                              C.c_double, C.c_int, dp, dp, vp, dp, dp, dp, dp, C.c_int, C.c_int, vp]
+    lib.pnx_curvefit_varpro_prior_em_classes_f64.restype = C.c_int
+    lib.pnx_curvefit_varpro_prior_em_classes_f64.argtypes = [C.POINTER(CurvefitOpts), C.c_int64, dp, dp, C.c_int, dp, dp, dp, dp, C.c_int, vp, dp,
+                                                             C.c_double, C.c_int, C.c_int, C.c_double, C.c_double, dp, dp, dp,
+                                                             C.POINTER(C.c_int), vp, C.c_int, C.c_int, vp]
     # the posterior's inputs, n_bins, bin_of, bin_value, n_q, probs, marginal, quantile, geo_mean, log_evidence
     lib.pnx_curvefit_varpro_marginals_f64.restype = C.c_int
     lib.pnx_curvefit_varpro_marginals_f64.argtypes = [C.POINTER(CurvefitOpts), C.c_int64, dp, dp, C.c_int, dp, dp, dp, dp, dp, C.c_double, C.c_int,

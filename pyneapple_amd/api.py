@@ -446,6 +446,14 @@ def _class_table(log_prior, n_classes, n_atoms):
     return lp
 
 
+def _class_labels(labels, n_vox):
+    """One int32 label per voxel for the per-label calls of either solver; a label that int32 cannot hold is background (-1)."""
+    lab = np.asarray(labels)
+    if lab.shape != (n_vox,) or lab.dtype.kind not in "iu":
+        raise ValueError(f"labels must be {n_vox} integers (one per voxel), got shape {lab.shape} and dtype {lab.dtype}")
+    return np.ascontiguousarray(np.where((lab < 0) | (lab > np.iinfo(np.int32).max), -1, lab), np.int32)
+
+
 def _class_host_inputs(who, model, b, y, atoms, lo, hi, labels, fixed_idx, fixed_vals, sigma, t1_mode, tr, tm):
     b = np.ascontiguousarray(b, np.float64)
     y = np.ascontiguousarray(np.atleast_2d(y), np.float64)
@@ -464,11 +472,7 @@ def _class_host_inputs(who, model, b, y, atoms, lo, hi, labels, fixed_idx, fixed
         raise ValueError(f"atoms must have shape ({n}, n_atoms), lo / hi ({n},)")
     if fv is not None and fv.shape != (o.n_fixed,):
         raise ValueError("fixed_vals has the wrong shape")
-    lab = np.asarray(labels)
-    if lab.shape != (n_vox,) or lab.dtype.kind not in "iu":
-        raise ValueError(f"labels must be {n_vox} integers (one per voxel), got shape {lab.shape} and dtype {lab.dtype}")
-    lab = np.ascontiguousarray(np.where((lab < 0) | (lab > np.iinfo(np.int32).max), -1, lab), np.int32)
-    return o, n_vox, b, y, atoms, fv, lo, hi, lab
+    return o, n_vox, b, y, atoms, fv, lo, hi, _class_labels(labels, n_vox)
 
 
 def grid_posterior_classes(model, b, y, atoms, lo, hi, labels, n_classes, *, log_prior=None, noise_sd=0.0, fixed_idx=(), fixed_vals=None,
@@ -881,6 +885,116 @@ def varpro_prior_em_device(opts, n_vox, b, y, nl_atoms, fixed, lo, hi, log_prior
     lp = _posterior_log_prior(log_prior, nl_atoms.shape[1])
     return _varpro_prior_em_call(opts, n_vox, b, y, nl_atoms, fixed, lo, hi, lp, noise_sd, marginal_amplitudes, n_iter, pseudo_count, rel_tol,
                                  MEM_DEVICE, device, stream)
+
+
+def varpro_class_slab_atoms(n_b, k, n_classes, extra):
+    """Atoms per LDS slab of the per-label kernels over the variable-projection dictionary (varpro_class_slab of
+    csrc/pnx_varpro_class_args.hpp): the variable projection's rule with n_classes + extra more values per atom -- the rows of
+    log-weights and, as extra, the posterior's k + 1 centred non-linear values or the 4 n_classes wave-private rows of both EM
+    passes.  At one class these are `varpro_posterior_slab_atoms` and `varpro_prior_slab_atoms`."""
+    kpad, k, width = (int(n_b) + 3) & ~3, int(k), 16
+    for w in range(16, 257, 16):
+        if k * kpad * (w if w & 16 else w + 16) + (k * (k + 1) + int(n_classes) + int(extra)) * w <= 8192:
+            width = w
+    return width
+
+
+def _varpro_class_host_inputs(model, b, y, nl_atoms, lo, hi, labels, fixed_idx, fixed_vals, sigma, t1_mode, tr, tm):
+    b = np.ascontiguousarray(b, np.float64)
+    y = np.ascontiguousarray(np.atleast_2d(y), np.float64)
+    n_vox, n_b = y.shape
+    if b.shape != (n_b,):
+        raise ValueError(f"b has shape {b.shape}, expected ({n_b},)")
+    o, nl_atoms, lo, hi, _, fv = _varpro_args(model, n_b, nl_atoms, lo, hi, lo, fixed_idx, fixed_vals, sigma, t1_mode, tr, tm)
+    return o, n_vox, b, y, nl_atoms, fv, lo, hi, _class_labels(labels, n_vox)
+
+
+def varpro_posterior_classes(model, b, y, nl_atoms, lo, hi, labels, n_classes, *, log_prior=None, noise_sd=0.0, marginal_amplitudes=True,
+                             fixed_idx=(), fixed_vals=None, sigma=None, t1_mode=0, tr=0., tm=0., device=0, out=None):
+    """`varpro_posterior` with one prior row per segmentation label on host (numpy) arrays
+    (pnx_curvefit_varpro_posterior_classes_f64; method: include/pnx.h).  The arguments of `varpro_posterior`, and
+    labels (n_vox,) integers: the row of the table each voxel is judged under; a label outside [0, n_classes) -- background, -1 by
+        convention -- gives the voxel NaN outputs and map_atom -1, as a non-finite signal does;
+    n_classes: 1..16;  log_prior: None (every row uniform) or (n_classes, n_atoms), finite or -inf, every row with a finite entry.
+    Returns the dict of `varpro_posterior`."""
+    _lib.require_device()
+    o, n_vox, b, y, nl_atoms, fv, lo, hi, lab = _varpro_class_host_inputs(model, b, y, nl_atoms, lo, hi, labels, fixed_idx, fixed_vals, sigma,
+                                                                          t1_mode, tr, tm)
+    n = o.n_free
+    lp = _class_table(log_prior, n_classes, nl_atoms.shape[1])
+    res = {key: _out(out, key, (n, n_vox), np.float64) for key in ("mean", "sd", "map_p")}
+    res["map_atom"] = _out(out, "map_atom", (n_vox,), np.int32)
+    for key in ("log_evidence", "ess", "clipped_mass"):
+        res[key] = _out(out, key, (n_vox,), np.float64)
+    check(load().pnx_curvefit_varpro_posterior_classes_f64(C.byref(o), n_vox, ptr(b), ptr(y), int(nl_atoms.shape[1]), ptr(nl_atoms), ptr(fv),
+                                                           ptr(lo), ptr(hi), int(n_classes), ptr(lab), ptr(lp), float(noise_sd),
+                                                           int(bool(marginal_amplitudes)), ptr(res["mean"]), ptr(res["sd"]),
+                                                           ptr(res["map_atom"]), ptr(res["map_p"]), ptr(res["log_evidence"]), ptr(res["ess"]),
+                                                           ptr(res["clipped_mass"]), MEM_HOST, int(device), None))
+    return res
+
+
+def varpro_posterior_classes_device(opts, n_vox, b, y, nl_atoms, fixed, lo, hi, labels, n_classes, log_prior, noise_sd, marginal_amplitudes,
+                                    mean, sd, map_atom, map_p, log_evidence, ess, clipped_mass, device, stream=None):
+    """Enqueue `varpro_posterior_classes` on HBM-resident torch tensors (asynchronous; caller synchronises): the tensors of
+    `varpro_posterior_device` and labels (n_vox,) int32 on the device; log_prior (n_classes, n_atoms) or None is a host array."""
+    b, nl_atoms, lo, hi = (np.ascontiguousarray(a, np.float64) for a in (b, nl_atoms, lo, hi))
+    if fixed is not None:
+        fixed = np.ascontiguousarray(fixed, np.float64)
+    if nl_atoms.ndim != 2:
+        raise ValueError("nl_atoms must have shape (n_nonlinear_free, n_atoms)")
+    lp = _class_table(log_prior, n_classes, nl_atoms.shape[1])
+    check(load().pnx_curvefit_varpro_posterior_classes_f64(C.byref(opts), int(n_vox), ptr(b), ptr(y), int(nl_atoms.shape[1]), ptr(nl_atoms),
+                                                           ptr(fixed), ptr(lo), ptr(hi), int(n_classes), ptr(labels), ptr(lp), float(noise_sd),
+                                                           int(bool(marginal_amplitudes)), ptr(mean), ptr(sd), ptr(map_atom), ptr(map_p),
+                                                           ptr(log_evidence), ptr(ess), ptr(clipped_mass), MEM_DEVICE, int(device), stream))
+
+
+def _varpro_prior_em_classes_call(o, n_vox, b, y, nl_atoms, fv, lo, hi, labels, n_classes, lp, noise_sd, marginal_amplitudes, n_iter,
+                                  pseudo_count, rel_tol, mem, device, stream):
+    n_iter, n_classes = int(n_iter), int(n_classes)
+    out = np.empty((n_classes, nl_atoms.shape[1]), np.float64)
+    n_t = min(max(n_iter, 0), 1000) + 1  # outside 1..1000 the library refuses before it writes
+    loglik, loglik_class = np.full(n_t, np.nan), np.full((n_t, n_classes), np.nan)
+    done, n_eff = C.c_int(0), np.zeros(n_classes, np.int64)
+    check(load().pnx_curvefit_varpro_prior_em_classes_f64(C.byref(o), int(n_vox), ptr(b), ptr(y), int(nl_atoms.shape[1]), ptr(nl_atoms), ptr(fv),
+                                                          ptr(lo), ptr(hi), n_classes, ptr(labels), ptr(lp), float(noise_sd),
+                                                          int(bool(marginal_amplitudes)), n_iter, float(pseudo_count), float(rel_tol),
+                                                          ptr(out), ptr(loglik), ptr(loglik_class), C.byref(done), ptr(n_eff), mem,
+                                                          int(device), stream))
+    return dict(log_prior=out, loglik=loglik, loglik_class=loglik_class, n_iter=int(done.value), n_eff=n_eff)
+
+
+def varpro_prior_em_classes(model, b, y, nl_atoms, lo, hi, labels, n_classes, *, log_prior=None, noise_sd=0.0, marginal_amplitudes=True,
+                            n_iter=20, pseudo_count=0.0, rel_tol=1e-6, fixed_idx=(), fixed_vals=None, sigma=None, t1_mode=0, tr=0., tm=0.,
+                            device=0):
+    """`varpro_prior_em` with one prior row per segmentation label, every row learned from its own voxels in one pass pair over the
+    volume (pnx_curvefit_varpro_prior_em_classes_f64; method: include/pnx.h).  The arguments of `varpro_prior_em`, labels and
+    n_classes as `varpro_posterior_classes` takes them (a label outside [0, n_classes) takes no part), log_prior None or
+    (n_classes, n_atoms): the start.  Returns `grid_prior_em_classes`' dict: log_prior (n_classes, n_atoms) every row normalised --
+    ready for `varpro_posterior_classes` --, loglik (n_iter + 1,) the sum over the classes, loglik_class (n_iter + 1, n_classes),
+    n_iter the updates done, n_eff (n_classes,) the voxels of each class that took part; a class without one keeps its normalised
+    start row."""
+    _lib.require_device()
+    o, n_vox, b, y, nl_atoms, fv, lo, hi, lab = _varpro_class_host_inputs(model, b, y, nl_atoms, lo, hi, labels, fixed_idx, fixed_vals, sigma,
+                                                                          t1_mode, tr, tm)
+    lp = _class_table(log_prior, n_classes, nl_atoms.shape[1])
+    return _varpro_prior_em_classes_call(o, n_vox, b, y, nl_atoms, fv, lo, hi, lab, n_classes, lp, noise_sd, marginal_amplitudes, n_iter,
+                                         pseudo_count, rel_tol, MEM_HOST, device, None)
+
+
+def varpro_prior_em_classes_device(opts, n_vox, b, y, nl_atoms, fixed, lo, hi, labels, n_classes, log_prior, noise_sd, marginal_amplitudes,
+                                   n_iter, pseudo_count, rel_tol, device, stream=None):
+    """`varpro_prior_em_classes` on HBM-resident torch tensors y (n_vox, n_b) float64 and labels (n_vox,) int32, read in place; the
+    other arguments are host arrays, `opts` from make_opts.  Synchronises `stream` before it returns the same dict."""
+    b, nl_atoms, lo, hi = (np.ascontiguousarray(a, np.float64) for a in (b, nl_atoms, lo, hi))
+    if fixed is not None:
+        fixed = np.ascontiguousarray(fixed, np.float64)
+    if nl_atoms.ndim != 2:
+        raise ValueError("nl_atoms must have shape (n_nonlinear_free, n_atoms)")
+    lp = _class_table(log_prior, n_classes, nl_atoms.shape[1])
+    return _varpro_prior_em_classes_call(opts, n_vox, b, y, nl_atoms, fixed, lo, hi, labels, n_classes, lp, noise_sd, marginal_amplitudes,
+                                         n_iter, pseudo_count, rel_tol, MEM_DEVICE, device, stream)
 
 
 def _varpro_marginal_bins(o, model, nl_atoms, bins):

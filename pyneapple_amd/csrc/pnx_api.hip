@@ -32,6 +32,7 @@
 #include "pnx_predict.hpp"
 #include "pnx_simplex.hpp"
 #include "pnx_varpro.hpp"
+#include "pnx_varpro_class.hpp"
 #include "pnx_varpro_marginal.hpp"
 #include "pnx_varpro_posterior.hpp"
 #include "pnx_varpro_prior.hpp"
@@ -1762,6 +1763,145 @@ int pnx_curvefit_varpro_prior_em_f64(const pnx_curvefit_opts *o, int64_t n_vox, 
     if (loglik)
         for (int t = 0; t <= done; ++t) loglik[t] = trace[t];
     grid_prior_report(n_iter, done, stats.n_finite, loglik, n_iter_done, n_eff);
+    return PNX_OK;
+}
+
+// ---- one prior row per segmentation label over the variable-projection dictionary (kernels: pnx_varpro_class.hip and the
+// posterior's preparation, argument checks: pnx_varpro_class_args.hpp; the host loop is pnx_curvefit_grid_prior_em_classes_f64's)
+int pnx_curvefit_varpro_posterior_classes_f64(const pnx_curvefit_opts *o, int64_t n_vox, const double *b, const double *y, int n_atoms,
+                                              const double *nl_atoms, const double *fixed, const double *lo, const double *hi, int n_classes,
+                                              const int32_t *labels, const double *log_prior, double noise_sd, int marginal_amplitudes,
+                                              double *mean, double *sd, int32_t *map_atom, double *map_p, double *log_evidence, double *ess,
+                                              double *clipped_mass, int mem, int device, void *stream) {
+    if (!o) return set_error(PNX_ERR_INVALID, "opts is NULL");
+    pnx_curvefit_opts c = *o;  // as grid start: jac_mode and the tolerances are not looked at
+    c.jac_mode = PNX_JAC_ANALYTIC;
+    c.ftol = c.xtol = c.gtol = 0.0;
+    int rc = check_curvefit_opts(&c);
+    if (rc) return rc;
+    VarproLayout L;
+    VarproPosteriorHost H;
+    GridClassHost K;
+    if ((rc = varpro_class_posterior_check_args(&c, n_vox, b, y, n_atoms, nl_atoms, fixed, lo, hi, n_classes, labels, log_prior, noise_sd,
+                                                marginal_amplitudes, mean, mem, &L, &H, &K)))
+        return rc;
+    if (n_vox == 0) return PNX_OK;
+    DeviceInfo *dev;
+    if ((rc = use_device(device, &dev))) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    AsyncBuf dict_buf, post_buf, table_buf;  // built once per call, stream-ordered, freed behind the work that reads them
+    VarproDict D;
+    VarproPosterior P;
+    VarproClassTable T;
+    if ((rc = dict_buf.alloc(varpro_dict_bytes(c.n_free, L.n_nl, L.k, n_atoms, c.n_b), st))) return rc;
+    if ((rc = post_buf.alloc(varpro_posterior_bytes(L.n_nl, n_atoms), st))) return rc;
+    if ((rc = table_buf.alloc(varpro_class_table_bytes(n_classes, n_atoms), st))) return rc;
+    if ((rc = varpro_dict_build(&c, L, b, n_atoms, nl_atoms, fixed, lo, dict_buf.p, &D, st))) return rc;  // no fallback: lo is not read back
+    // without a prior the posterior's lw is the Occam term alone (0 with the profile weight), theta is centred about H.centre
+    if ((rc = varpro_posterior_prepare(D, H, nullptr, noise_sd, marginal_amplitudes, post_buf.p, &P, st))) return rc;
+    if ((rc = varpro_class_table_prepare(D, P, K, n_classes, log_prior, table_buf.p, &T, st))) return rc;
+    if (mem == PNX_MEM_DEVICE)
+        return varpro_class_posterior_device(D, P, T, n_vox, y, labels, mean, sd, map_atom, map_p, log_evidence, ess, clipped_mass, dev->cus, st);
+    PNX_HIP(hipStreamSynchronize(st));  // the ring's streams read the dictionary: complete before the first chunk starts
+    enum { VC_Y, VC_LAB, VC_MEAN, VC_SD, VC_ATOM, VC_MAPP, VC_LOGEV, VC_ESS, VC_CM };
+    ArrayTable A;
+    A.add(y, sizeof(double), c.n_b, false);
+    A.add(labels, sizeof(int32_t), 1, false);
+    A.add(mean, sizeof(double), c.n_free, true).pmajor = true;
+    A.add(sd, sizeof(double), c.n_free, true).pmajor = true;
+    A.add(map_atom, sizeof(int32_t), 1, true);
+    A.add(map_p, sizeof(double), c.n_free, true).pmajor = true;
+    A.add(log_evidence, sizeof(double), 1, true);
+    A.add(ess, sizeof(double), 1, true);
+    A.add(clipped_mass, sizeof(double), 1, true);
+    return ring_call(A, (size_t)n_vox, 3 << 18, device, st, [&](size_t n, const DevSet &S, hipStream_t s) {
+        return varpro_class_posterior_device(D, P, T, (int64_t)n, S.d(VC_Y), (const int32_t *)S.dev[VC_LAB], S.d(VC_MEAN), S.d(VC_SD),
+                                             (int32_t *)S.dev[VC_ATOM], S.d(VC_MAPP), S.d(VC_LOGEV), S.d(VC_ESS), S.d(VC_CM), dev->cus, s);
+    });
+}
+
+int pnx_curvefit_varpro_prior_em_classes_f64(const pnx_curvefit_opts *o, int64_t n_vox, const double *b, const double *y, int n_atoms,
+                                             const double *nl_atoms, const double *fixed, const double *lo, const double *hi, int n_classes,
+                                             const int32_t *labels, const double *log_prior, double noise_sd, int marginal_amplitudes,
+                                             int n_iter, double pseudo_count, double rel_tol, double *log_prior_out, double *loglik,
+                                             double *loglik_class, int *n_iter_done, int64_t *n_eff, int mem, int device, void *stream) {
+    if (!o) return set_error(PNX_ERR_INVALID, "opts is NULL");
+    pnx_curvefit_opts c = *o;  // as grid start: jac_mode and the tolerances are not looked at
+    c.jac_mode = PNX_JAC_ANALYTIC;
+    c.ftol = c.xtol = c.gtol = 0.0;
+    int rc = check_curvefit_opts(&c);
+    if (rc) return rc;
+    VarproLayout L;
+    VarproPosteriorHost H;
+    GridClassHost K;
+    if ((rc = varpro_class_prior_check_args(&c, n_vox, b, y, n_atoms, nl_atoms, fixed, lo, hi, n_classes, labels, log_prior, noise_sd,
+                                            marginal_amplitudes, n_iter, pseudo_count, rel_tol, log_prior_out, mem, &L, &H, &K)))
+        return rc;
+    grid_class_start(n_classes, n_atoms, log_prior, K, log_prior_out);  // the start, every row normalised; n_adm needs occ: on the device
+    for (int cl = 0; cl < n_classes; ++cl) K.norm[cl] = 0.0;           // and so is the table every pass reads
+    if (loglik) loglik[0] = 0.0;
+    if (loglik_class)
+        for (int cl = 0; cl < n_classes; ++cl) loglik_class[cl] = 0.0;
+    if (n_vox == 0) {
+        grid_class_report(n_iter, 0, n_classes, nullptr, loglik, loglik_class, n_iter_done, n_eff);
+        return PNX_OK;
+    }
+    DeviceInfo *dev;
+    if ((rc = use_device(device, &dev))) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    AsyncBuf dict_buf, post_buf, table_buf, work_buf, y_buf, lab_buf;  // stream-ordered, freed behind the work that reads them
+    VarproDict D;
+    VarproPosterior P;
+    VarproClassTable T;
+    VarproClassWork W;
+    if ((rc = dict_buf.alloc(varpro_dict_bytes(c.n_free, L.n_nl, L.k, n_atoms, c.n_b), st))) return rc;
+    if ((rc = post_buf.alloc(varpro_posterior_bytes(L.n_nl, n_atoms), st))) return rc;
+    if ((rc = table_buf.alloc(varpro_class_table_bytes(n_classes, n_atoms), st))) return rc;
+    if ((rc = work_buf.alloc(varpro_class_prior_bytes(n_vox, n_atoms, n_classes, dev->cus), st))) return rc;
+    if (mem == PNX_MEM_HOST) {  // every pass of every iteration reads the same signals and labels: one upload, kept for the call
+        const size_t bytes = (size_t)n_vox * c.n_b * sizeof(double), lbytes = (size_t)n_vox * sizeof(int32_t);
+        if (y_buf.alloc(bytes, st) != PNX_OK || lab_buf.alloc(lbytes, st) != PNX_OK)
+            return set_error(PNX_ERR_NOMEM, "varpro prior: no device memory for the %zu bytes of y and labels (%lld voxels x %d), which stay "
+                                            "resident for all iterations: learn the prior from a sub-sample of the voxels",
+                             bytes + lbytes, (long long)n_vox, c.n_b);
+        if ((rc = pnx_upload(y_buf.p, y, (int64_t)bytes, device, st, 0))) return rc;
+        if ((rc = pnx_upload(lab_buf.p, labels, (int64_t)lbytes, device, st, 0))) return rc;
+        y = (const double *)y_buf.p;
+        labels = (const int32_t *)lab_buf.p;
+    }
+    if ((rc = varpro_dict_build(&c, L, b, n_atoms, nl_atoms, fixed, lo, dict_buf.p, &D, st))) return rc;  // no fallback: lo is not read back
+    if ((rc = varpro_posterior_prepare(D, H, nullptr, noise_sd, marginal_amplitudes, post_buf.p, &P, st))) return rc;
+    if ((rc = varpro_class_table_prepare(D, P, K, n_classes, log_prior_out, table_buf.p, &T, st))) return rc;
+    varpro_class_prior_carve(n_vox, n_atoms, n_classes, dev->cus, work_buf.p, &W);
+    std::vector<double> trace((size_t)n_iter + 1, 0.0), trace_class(((size_t)n_iter + 1) * n_classes, 0.0);
+    VarproClassStats stats;
+    memset(&stats, 0, sizeof(stats));
+    int done = 0;
+    for (int t = 0;; ++t) {  // trace[t]: the log-likelihood under the table before update t, the returned table's at t = done
+        if ((rc = varpro_class_prior_normalise(D, P, T, n_vox, y, labels, W, st))) return rc;
+        PNX_HIP(hipMemcpyAsync(&stats, W.stats, sizeof(stats), hipMemcpyDeviceToHost, st));
+        PNX_HIP(hipStreamSynchronize(st));
+        trace[t] = stats.loglik;
+        long long total = 0;
+        for (int cl = 0; cl < n_classes; ++cl) {
+            trace_class[(size_t)t * n_classes + cl] = stats.loglik_class[cl];
+            total += stats.n_finite[cl];
+        }
+        done = t;
+        if (total == 0 || t == n_iter || grid_prior_converged(trace.data(), t, rel_tol)) break;
+        if ((rc = varpro_class_prior_update(D, P, T, n_vox, y, labels, W, pseudo_count, st))) return rc;
+    }
+    PNX_HIP(hipMemcpy2DAsync(log_prior_out, (size_t)n_atoms * sizeof(double), T.lp, (size_t)D.gp * sizeof(double),
+                             (size_t)n_atoms * sizeof(double), (size_t)n_classes, hipMemcpyDeviceToHost, st));
+    PNX_HIP(hipStreamSynchronize(st));
+    for (int t = 0; t <= done; ++t) {
+        if (loglik) loglik[t] = trace[t];
+        if (loglik_class)
+            for (int cl = 0; cl < n_classes; ++cl) loglik_class[(size_t)t * n_classes + cl] = trace_class[(size_t)t * n_classes + cl];
+    }
+    int64_t finite[kGridMaxClasses];
+    for (int cl = 0; cl < n_classes; ++cl) finite[cl] = stats.n_finite[cl];
+    grid_class_report(n_iter, done, n_classes, finite, loglik, loglik_class, n_iter_done, n_eff);
     return PNX_OK;
 }
 

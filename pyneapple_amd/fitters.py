@@ -385,7 +385,7 @@ class HipPixelWiseFitter(HipFitterBase):
                     raise ValueError(f"fixed_param_maps[{name!r}] must have shape {spatial}, got {vol.shape}.")
                 pixel_fixed[name] = np.ascontiguousarray(vol[mask], dtype=np.float64)
         self._pixel_fixed = pixel_fixed
-        # a solver with one prior row per segmentation label (HipBayesGridSolver: per_label, or a 2-D log_prior) takes the label values
+        # a solver with one prior row per segmentation label (HipBayesGridSolver, HipBayesVarProSolver: per_label, or a 2-D log_prior) takes the label values
         if getattr(self.solver, "needs_labels", False) and "labels" not in fit_kwargs:
             if segmentation is None:
                 raise ValueError(f"{type(self.solver).__name__} asks for labels (a per-label prior): pass a segmentation")

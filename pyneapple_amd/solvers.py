@@ -1262,7 +1262,9 @@ class HipBayesVarProSolver(RefBaseSolver):
             bounds is the box the amplitudes are clipped into; lo of S0 >= 0.
         noise_sd: None / 0 (default) marginalises the noise scale under a Jeffreys prior; > 0 is a known Gaussian noise sd in the
             units of the (sigma-weighted) signal.
-        log_prior: None (uniform) or (n_atoms,) log weights in the order of the atoms; -inf excludes an atom.
+        log_prior: None (uniform) or (n_atoms,) log weights in the order of the atoms; -inf excludes an atom.  (C, n_atoms), 2 <= C
+            <= 16: one row per label, label c judged under row c (pnx_curvefit_varpro_posterior_classes_f64); `fit` then needs
+            labels, and any other label is background (NaN outputs).
         marginal_amplitudes: True (default) weighs an atom by the marginal over its amplitudes under a flat prior (the Occam term
             -0.5 log det N); False by the profile over them.
         sigma: None, a scalar or (n_b,), as HipCurveFitSolver's.  device: HIP device index.
@@ -1283,7 +1285,12 @@ class HipBayesVarProSolver(RefBaseSolver):
             HipBayesGridSolver's option, the same rules and messages): `fit` first learns the prior over the rate atoms from the
             volume by EM (pnx_curvefit_varpro_prior_em_f64; `log_prior` is its start, the Occam term of `marginal_amplitudes` stays
             in the likelihood) on ydata[::ceil(n / max_voxels)], then reports the posterior -- and the marginals -- under the
-            learned table.  It needs many voxels: a few dozen over-fit.
+            learned table.  It needs many voxels: a few dozen over-fit.  With "per_label": True (HipBayesGridSolver's option, the
+            same TOML table) `fit(..., labels=...)` learns one table per distinct non-negative label, rows in ascending label order
+            (pnx_curvefit_varpro_prior_em_classes_f64; at most 16 labels, a negative label is background), and reports the
+            posterior of every voxel under its label's table; the diagnostics are then the grid solver's per-label set:
+            "log_prior" (C, n_atoms), "prior_loglik" (n_iter + 1, C), "prior_loglik_total", "prior_n_eff" (C,), "prior_labels".
+            Refused by name: marginals together with labels, max_voxels with per_label, a 2-D log_prior without per_label.
     After fit: params_ = the posterior mean keyed by the model's names; diagnostics_ {"posterior_sd", "map" (dicts name ->
     (n_pixels,)), "map_atom", "log_evidence", "ess", "clipped_mass", "n_pixels"}, with marginals also {"marginal" {name: (n_bins,
     n_pixels)}, "marginal_values" {name: (n_bins,)}, "quantiles" {name: (n_q, n_pixels)}, "quantile_probs", "geo_mean" {name:
@@ -1302,7 +1309,15 @@ class HipBayesVarProSolver(RefBaseSolver):
         RefBaseSolver.__init__(self, model=model, max_iter=max_iter, tol=tol, verbose=bool(ignored_reference_kwargs.pop("verbose", False)))
         self._kernel_model = kernel_model_key(model)
         self._kernel_t1 = kernel_t1(model)
+        per_label = False
+        if isinstance(empirical_prior, dict) and "per_label" in empirical_prior:  # the grid solver's option, taken out here: the
+            empirical_prior = dict(empirical_prior)                               # shared classmethod knows the four others
+            per_label = empirical_prior.pop("per_label")
+            if not isinstance(per_label, (bool, np.bool_)):
+                raise ValueError(f"empirical_prior per_label must be a bool, got {per_label!r}")
         self.empirical_prior = self._empirical_prior_options(empirical_prior)
+        if per_label:
+            self.empirical_prior["per_label"] = True
         self.marginals = self._marginals_options(marginals)
         if _io_dtype(io_dtype) is not np.float64 or precision != "float64":
             raise ValueError("HipBayesVarProSolver is built for precision='float64' and io_dtype='float64': the posterior reads and "
@@ -1322,12 +1337,16 @@ class HipBayesVarProSolver(RefBaseSolver):
             raise ValueError(f"noise_sd must be None / 0 (marginalised) or a finite positive standard deviation, got {noise_sd!r}")
         self.log_prior = None
         if log_prior is not None:
-            lp = np.ascontiguousarray(log_prior, np.float64).reshape(-1)
-            if lp.shape != (self._nl_atoms.shape[1],):
+            lp = np.ascontiguousarray(log_prior, np.float64)
+            if lp.ndim == 2 and lp.shape[1] == self._nl_atoms.shape[1] and lp.shape[0] > api.GRID_MAX_CLASSES:
+                raise ValueError(f"log_prior has {lp.shape[0]} rows: at most {api.GRID_MAX_CLASSES} classes (labels) are built")
+            if not (lp.ndim == 2 and lp.shape[0] >= 2 and lp.shape[1] == self._nl_atoms.shape[1]):  # (1, n_atoms) is the one table, as before
+                lp = lp.reshape(-1)
+            if lp.ndim == 1 and lp.shape != (self._nl_atoms.shape[1],):
                 raise ValueError(f"log_prior has {lp.size} entries for {self._nl_atoms.shape[1]} atoms (one per atom, in the order of the "
                                  "atoms)")
-            if np.isnan(lp).any() or (lp == np.inf).any() or not np.isfinite(lp).any():
-                raise ValueError("log_prior entries must be finite or -inf, at least one of them finite")
+            if np.isnan(lp).any() or (lp == np.inf).any() or not np.isfinite(lp).any(axis=-1).all():
+                raise ValueError("log_prior entries must be finite or -inf, at least one of them finite" + (" in every row" if lp.ndim == 2 else ""))
             self.log_prior = lp
         self.marginal_amplitudes = bool(marginal_amplitudes)
         self.sigma = None
@@ -1341,8 +1360,53 @@ class HipBayesVarProSolver(RefBaseSolver):
         self.device = int(device)
         self.io_dtype = np.float64
         self.solver_kwargs = ignored_reference_kwargs
+        if self.needs_labels and self.marginals:
+            raise ValueError("HipBayesVarProSolver: marginals are not built with per-label priors (a 2-D log_prior or empirical_prior "
+                             "per_label): pnx_curvefit_varpro_marginals_f64 takes one prior table")
+        if per_label and self.empirical_prior["max_voxels"]:
+            raise ValueError("empirical_prior max_voxels is not built with per_label: every label learns from all of its voxels")
+        if self.empirical_prior and not per_label and self.log_prior is not None and self.log_prior.ndim == 2:
+            raise ValueError("empirical_prior with a 2-D log_prior needs per_label: a single learned table has no single row to start from")
 
-    def fit(self, xdata: np.ndarray, ydata: np.ndarray, pixel_fixed_params=None, **fit_kwargs) -> "HipBayesVarProSolver":
+    @property
+    def needs_labels(self) -> bool:
+        """True when `fit` needs `labels`: a 2-D log_prior, or empirical_prior with per_label."""
+        return bool((self.log_prior is not None and self.log_prior.ndim == 2) or (self.empirical_prior and self.empirical_prior.get("per_label")))
+
+    label_rows = staticmethod(HipBayesGridSolver.label_rows)  # one mapping from label values to rows for both solvers
+
+    def _fit_labelled(self, xdata, ydata, labels, lo, hi, common):
+        """(posterior result, learned or None) under one prior row per label: HipBayesGridSolver._fit_labelled over the rate atoms."""
+        n_pixels = ydata.shape[0]
+        if labels is None:
+            raise ValueError("HipBayesVarProSolver: labels (n_pixels,) is required with a 2-D log_prior or empirical_prior per_label")
+        per_label = bool(self.empirical_prior and self.empirical_prior.get("per_label"))
+        table = self.log_prior
+        if per_label:
+            values, rows = self.label_rows(labels, n_pixels)
+            n_classes = max(int(values.size), 1)
+            if table is not None and table.ndim == 2 and table.shape[0] != n_classes:
+                raise ValueError(f"log_prior has {table.shape[0]} rows for the {n_classes} distinct labels of this call")
+            if table is not None and table.ndim == 1:
+                table = np.ascontiguousarray(np.broadcast_to(table, (n_classes, table.size)))
+        else:  # the caller's table: label c is row c, anything else is background
+            n_classes = table.shape[0]
+            lab = np.asarray(labels)
+            if lab.shape != (n_pixels,) or lab.dtype.kind not in "iuf":
+                raise ValueError(f"labels must be {n_pixels} integers (one per pixel), got shape {lab.shape} and dtype {lab.dtype}")
+            rows = np.where((lab >= 0) & (lab < n_classes) & (lab == np.floor(lab)), lab, -1).astype(np.int32)
+        learned = None
+        if per_label:
+            ep = self.empirical_prior
+            learned = api.varpro_prior_em_classes(self._kernel_model, xdata, ydata, self._nl_atoms, lo, hi, rows, n_classes, log_prior=table,
+                                                  n_iter=ep["n_iter"], pseudo_count=ep["pseudo_count"], rel_tol=ep["rel_tol"], **common)
+            learned["n_voxels"] = n_pixels
+            learned["labels"] = values
+            table = learned["log_prior"]
+        res = api.varpro_posterior_classes(self._kernel_model, xdata, ydata, self._nl_atoms, lo, hi, rows, n_classes, log_prior=table, **common)
+        return res, learned
+
+    def fit(self, xdata: np.ndarray, ydata: np.ndarray, pixel_fixed_params=None, labels=None, **fit_kwargs) -> "HipBayesVarProSolver":
         if pixel_fixed_params:
             raise ValueError("HipBayesVarProSolver is not built with per-pixel fixed parameters (pixel_fixed_params): the dictionary "
                              "would differ from voxel to voxel")
@@ -1363,7 +1427,11 @@ class HipBayesVarProSolver(RefBaseSolver):
         lo = np.array([self.bounds[n][0] for n in names], float)
         hi = np.array([self.bounds[n][1] for n in names], float)
         log_prior, learned = self.log_prior, None
-        if self.empirical_prior:
+        if self.needs_labels:
+            res, learned = self._fit_labelled(xdata, ydata, labels, lo, hi,
+                                              dict(noise_sd=self.noise_sd, marginal_amplitudes=self.marginal_amplitudes, fixed_idx=fixed_idx,
+                                                   fixed_vals=fixed_vals, sigma=self.sigma, device=self.device, **self._kernel_t1))
+        elif self.empirical_prior:
             ep = self.empirical_prior
             step = 1 if ep["max_voxels"] is None else -(-n_pixels // ep["max_voxels"])
             sample = ydata[::step]
@@ -1373,9 +1441,10 @@ class HipBayesVarProSolver(RefBaseSolver):
                                           sigma=self.sigma, device=self.device, **self._kernel_t1)
             learned["n_voxels"] = sample.shape[0]
             log_prior = learned["log_prior"]
-        res = api.varpro_posterior(self._kernel_model, xdata, ydata, self._nl_atoms, lo, hi, log_prior=log_prior, noise_sd=self.noise_sd,
-                                   marginal_amplitudes=self.marginal_amplitudes, fixed_idx=fixed_idx, fixed_vals=fixed_vals, sigma=self.sigma,
-                                   device=self.device, **self._kernel_t1)
+        if not self.needs_labels:
+            res = api.varpro_posterior(self._kernel_model, xdata, ydata, self._nl_atoms, lo, hi, log_prior=log_prior, noise_sd=self.noise_sd,
+                                       marginal_amplitudes=self.marginal_amplitudes, fixed_idx=fixed_idx, fixed_vals=fixed_vals,
+                                       sigma=self.sigma, device=self.device, **self._kernel_t1)
         mean, atom = res["mean"], res["map_atom"]
         self.pixel_results_ = PixelResultsView(mean.T, None, atom >= 0,
                                                lambda i, a=atom: None if a[i] >= 0 else _BAYES_MESSAGES[-2])
@@ -1387,6 +1456,9 @@ class HipBayesVarProSolver(RefBaseSolver):
         if learned is not None:
             self.diagnostics_.update({"log_prior": learned["log_prior"], "prior_loglik": learned["loglik"], "prior_n_iter": learned["n_iter"],
                                       "prior_n_voxels": learned["n_voxels"]})
+            if "labels" in learned:
+                self.diagnostics_.update({"prior_loglik": learned["loglik_class"], "prior_loglik_total": learned["loglik"],
+                                          "prior_n_eff": learned["n_eff"], "prior_labels": [int(v) for v in learned["labels"]]})
         if self.marginals:
             mg = api.varpro_marginals(self._kernel_model, xdata, ydata, self._nl_atoms, lo, hi, log_prior=log_prior, noise_sd=self.noise_sd,
                                       marginal_amplitudes=self.marginal_amplitudes, quantiles=self.marginals["quantiles"], fixed_idx=fixed_idx,
