@@ -527,6 +527,88 @@ PNX_API int pnx_curvefit_grid_prior_em_classes_f64(const pnx_curvefit_opts *opts
                                    double *loglik, double *loglik_class, int *n_iter_done, int64_t *n_eff, int mem, int device,
                                    void *stream);
 /*
+ * A neighbourhood (MRF) prior for pnx_curvefit_grid_posterior_f64 by coloured mean-field sweeps: three calls,
+ * the gather, one colour update, and the driver that composes them.  Over a symmetric neighbour graph of the voxels and with a
+ * precision lambda_k >= 0 per free parameter the prior is
+ *   p(theta) ~ prod_v pi(theta_v) exp(-1/2 sum_{edges (u,v)} sum_k lambda_k (theta_vk - theta_uk)^2),
+ * and mean field with q = prod_v q_v over the atoms updates one voxel, its neighbours held fixed, by
+ *   l_g(v) = [pnx_curvefit_grid_posterior_f64's l_g(v), term for term] + sum_k thetac_kg q_vk - 1/2 n_v r_g
+ *   thetac_kg = atoms[k, g] - centre_k     centre_k: the posterior's own centre, min + (max - min) / 2 over the admissible atoms,
+ *                                          0 for a projected S0 row
+ *   q_vk = lambda_k sum_{u in N(v), present} (mean[k, u] - centre_k)       summed in slot order, then one multiply
+ *   n_v = the number of present neighbours;  r_g = sum_k lambda_k thetac_kg^2   (host, fp64, k ascending)
+ * A neighbour is present when its slot holds an index >= 0 and mean[0, u] is finite; a voxel with a non-finite signal is NaN in
+ * every output, as in the posterior, and so counts for nobody.  The neighbours' variances are constant in theta_v and drop out.
+ * The centred form matters: uncentred, a narrow axis far from zero cancels catastrophically.
+ *
+ * pnx_curvefit_grid_neighbour_field_f64: the gather.  One lane per voxel of [first, first + count).
+ *   n_vox in [0, 2^31 - 1]; n_free in [1, 8]; n_nb in [1, 8];
+ *   neighbours (n_vox, n_nb) int32, -1 where a slot is empty; mean (n_free, n_vox): host|device as `mem`;
+ *   centre, precision (n_free,) host: finite, precision >= 0;
+ *   field_q (n_free, n_vox), field_n (n_vox) int32: out, host|device as `mem`, written for the range only;
+ *   flag: an index outside [-1, n_vox) is never dereferenced (the slot counts as empty); it is an argument error.
+ *     PNX_MEM_DEVICE only enqueues and cannot report: flag is a device int32 or NULL, which the caller sets to INT32_MAX and which
+ *     receives (integer atomicMin) the lowest voxel of the range with such an index -- the call that synchronises reports it, as
+ *     pnx_curvefit_grid_posterior_mrf_f64 does.  PNX_MEM_HOST uploads the table and the means, synchronises `stream` and returns
+ *     PNX_ERR_INVALID naming that voxel; flag is then a host int32 or NULL.
+ */
+PNX_API int pnx_curvefit_grid_neighbour_field_f64(int64_t n_vox, int64_t first, int64_t count, int n_free, int n_nb,
+                                   const int32_t *neighbours, const double *mean, const double *centre, const double *precision,
+                                   double *field_q, int32_t *field_n, int32_t *flag, int mem, int device, void *stream);
+/*
+ * pnx_curvefit_grid_posterior_field_f64: one colour update.  Every argument of pnx_curvefit_grid_posterior_f64, its weighting,
+ * refusals and outputs, for the voxels [first, first + count) under the l_g above, written IN PLACE into the full-length output
+ * arrays (n_free, n_vox) / (n_vox); the other voxels' entries are not touched.
+ *   field_q (n_free, n_vox), field_n (n_vox) int32: device, as the gather wrote them (only the range is read);
+ *   precision (n_free,) host: finite, >= 0, and 0 on a projected S0 row, which has no grid value (PNX_ERR_INVALID otherwise);
+ *   delta_max: device scalar or NULL; receives max over { k: precision_k > 0 and range_k > 0; v in the range, finite } of
+ *     |mean_new[k, v] - mean_old[k, v]| / range_k,  range_k = max_g theta_kg - min_g theta_kg over the admissible atoms.  Each lane
+ *     reads its old mean before it overwrites it; the maximum is reduced per block and then over the blocks by a small kernel:
+ *     no floating-point atomics.  0 for an empty range.
+ * With field_q = 0 and field_n = 0 the added terms are exactly +0.0 and the call returns the bytes of
+ * pnx_curvefit_grid_posterior_f64 for those voxels; with every precision 0 the field is not read and the same holds.
+ * log_evidence is L_v - log sum_g exp(log_prior_g) with the field inside L_v: a LOCAL NORMALISER of the voxel's update given its
+ * neighbours, not a model evidence -- do not sum it over voxels or compare it between models.
+ * A pair at log_prior = -inf is skipped before any arithmetic.  The field product runs on the fp64 matrix cores in an accumulator
+ * of its own (adding it to y . s would be wrong outside known noise without projection).  PNX_MEM_DEVICE only (PNX_ERR_INVALID
+ * otherwise); the call only enqueues.
+ */
+PNX_API int pnx_curvefit_grid_posterior_field_f64(const pnx_curvefit_opts *opts, int64_t n_vox, const double *b, const double *y,
+                                   int n_atoms, const double *atoms, const double *fixed, const double *lo, const double *hi,
+                                   int project_amplitude, const double *log_prior, double noise_sd, int64_t first, int64_t count,
+                                   const double *field_q, const int32_t *field_n, const double *precision, double *mean, double *sd,
+                                   int32_t *map_atom, double *map_p, double *log_evidence, double *ess, double *delta_max, int mem,
+                                   int device, void *stream);
+/*
+ * pnx_curvefit_grid_posterior_mrf_f64: the driver.  The arguments and outputs of pnx_curvefit_grid_posterior_f64, and
+ *   n_nb in [1, 8]; neighbours (n_vox, n_nb) int32, host|device as `mem`; the graph must be symmetric (not checked);
+ *   n_colours in [1, 8]; colour_start (n_colours + 1,) int64 host, ascending from 0 to n_vox: the voxels of colour c are the
+ *     contiguous range [colour_start[c], colour_start[c+1]) -- the caller sorts the voxels by colour; a colour may be empty;
+ *   precision (n_free,) host; n_sweeps in [0, 100]; tol finite, >= 0;
+ *   delta (n_sweeps,) host or NULL; n_sweeps_done host or NULL.
+ * Sweep 0 is the plain posterior on all voxels (the bytes of pnx_curvefit_grid_posterior_f64).  Sweep s = 1 .. n_sweeps runs, for
+ * each colour in order, the gather and then the field posterior on that colour's range.  No voxel of a colour has a neighbour in
+ * it, so colour after colour is coordinate ascent on the variational free energy, which never decreases; a simultaneous update
+ * of all voxels would not be monotone.  delta[s-1] is the maximum of delta_max over the sweep's colour updates; the call stops
+ * after sweep s when delta[s-1] <= tol (tol = 0 runs all sweeps, without a host round trip per sweep); entries of delta past
+ * n_sweeps_done are NaN.  log_evidence is the local normaliser described above.
+ * A small kernel verifies the table before any sweep: an index outside [-1, n_vox), or a neighbour of a voxel inside the voxel's
+ * own colour range, returns PNX_ERR_INVALID and names the first offending voxel.  Refused before any device work: everything the
+ * posterior refuses; n_nb, n_colours, n_sweeps or tol out of range; colour_start not ascending from 0 to n_vox; a negative or
+ * non-finite precision; a positive precision on a projected S0 row.
+ * Every sum of a voxel depends on the order of the atoms and of its slots only: two calls return the same bytes, PNX_MEM_HOST or
+ * PNX_MEM_DEVICE, and the call returns the bytes of the same sequence composed from the three calls above.
+ *   PNX_MEM_HOST: y and neighbours are uploaded once (pnx_upload's path) and the outputs come back from one stream-ordered
+ *   buffer, as pnx_curvefit_grid_prior_em_f64 stages its signals -- no chunk ring; PNX_ERR_NOMEM names the size.  For both `mem`
+ *   values the call SYNCHRONISES `stream` before it returns.
+ */
+PNX_API int pnx_curvefit_grid_posterior_mrf_f64(const pnx_curvefit_opts *opts, int64_t n_vox, const double *b, const double *y,
+                                   int n_atoms, const double *atoms, const double *fixed, const double *lo, const double *hi,
+                                   int project_amplitude, const double *log_prior, double noise_sd, int n_nb, const int32_t *neighbours,
+                                   int n_colours, const int64_t *colour_start, const double *precision, int n_sweeps, double tol,
+                                   double *mean, double *sd, int32_t *map_atom, double *map_p, double *log_evidence, double *ess,
+                                   double *delta, int *n_sweeps_done, int mem, int device, void *stream);
+/*
  * Marginal posterior of every free parameter over the dictionary, and credible-interval quantiles from it.  The
  * arguments up to noise_sd, the weighting, the dictionary, a_g(v), c_g(v), tol_v, l_g and every refusal are
  * pnx_curvefit_grid_posterior_f64's.  The atoms sit on a grid: along free parameter k every atom holds one of n_bins[k] values.

@@ -40,6 +40,8 @@ SOURCE_GROUPS = {
                    "pnx_grid_posterior_args.hpp", "pnx_grid.hpp", "pnx_grid_args.hpp"],
     "grid_class": ["pnx_grid_class.hip", "pnx_grid_class.hpp", "pnx_grid_class_args.hpp", "pnx_grid_prior_args.hpp", "pnx_grid_posterior.hpp",
                    "pnx_grid_posterior_args.hpp", "pnx_grid.hpp", "pnx_grid_args.hpp"],
+    "grid_mrf": ["pnx_grid_mrf.hip", "pnx_grid_mrf.hpp", "pnx_grid_mrf_args.hpp", "pnx_grid_posterior.hpp", "pnx_grid_posterior_args.hpp",
+                 "pnx_grid.hpp", "pnx_grid_args.hpp"],
     "grid_marginal": ["pnx_grid_marginal.hip", "pnx_grid_marginal.hpp", "pnx_grid_marginal_args.hpp", "pnx_grid_prior.hpp",
                       "pnx_grid_prior_args.hpp", "pnx_grid_posterior.hpp", "pnx_grid_posterior_args.hpp", "pnx_grid.hpp", "pnx_grid_args.hpp"],
     "varpro": ["pnx_varpro.hip", "pnx_varpro.hpp", "pnx_varpro_args.hpp", "pnx_grid_args.hpp", "pnx_predict.hpp"],
@@ -87,6 +89,7 @@ def _units():
              ("pnx_simplex.o", "pnx_simplex.hip", []), ("pnx_grid.o", "pnx_grid.hip", []),
              ("pnx_grid_posterior.o", "pnx_grid_posterior.hip", []), ("pnx_grid_prior.o", "pnx_grid_prior.hip", []),
              ("pnx_grid_marginal.o", "pnx_grid_marginal.hip", []), ("pnx_grid_class.o", "pnx_grid_class.hip", []),
+             ("pnx_grid_mrf.o", "pnx_grid_mrf.hip", []),
              ("pnx_varpro.o", "pnx_varpro.hip", []),
              ("pnx_varpro_posterior.o", "pnx_varpro_posterior.hip", []),
              ("pnx_varpro_marginal.o", "pnx_varpro_marginal.hip", []),
@@ -139,12 +142,14 @@ def _stale(unit, force: bool) -> bool:
     elif src in ("pnx_varpro_marginal.hip", "pnx_varpro_prior.hip", "pnx_varpro_class.hip"):  # of the dictionary search's headers, the HIP-free argument halves only
         deps = [d for d in deps if os.path.basename(d).endswith("_args.hpp") or "pnx_grid" not in os.path.basename(d)]
     elif src not in ("pnx_api.hip", "pnx_grid.hip", "pnx_grid_posterior.hip", "pnx_grid_prior.hip", "pnx_grid_marginal.hip", "pnx_grid_class.hip",
-                     "pnx_varpro.hip"):
+                     "pnx_grid_mrf.hip", "pnx_varpro.hip"):
         deps = [d for d in deps if "pnx_grid" not in os.path.basename(d)]  # the dictionary search's headers: its units and the ABI's
     elif src == "pnx_varpro.hip":
         deps = [d for d in deps if os.path.basename(d) == "pnx_grid_args.hpp" or "pnx_grid" not in os.path.basename(d)]  # of those, the slab rule only
     elif src == "pnx_grid.hip":
         deps = [d for d in deps if "pnx_grid_posterior" not in os.path.basename(d)]  # the posterior's headers: its unit and the ABI's
+    if src not in ("pnx_api.hip", "pnx_grid_mrf.hip"):
+        deps = [d for d in deps if "pnx_grid_mrf" not in os.path.basename(d)]  # the neighbourhood prior's headers: its unit and the ABI's
     if src not in ("pnx_api.hip", "pnx_grid_class.hip", "pnx_varpro_class.hip"):
         deps = [d for d in deps if "pnx_grid_class" not in os.path.basename(d)]  # the per-label prior's headers: its unit and the ABI's
     if src not in ("pnx_api.hip", "pnx_grid_prior.hip", "pnx_grid_marginal.hip", "pnx_grid_class.hip", "pnx_varpro_marginal.hip",

@@ -33,6 +33,7 @@ ABI_SYMBOLS = [
     "pnx_loglinear_f64", "pnx_loglinear_f32", "pnx_peel_f64", "pnx_peel_f32",
     "pnx_curvefit_grid_posterior_classes_f64", "pnx_curvefit_grid_prior_em_classes_f64",
     "pnx_curvefit_varpro_posterior_classes_f64", "pnx_curvefit_varpro_prior_em_classes_f64",
+    "pnx_curvefit_grid_neighbour_field_f64", "pnx_curvefit_grid_posterior_field_f64", "pnx_curvefit_grid_posterior_mrf_f64",
 ]
 
 
@@ -138,6 +139,19 @@ def load():
     lib.pnx_curvefit_grid_prior_em_classes_f64.argtypes = [C.POINTER(CurvefitOpts), C.c_int64, dp, dp, C.c_int, dp, dp, dp, dp, C.c_int, C.c_int,
                                                            vp, dp, C.c_double, C.c_int, C.c_double, C.c_double, dp, dp, dp,
                                                            C.POINTER(C.c_int), vp, C.c_int, C.c_int, vp]
+    # the neighbourhood (MRF) prior: the gather; the posterior's arguments with first, count, field_q, field_n, precision in front of
+    # the outputs and delta_max behind them; the driver with n_nb, neighbours, n_colours, colour_start, precision, n_sweeps, tol
+    lib.pnx_curvefit_grid_neighbour_field_f64.restype = C.c_int
+    lib.pnx_curvefit_grid_neighbour_field_f64.argtypes = [C.c_int64, C.c_int64, C.c_int64, C.c_int, C.c_int, vp, dp, dp, dp, dp, vp, vp,
+                                                          C.c_int, C.c_int, vp]
+    lib.pnx_curvefit_grid_posterior_field_f64.restype = C.c_int
+    lib.pnx_curvefit_grid_posterior_field_f64.argtypes = [C.POINTER(CurvefitOpts), C.c_int64, dp, dp, C.c_int, dp, dp, dp, dp, C.c_int, dp,
+                                                          C.c_double, C.c_int64, C.c_int64, dp, vp, dp, dp, dp, vp, dp, dp, dp, dp, C.c_int,
+                                                          C.c_int, vp]
+    lib.pnx_curvefit_grid_posterior_mrf_f64.restype = C.c_int
+    lib.pnx_curvefit_grid_posterior_mrf_f64.argtypes = [C.POINTER(CurvefitOpts), C.c_int64, dp, dp, C.c_int, dp, dp, dp, dp, C.c_int, dp,
+                                                        C.c_double, C.c_int, vp, C.c_int, vp, dp, C.c_int, C.c_double, dp, dp, vp, dp, dp, dp,
+                                                        dp, C.POINTER(C.c_int), C.c_int, C.c_int, vp]
     # the posterior's inputs, n_bins, bin_of, bin_value, n_q, probs, marginal, quantile, log_evidence
     lib.pnx_curvefit_grid_marginals_f64.restype = C.c_int
     lib.pnx_curvefit_grid_marginals_f64.argtypes = [C.POINTER(CurvefitOpts), C.c_int64, dp, dp, C.c_int, dp, dp, dp, dp, C.c_int, dp, C.c_double,

@@ -560,6 +560,206 @@ def grid_prior_em_classes_device(opts, n_vox, b, y, atoms, fixed, lo, hi, projec
                                   pseudo_count, rel_tol, MEM_DEVICE, device, stream)
 
 
+GRID_MRF_MAX_NEIGHBOURS = 8  # kGridMrfMaxNeighbours, kGridMrfMaxColours, kGridMrfMaxSweeps of csrc/pnx_grid_mrf_args.hpp
+GRID_MRF_MAX_COLOURS = 8
+GRID_MRF_MAX_SWEEPS = 100
+_GRID_OFFSETS = {4: ((-1, 0, 0), (1, 0, 0), (0, -1, 0), (0, 1, 0)),
+                 8: ((-1, 0, 0), (1, 0, 0), (0, -1, 0), (0, 1, 0), (-1, -1, 0), (-1, 1, 0), (1, -1, 0), (1, 1, 0)),
+                 6: ((-1, 0, 0), (1, 0, 0), (0, -1, 0), (0, 1, 0), (0, 0, -1), (0, 0, 1))}
+
+
+def grid_mrf_slab_atoms(n_b, n_free):
+    """Atoms per LDS slab of the field posterior (grid_mrf_slab of csrc/pnx_grid_mrf_args.hpp): the widest multiple of 16, at most
+    256, whose dictionary rows, 4 + n_free values per atom (||s||^2, its inverse, log_prior, r_g, the centred parameter values) and
+    the 8 doubles of the delta reduction fit 64 KB."""
+    kpad, width = (int(n_b) + 3) & ~3, 16
+    for w in range(16, 257, 16):
+        if kpad * (w if w & 16 else w + 16) + (4 + int(n_free)) * w + 8 <= 8192:
+            width = w
+    return width
+
+
+def grid_neighbours(mask, connectivity=6):
+    """The neighbour table and the colours of the voxels of a boolean mask (2-D or 3-D), in mask-flattened (C) order -- the order
+    of image[mask].  connectivity 4 or 8: in-plane, per slice of the last spatial axis of a 3-D mask; 6: the 3-D axis neighbours.
+    Returns (neighbours (n, connectivity) int32 with -1 where a slot has no voxel inside the mask, colours (n,) int32): the
+    coordinate parities, (i + j [+ k]) & 1 for connectivity 4 and 6 (2 colours), (i & 1) + 2 (j & 1) for 8 (4 colours), so that no
+    voxel has a neighbour of its own colour.  Slot order: -x, +x, -y, +y, then the diagonals (8) or -z, +z (6)."""
+    if connectivity not in _GRID_OFFSETS:
+        raise ValueError(f"connectivity must be 4, 8 (in-plane) or 6 (3-D), got {connectivity!r}")
+    mask = np.asarray(mask).astype(bool)
+    if mask.ndim == 2:
+        mask = mask[:, :, None]
+    if mask.ndim != 3:
+        raise ValueError(f"mask must be a 2-D or 3-D array, got shape {mask.shape}")
+    n = int(mask.sum())
+    if n > np.iinfo(np.int32).max:
+        raise ValueError("the mask holds more voxels than an int32 index can address")
+    idx = np.full(tuple(s + 2 for s in mask.shape), -1, np.int32)  # one voxel of padding on every side: absent
+    inner = idx[1:-1, 1:-1, 1:-1]
+    inner[mask] = np.arange(n, dtype=np.int32)
+    offsets = _GRID_OFFSETS[connectivity]
+    nb = np.empty((n, len(offsets)), np.int32)
+    X, Y, Z = mask.shape
+    for s, (dx, dy, dz) in enumerate(offsets):
+        nb[:, s] = idx[1 + dx:1 + dx + X, 1 + dy:1 + dy + Y, 1 + dz:1 + dz + Z][mask]
+    i, j, k = np.nonzero(mask)
+    colours = ((i & 1) + 2 * (j & 1)) if connectivity == 8 else ((i + j + (k if connectivity == 6 else 0)) & 1)
+    return nb, colours.astype(np.int32)
+
+
+def grid_mrf_centre(atoms, log_prior=None, s0_row=-1):
+    """The centres the posterior accumulates its moments about (grid_posterior_check_args): min + (max - min) / 2 of every row of
+    atoms over the admissible atoms (log_prior > -inf), 0 for a projected S0 row.  What `grid_neighbour_field` takes as `centre`."""
+    atoms = np.asarray(atoms, np.float64)
+    adm = np.ones(atoms.shape[1], bool) if log_prior is None else np.asarray(log_prior, np.float64) > -np.inf
+    mn, mx = atoms[:, adm].min(axis=1), atoms[:, adm].max(axis=1)
+    centre = mn + 0.5 * (mx - mn)
+    if s0_row >= 0:
+        centre[s0_row] = 0.0
+    return centre
+
+
+def _mrf_precision(precision, n_free):
+    pr = np.ascontiguousarray(precision, np.float64)
+    if pr.shape != (n_free,):
+        raise ValueError(f"precision has shape {pr.shape}, expected ({n_free},): one value per free parameter")
+    return pr
+
+
+def grid_neighbour_field(neighbours, mean, centre, precision, *, first=0, count=None, out=None, flag=None, device=0, stream=None):
+    """The field of the neighbourhood prior for the voxels [first, first + count) (pnx_curvefit_grid_neighbour_field_f64; method:
+    include/pnx.h): field_q[k, v] = precision[k] * sum over the present neighbours u of (mean[k, u] - centre[k]), slots in order,
+    and field_n[v] their number.  neighbours (n_vox, n_nb) int32 and mean (n_free, n_vox) float64 are numpy arrays (staged; the
+    call synchronises and raises on an index outside [-1, n_vox)) or torch tensors on the device (enqueued; `flag`, a device int32
+    tensor preset to 2**31 - 1, receives the lowest offending voxel).  `out`: dict with "field_q" (n_free, n_vox) and "field_n"
+    (n_vox,) int32 -- required for tensors, optional for arrays; only the range is written.  Returns that dict."""
+    dev = _is_torch(mean)
+    if dev != _is_torch(neighbours):
+        raise ValueError("neighbours and mean must both be numpy arrays or both torch tensors")
+    n_free, n_vox = mean.shape
+    if tuple(neighbours.shape[:1]) != (n_vox,) or neighbours.ndim != 2:
+        raise ValueError(f"neighbours must have shape ({n_vox}, n_nb), got {tuple(neighbours.shape)}")
+    n_nb = int(neighbours.shape[1])
+    centre, pr = _mrf_precision(centre, n_free), _mrf_precision(precision, n_free)
+    count = n_vox - int(first) if count is None else int(count)
+    if dev:
+        if out is None or "field_q" not in out or "field_n" not in out:
+            raise ValueError("device tensors need out={'field_q': ..., 'field_n': ...}")
+        res = dict(field_q=out["field_q"], field_n=out["field_n"])
+    else:
+        _lib.require_device()
+        neighbours = np.ascontiguousarray(neighbours, np.int32)
+        mean = np.ascontiguousarray(mean, np.float64)
+        res = dict(field_q=_out(out, "field_q", (n_free, n_vox), np.float64), field_n=_out(out, "field_n", (n_vox,), np.int32))
+    check(load().pnx_curvefit_grid_neighbour_field_f64(n_vox, int(first), count, n_free, n_nb, ptr(neighbours), ptr(mean), ptr(centre), ptr(pr),
+                                                       ptr(res["field_q"]), ptr(res["field_n"]), ptr(flag), MEM_DEVICE if dev else MEM_HOST,
+                                                       int(device), stream))
+    return res
+
+
+def _mrf_host_inputs(who, model, b, n_b, atoms, lo, hi, fixed_idx, fixed_vals, sigma, t1_mode, tr, tm, log_prior):
+    b = np.ascontiguousarray(b, np.float64)
+    if b.shape != (n_b,):
+        raise ValueError(f"b has shape {b.shape}, expected ({n_b},)")
+    atoms, lo, hi = (np.ascontiguousarray(a, np.float64) for a in (atoms, lo, hi))
+    fv = None
+    if len(fixed_idx):
+        fv = np.ascontiguousarray(fixed_vals, np.float64)
+        if fv.ndim != 1:
+            raise ValueError(f"{who} takes shared fixed values (n_fixed,): per-voxel fixed maps are not built")
+    o = make_opts(model, n_b, fixed_idx, jac="analytic", t1_mode=t1_mode, tr=tr, tm=tm, sigma=sigma)
+    n = o.n_free
+    if atoms.ndim != 2 or atoms.shape[0] != n or lo.shape != (n,) or hi.shape != (n,):
+        raise ValueError(f"atoms must have shape ({n}, n_atoms), lo / hi ({n},)")
+    if fv is not None and fv.shape != (o.n_fixed,):
+        raise ValueError("fixed_vals has the wrong shape")
+    return o, b, atoms, fv, lo, hi, _posterior_log_prior(log_prior, atoms.shape[1])
+
+
+_POSTERIOR_KEYS = ("mean", "sd", "map_atom", "map_p", "log_evidence", "ess")
+
+
+def grid_posterior_field(model, b, y, atoms, lo, hi, field_q, field_n, precision, out, *, first=0, count=None, log_prior=None,
+                         noise_sd=0.0, fixed_idx=(), fixed_vals=None, sigma=None, project_amplitude=False, t1_mode=0, tr=0., tm=0.,
+                         delta_max=None, device=0, stream=None):
+    """One colour update of the neighbourhood prior (pnx_curvefit_grid_posterior_field_f64; method: include/pnx.h): the posterior
+    of the voxels [first, first + count) with the field inside l_g, written in place into the full-length tensors of `out`.
+    Device only, asynchronous (the caller synchronises): y (n_vox, n_b), field_q (n_free, n_vox), field_n (n_vox,) int32 and
+    out["mean"] (required, and read: delta compares against it), out["sd"], out["map_p"] (n_free, n_vox), out["map_atom"] (n_vox,)
+    int32, out["log_evidence"], out["ess"] (n_vox,) are torch tensors on the device; delta_max: a one-element float64 device tensor
+    or None.  The other arguments are `grid_posterior`'s host arrays and precision (n_free,).  Returns `out`."""
+    for name, t in (("y", y), ("field_q", field_q), ("field_n", field_n), ("out['mean']", (out or {}).get("mean"))):
+        if not _is_torch(t):
+            raise ValueError(f"grid_posterior_field works in place on device tensors: {name} is not a torch tensor")
+    n_vox, n_b = y.shape
+    o, b, atoms, fv, lo, hi, lp = _mrf_host_inputs("grid_posterior_field", model, b, n_b, atoms, lo, hi, fixed_idx, fixed_vals, sigma, t1_mode,
+                                                   tr, tm, log_prior)
+    pr = _mrf_precision(precision, o.n_free)
+    count = n_vox - int(first) if count is None else int(count)
+    check(load().pnx_curvefit_grid_posterior_field_f64(C.byref(o), int(n_vox), ptr(b), ptr(y), int(atoms.shape[1]), ptr(atoms), ptr(fv), ptr(lo),
+                                                       ptr(hi), int(bool(project_amplitude)), ptr(lp), float(noise_sd), int(first), count,
+                                                       ptr(field_q), ptr(field_n), ptr(pr), ptr(out["mean"]), ptr(out.get("sd")),
+                                                       ptr(out.get("map_atom")), ptr(out.get("map_p")), ptr(out.get("log_evidence")),
+                                                       ptr(out.get("ess")), ptr(delta_max), MEM_DEVICE, int(device), stream))
+    return out
+
+
+def grid_posterior_mrf(model, b, y, atoms, lo, hi, neighbours, colour_start, precision, *, n_sweeps=4, tol=0.0, log_prior=None, noise_sd=0.0,
+                       fixed_idx=(), fixed_vals=None, sigma=None, project_amplitude=False, t1_mode=0, tr=0., tm=0., device=0, out=None,
+                       stream=None):
+    """The grid posterior under a neighbourhood (MRF) prior by coloured mean-field sweeps (pnx_curvefit_grid_posterior_mrf_f64;
+    method: include/pnx.h).  The arguments of `grid_posterior`, and
+    neighbours (n_vox, n_nb <= 8) int32, -1 where a slot is empty, a symmetric graph; the voxels sorted by colour, with
+    colour_start (n_colours + 1,) the offsets of the colour ranges (0 .. n_vox; no voxel has a neighbour inside its own range);
+    precision (n_free,) >= 0, 0 on a projected S0; n_sweeps 0..100 (0: the plain posterior); tol >= 0: stop once a sweep moves no
+    mean by more than tol of its grid range (0 runs all sweeps).
+    y and neighbours are numpy arrays (staged once) or torch tensors on the device (read in place; `out` may hold preallocated
+    result tensors); the call synchronises either way.  Returns the dict of `grid_posterior` -- log_evidence is the local normaliser
+    of the last update, not a model evidence -- with "delta" (n_sweeps,) the largest relative move of a mean per sweep, NaN past
+    "n_sweeps", the sweeps done."""
+    dev = _is_torch(y)
+    if dev != _is_torch(neighbours):
+        raise ValueError("y and neighbours must both be numpy arrays or both torch tensors")
+    if not dev:
+        _lib.require_device()
+        y = np.ascontiguousarray(np.atleast_2d(y), np.float64)
+        neighbours = np.ascontiguousarray(neighbours, np.int32)
+    n_vox, n_b = y.shape
+    o, b, atoms, fv, lo, hi, lp = _mrf_host_inputs("grid_posterior_mrf", model, b, n_b, atoms, lo, hi, fixed_idx, fixed_vals, sigma, t1_mode, tr,
+                                                   tm, log_prior)
+    n = o.n_free
+    if neighbours.ndim != 2 or neighbours.shape[0] != n_vox:
+        raise ValueError(f"neighbours must have shape ({n_vox}, n_nb), got {tuple(neighbours.shape)}")
+    pr = _mrf_precision(precision, n)
+    cs = np.ascontiguousarray(colour_start, np.int64)
+    if cs.ndim != 1 or cs.size < 2:
+        raise ValueError("colour_start must hold n_colours + 1 offsets")
+    n_sweeps = int(n_sweeps)
+    if dev:
+        import torch
+
+        mk = lambda key, shape, dt: (out or {}).get(key) if (out or {}).get(key) is not None else torch.empty(shape, dtype=dt, device=y.device)
+        res = {key: mk(key, (n, n_vox), torch.float64) for key in ("mean", "sd", "map_p")}
+        res["map_atom"] = mk("map_atom", (n_vox,), torch.int32)
+        res["log_evidence"], res["ess"] = mk("log_evidence", (n_vox,), torch.float64), mk("ess", (n_vox,), torch.float64)
+    else:
+        res = {key: _out(out, key, (n, n_vox), np.float64) for key in ("mean", "sd", "map_p")}
+        res["map_atom"] = _out(out, "map_atom", (n_vox,), np.int32)
+        res["log_evidence"] = _out(out, "log_evidence", (n_vox,), np.float64)
+        res["ess"] = _out(out, "ess", (n_vox,), np.float64)
+    delta = np.full(min(max(n_sweeps, 0), GRID_MRF_MAX_SWEEPS), np.nan)  # outside 0..100 the library refuses before it writes
+    done = C.c_int(0)
+    check(load().pnx_curvefit_grid_posterior_mrf_f64(C.byref(o), int(n_vox), ptr(b), ptr(y), int(atoms.shape[1]), ptr(atoms), ptr(fv), ptr(lo),
+                                                     ptr(hi), int(bool(project_amplitude)), ptr(lp), float(noise_sd), int(neighbours.shape[1]),
+                                                     ptr(neighbours), int(cs.size - 1), ptr(cs), ptr(pr), n_sweeps, float(tol), ptr(res["mean"]),
+                                                     ptr(res["sd"]), ptr(res["map_atom"]), ptr(res["map_p"]), ptr(res["log_evidence"]),
+                                                     ptr(res["ess"]), ptr(delta), C.byref(done), MEM_DEVICE if dev else MEM_HOST, int(device),
+                                                     stream))
+    res["delta"], res["n_sweeps"] = delta, int(done.value)
+    return res
+
+
 GRID_MARGINAL_MAX_BINS = 128  # kGridMarginalMaxBins of csrc/pnx_grid_marginal_args.hpp
 GRID_MARGINAL_MAX_PROBS = 8
 

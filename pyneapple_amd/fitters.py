@@ -390,6 +390,12 @@ class HipPixelWiseFitter(HipFitterBase):
             if segmentation is None:
                 raise ValueError(f"{type(self.solver).__name__} asks for labels (a per-label prior): pass a segmentation")
             fit_kwargs = dict(fit_kwargs, labels=segmentation[mask])
+        # a solver with a neighbourhood (MRF) prior (HipBayesGridSolver: spatial_prior) takes the neighbour table and colours of the mask
+        if getattr(self.solver, "needs_neighbours", False) and "neighbours" not in fit_kwargs:
+            from . import api
+
+            nb, colours = api.grid_neighbours(mask, self.solver.spatial_prior["connectivity"])
+            fit_kwargs = dict(fit_kwargs, neighbours=nb, colours=colours)
         # pixelwise.py:91-96 always forwards pixel_fixed_params; a solver that cannot take it must not silently lose the maps
         if _accepts_pixel_fixed_params(self.solver):
             self.solver.fit(xdata, pixels, pixel_fixed_params=pixel_fixed, **fit_kwargs)

@@ -913,6 +913,17 @@ class HipBayesGridSolver(RefBaseSolver):
             negative label is background: NaN results, success False) and starts every row from `log_prior` (a 2-D `log_prior`
             must then have C rows).  Each label needs as many voxels as a whole volume does for the single table.  Not built with
             per-label priors: `marginals` and max_voxels (a ValueError that says so), hip_bayes_varpro, neighbourhood (MRF) priors.
+        spatial_prior: None / False (default): every voxel is judged on its own.  A dict {"strength": s or {name: s}, "n_sweeps": 4,
+            "tol": 0.0, "connectivity": 6} (TOML: a table [Fitting.solver.spatial_prior]; an unknown key, a negative strength or an
+            unknown parameter name is a ValueError): a pairwise Gaussian neighbourhood (MRF) prior between adjacent voxels, by
+            coloured mean-field sweeps (pnx_curvefit_grid_posterior_mrf_f64).  The precision of parameter k is
+            strength_k / (range of its grid values over the admitted atoms)^2, 0 for a one-value axis and for a projected S0;
+            strength 0 is the plain posterior.  `fit` then needs `neighbours` (n_pixels, n_nb) and `colours` (n_pixels,) --
+            HipPixelWiseFitter passes api.grid_neighbours(mask, connectivity) (4 / 8: in-plane, 6: 3-D) --, sorts the voxels stably
+            by colour, runs the sweeps and returns the results in the caller's order.  Worth it at low SNR: on a two-region
+            phantom at 5 % noise strength 64 cuts the median errors by a quarter to a third; at 2 % noise strength 4 gains a few
+            per cent and strength 64 over-smooths and LOSES up to 18 % (README).  With empirical_prior (single table) the table is
+            learned first, without the spatial term.  Refused by name: together with a per-label or 2-D prior, or with marginals.
         marginals: None / False (default): nothing more.  True, or a dict {"quantiles": [0.025, 0.5, 0.975]} (TOML: a table
             [Fitting.solver.marginals]; an unknown key is a ValueError; up to 8 levels inside (0, 1)): `fit` also reports the
             marginal posterior of every gridded parameter over its grid values and these quantiles of it
@@ -930,19 +941,24 @@ class HipBayesGridSolver(RefBaseSolver):
     "log_prior" is (C, n_atoms), "prior_loglik" (n_iter + 1, C) with its sum over the labels in "prior_loglik_total", and
     {"prior_n_eff" (C,), "prior_labels" the label value of every row} come with them --, with marginals also
     {"marginal" {name: (n_bins, n_pixels)}, "marginal_values" {name: (n_bins,)}, "quantiles" {name: (n_q, n_pixels)},
-    "quantile_probs"} (a projected S0 is absent from the three dicts); pixel_results_ with success = the voxel's signal was finite."""
+    "quantile_probs"} (a projected S0 is absent from the three dicts), with spatial_prior also {"spatial_sweeps" the sweeps run,
+    "spatial_delta" (n_sweeps,) the largest move of a mean per sweep in units of its grid range, "spatial_precision" {name: lambda}}
+    and "log_evidence" is then the local normaliser of the last update, not a model evidence; pixel_results_ with success = the
+    voxel's signal was finite."""
 
     _MARGINALS_DEFAULTS = {"quantiles": (0.025, 0.5, 0.975)}
     _EMPIRICAL_PRIOR_DEFAULTS = {"n_iter": 20, "pseudo_count": 0.0, "rel_tol": 1e-6, "max_voxels": None}
     _EMPIRICAL_PRIOR_PER_LABEL = {"per_label": False}  # reported among the options only when it is on
+    _SPATIAL_PRIOR_DEFAULTS = {"strength": None, "n_sweeps": 4, "tol": 0.0, "connectivity": 6}
 
     def __init__(self, model: Any, grid=None, max_iter: int = 250, tol: float = 1e-8, p0: dict[str, float] | None = None,
                  bounds: dict[str, tuple[float, float]] | None = None, noise_sd: float | None = None, log_prior=None, project=None,
                  sigma=None, device: int = 0, io_dtype: str = "float64", precision: str = "float64", empirical_prior=None,
-                 marginals=None, **ignored_reference_kwargs):
+                 marginals=None, spatial_prior=None, **ignored_reference_kwargs):
         RefBaseSolver.__init__(self, model=model, max_iter=max_iter, tol=tol, verbose=bool(ignored_reference_kwargs.pop("verbose", False)))
         self._kernel_model = kernel_model_key(model)
         self._kernel_t1 = kernel_t1(model)
+        self.spatial_prior = self._spatial_prior_options(spatial_prior, list(model.param_names))
         self.empirical_prior = self._empirical_prior_options(empirical_prior)
         self.marginals = self._marginals_options(marginals)
         if _io_dtype(io_dtype) is not np.float64 or precision != "float64":
@@ -994,11 +1010,103 @@ class HipBayesGridSolver(RefBaseSolver):
             raise ValueError("empirical_prior max_voxels is not built with per_label: every label learns from all of its voxels")
         if self.empirical_prior and not per_label and self.log_prior is not None and self.log_prior.ndim == 2:
             raise ValueError("empirical_prior with a 2-D log_prior needs per_label: a single learned table has no single row to start from")
+        if self.spatial_prior and self.needs_labels:
+            raise ValueError("HipBayesGridSolver: spatial_prior is not built with per-label priors (a 2-D log_prior or empirical_prior "
+                             "per_label): pnx_curvefit_grid_posterior_mrf_f64 takes one prior table")
+        if self.spatial_prior and self.marginals:
+            raise ValueError("HipBayesGridSolver: spatial_prior is not built with marginals: pnx_curvefit_grid_marginals_f64 knows no field")
 
     @property
     def needs_labels(self) -> bool:
         """True when `fit` needs `labels`: a 2-D log_prior, or empirical_prior with per_label."""
         return bool((self.log_prior is not None and self.log_prior.ndim == 2) or (self.empirical_prior and self.empirical_prior.get("per_label")))
+
+    @property
+    def needs_neighbours(self) -> bool:
+        """True when `fit` needs `neighbours` and `colours`: spatial_prior is on."""
+        return bool(self.spatial_prior)
+
+    @classmethod
+    def _spatial_prior_options(cls, value, names):
+        """None when off, else {"strength": {name: s} for every parameter, "n_sweeps", "tol", "connectivity"}, checked."""
+        if value is None or value is False:
+            return None
+        if not isinstance(value, dict):
+            raise ValueError(f"spatial_prior must be None or a dict of {sorted(cls._SPATIAL_PRIOR_DEFAULTS)}, got {value!r}")
+        unknown = sorted(set(value) - set(cls._SPATIAL_PRIOR_DEFAULTS))
+        if unknown:
+            raise ValueError(f"spatial_prior has unknown keys {unknown}; it takes {sorted(cls._SPATIAL_PRIOR_DEFAULTS)}")
+        opt = {**cls._SPATIAL_PRIOR_DEFAULTS, **value}
+        st = opt["strength"]
+        if st is None:
+            raise ValueError("spatial_prior needs a strength: a number, or {parameter name: number}")
+        if isinstance(st, dict):
+            bad = sorted(set(st) - set(names))
+            if bad:
+                raise ValueError(f"spatial_prior strength names unknown parameters {bad}; the model has {names}")
+            st = {n: st.get(n, 0.0) for n in names}
+        else:
+            st = {n: st for n in names}
+        for n, v in st.items():
+            if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not (np.isfinite(v) and v >= 0.0):
+                raise ValueError(f"spatial_prior strength of {n} must be finite and >= 0, got {v!r}")
+        ns, tol, conn = opt["n_sweeps"], opt["tol"], opt["connectivity"]
+        if isinstance(ns, bool) or int(ns) != ns or not 0 <= ns <= api.GRID_MRF_MAX_SWEEPS:
+            raise ValueError(f"spatial_prior n_sweeps must be an integer in [0, {api.GRID_MRF_MAX_SWEEPS}], got {ns!r}")
+        if not (np.isfinite(float(tol)) and float(tol) >= 0.0):
+            raise ValueError(f"spatial_prior tol must be finite and >= 0, got {tol!r}")
+        if isinstance(conn, bool) or conn not in (4, 6, 8):
+            raise ValueError(f"spatial_prior connectivity must be 4, 8 (in-plane) or 6 (3-D), got {conn!r}")
+        return {"strength": {n: float(v) for n, v in st.items()}, "n_sweeps": int(ns), "tol": float(tol), "connectivity": int(conn)}
+
+    def spatial_precision(self, log_prior=None):
+        """precision (n_free,) of the spatial prior under `log_prior` (None: uniform): strength / range^2 over the admitted atoms, 0
+        for a one-value axis and for a projected S0."""
+        names = list(self.model.param_names)
+        adm = np.ones(self._atoms.shape[1], bool) if log_prior is None else np.asarray(log_prior, float) > -np.inf
+        rng = self._atoms[:, adm].max(axis=1) - self._atoms[:, adm].min(axis=1)
+        pr = np.zeros(len(names))
+        for k, n in enumerate(names):
+            if rng[k] > 0.0 and not (self.project and n == "S0"):
+                pr[k] = self.spatial_prior["strength"][n] / rng[k] ** 2
+        return pr
+
+    @staticmethod
+    def colour_sort(neighbours, colours, n_pixels):
+        """(order, neighbours of the sorted voxels, colour_start): the voxels sorted stably by colour -- voxel order[i] of the caller
+        is voxel i of the call --, the table's rows permuted and its indices remapped, and the offsets of the colour ranges."""
+        nb, col = np.asarray(neighbours), np.asarray(colours)
+        if nb.ndim != 2 or nb.shape[0] != n_pixels or nb.dtype.kind not in "iu" or not 1 <= nb.shape[1] <= api.GRID_MRF_MAX_NEIGHBOURS:
+            raise ValueError(f"neighbours must be ({n_pixels}, 1..{api.GRID_MRF_MAX_NEIGHBOURS}) integers, got shape {nb.shape} and dtype {nb.dtype}")
+        if col.shape != (n_pixels,) or col.dtype.kind not in "iu" or (col.size and (col.min() < 0 or col.max() >= api.GRID_MRF_MAX_COLOURS)):
+            raise ValueError(f"colours must be {n_pixels} integers in [0, {api.GRID_MRF_MAX_COLOURS}), got shape {col.shape} and dtype {col.dtype}")
+        if nb.size and (nb.min() < -1 or nb.max() >= n_pixels):
+            raise ValueError(f"neighbours must hold voxel indices in [-1, {n_pixels})")
+        order = np.argsort(col, kind="stable")
+        place = np.empty(n_pixels, np.int64)
+        place[order] = np.arange(n_pixels)
+        rows = nb[order]
+        sorted_nb = np.where(rows >= 0, place[np.maximum(rows, 0)], -1).astype(np.int32)
+        n_colours = int(col.max()) + 1 if col.size else 1
+        start = np.concatenate([[0], np.cumsum(np.bincount(col, minlength=n_colours))]).astype(np.int64)
+        return order, np.ascontiguousarray(sorted_nb), start
+
+    def _fit_spatial(self, xdata, ydata, neighbours, colours, lo, hi, log_prior, common):
+        """The posterior under the neighbourhood prior, in the caller's voxel order."""
+        n_pixels = ydata.shape[0]
+        if neighbours is None or colours is None:
+            raise ValueError("HipBayesGridSolver: neighbours (n_pixels, n_nb) and colours (n_pixels,) are required with spatial_prior "
+                             "(api.grid_neighbours(mask, connectivity); HipPixelWiseFitter passes them)")
+        order, nb, start = self.colour_sort(neighbours, colours, n_pixels)
+        precision = self.spatial_precision(log_prior)
+        sp = self.spatial_prior
+        res = api.grid_posterior_mrf(self._kernel_model, xdata, np.ascontiguousarray(ydata[order]), self._atoms, lo, hi, nb, start, precision,
+                                     n_sweeps=sp["n_sweeps"], tol=sp["tol"], log_prior=log_prior, **common)
+        back = np.empty(n_pixels, np.int64)
+        back[order] = np.arange(n_pixels)
+        out = {k: np.ascontiguousarray(v[..., back]) for k, v in res.items() if k in ("mean", "sd", "map_p", "map_atom", "log_evidence", "ess")}
+        out.update(delta=res["delta"], n_sweeps=res["n_sweeps"], precision=precision)
+        return out
 
     @classmethod
     def _empirical_prior_options(cls, value):
@@ -1096,7 +1204,8 @@ class HipBayesGridSolver(RefBaseSolver):
         res = api.grid_posterior_classes(self._kernel_model, xdata, ydata, self._atoms, lo, hi, rows, n_classes, log_prior=table, **common)
         return res, learned
 
-    def fit(self, xdata: np.ndarray, ydata: np.ndarray, pixel_fixed_params=None, labels=None, **fit_kwargs) -> "HipBayesGridSolver":
+    def fit(self, xdata: np.ndarray, ydata: np.ndarray, pixel_fixed_params=None, labels=None, neighbours=None, colours=None,
+            **fit_kwargs) -> "HipBayesGridSolver":
         if pixel_fixed_params:
             raise ValueError("HipBayesGridSolver is not built with per-pixel fixed parameters (pixel_fixed_params): the dictionary "
                              "would differ from voxel to voxel")
@@ -1129,7 +1238,9 @@ class HipBayesGridSolver(RefBaseSolver):
                                         pseudo_count=ep["pseudo_count"], rel_tol=ep["rel_tol"], **common)
             learned["n_voxels"] = sample.shape[0]
             log_prior = learned["log_prior"]
-        if not self.needs_labels:
+        if self.spatial_prior:
+            res = self._fit_spatial(xdata, ydata, neighbours, colours, lo, hi, log_prior, common)
+        elif not self.needs_labels:
             res = api.grid_posterior(self._kernel_model, xdata, ydata, self._atoms, lo, hi, log_prior=log_prior, **common)
         mean, atom = res["mean"], res["map_atom"]
         self.pixel_results_ = PixelResultsView(mean.T, None, atom >= 0,
@@ -1144,6 +1255,9 @@ class HipBayesGridSolver(RefBaseSolver):
             if "labels" in learned:
                 self.diagnostics_.update({"prior_loglik": learned["loglik_class"], "prior_loglik_total": learned["loglik"],
                                           "prior_n_eff": learned["n_eff"], "prior_labels": [int(v) for v in learned["labels"]]})
+        if self.spatial_prior:
+            self.diagnostics_.update({"spatial_sweeps": res["n_sweeps"], "spatial_delta": res["delta"],
+                                      "spatial_precision": {n: float(res["precision"][i]) for i, n in enumerate(names)}})
         if self.marginals:
             mg = api.grid_marginals(self._kernel_model, xdata, ydata, self._atoms, lo, hi, log_prior=log_prior,
                                     quantiles=self.marginals["quantiles"], **common)
