@@ -106,12 +106,12 @@ def test_atom_axis(gpu, n_atoms, model, project):
     _both_modes(gpu, model, _case(model, 65, n_atoms, 32), project=project)
 
 
-@pytest.mark.parametrize("n_b", [1, 4, 5, 32, 33])  # 33 takes the larger instantiation; 1 and 5 pad the k-steps
+@pytest.mark.parametrize("n_b", [1, 4, 5, 32, 33, 64, 65, 128])  # 33 and up take the larger instantiation; 1, 5 and 65 pad the k-steps
 def test_b_axis(gpu, n_b):
     _both_modes(gpu, "tri_reduced", _case("tri_reduced", 65, 33, n_b))
 
 
-@pytest.mark.parametrize("n_b", [4, 5, 32, 33])
+@pytest.mark.parametrize("n_b", [4, 5, 32, 33, 65, 128])
 def test_b_axis_projected(gpu, n_b):
     _both_modes(gpu, "bi_s0", _case("bi_s0", 65, 33, n_b), project=True)
 

@@ -66,6 +66,43 @@ def test_slab_stays_inside_the_lds_budget_and_python_agrees(stub, n_b):
     assert api.grid_class_slab_atoms(n_b, 1, 3) == api.grid_posterior_slab_atoms(n_b, 3)
 
 
+def _slab_image(kpad_rows, per_atom, w):
+    """(stride, doubles) of the LDS image of a slab `w` atoms wide: kpad_rows dictionary rows of `stride` doubles and per_atom values
+    per atom -- the layout grid_class_slab / varpro_class_slab of the csrc headers size."""
+    stride = w if w & 16 else w + 16
+    return stride, kpad_rows * stride + per_atom * w
+
+
+def test_slab_rule_for_every_b_value_and_class_count():
+    """Every (n_b in 1..128, n_classes in 1..16), grid_class_slab and varpro_class_slab (k = 1..3), for the posterior and for both EM
+    passes: the width is a multiple of 16 and at least 16, the stride is 16 mod 32, the image fits 64 KB, and no wider slab would.
+    Through api.grid_class_slab_atoms / api.varpro_class_slab_atoms: the stub prints one width per process (its own run sweeps the
+    same product inside the C++), so the Python restatement is swept here and compared with the stub at the minimum-width corner
+    below and at four b-values above."""
+    for n_b in range(1, 129):
+        kpad = (n_b + 3) & ~3
+        for n_classes in range(1, 17):
+            for extra in (4 * n_classes, 1, 8):  # both EM passes; the posterior at 1 and 8 free parameters
+                w = api.grid_class_slab_atoms(n_b, n_classes, extra)
+                stride, doubles = _slab_image(kpad, 2 + n_classes + extra, w)
+                assert w >= 16 and w % 16 == 0 and w <= 256 and stride % 32 == 16 and stride >= w and doubles * 8 <= 64 * 1024
+                assert w == 256 or _slab_image(kpad, 2 + n_classes + extra, w + 16)[1] * 8 > 64 * 1024  # the widest that fits
+            for k in (1, 2, 3):
+                for extra in (4 * n_classes, k + 1):  # both EM passes; the posterior
+                    w = api.varpro_class_slab_atoms(n_b, k, n_classes, extra)
+                    stride, doubles = _slab_image(k * kpad, k * (k + 1) + n_classes + extra, w)
+                    assert w >= 16 and w % 16 == 0 and w <= 256 and stride % 32 == 16 and stride >= w and doubles * 8 <= 64 * 1024
+                    assert w == 256 or _slab_image(k * kpad, k * (k + 1) + n_classes + extra, w + 16)[1] * 8 > 64 * 1024
+
+
+def test_minimum_slab_width_corner(stub):
+    """128 b-values and 16 classes leave the EM 16 atoms; 12 classes are the last to leave it 32.  Python and the C++ agree."""
+    assert api.grid_class_slab_atoms(128, 16, 64) == 16 == int(_run_stub(stub, 128, 16, 64))
+    assert api.grid_class_slab_atoms(128, 12, 48) == 32 == int(_run_stub(stub, 128, 12, 48))
+    assert api.grid_class_slab_atoms(128, 13, 52) == 16 == int(_run_stub(stub, 128, 13, 52))
+    assert _slab_image(128, 2 + 16 + 64, 16) == (16, 3360)
+
+
 # ---- the ABI without a device
 def _call(name, o, n_vox=1, n_atoms=4, n_classes=2, labels=True, log_prior=None, noise_sd=0.0, n_iter=3, out=True):
     n = o.n_free

@@ -300,6 +300,43 @@ def test_labelled_posterior_reference_is_the_unlabelled_reference_row_by_row():
         assert ref["mean"][lab == k].tobytes() == one["mean"].tobytes() and ref["bound_mean"][lab == k].tobytes() == one["bound_mean"].tobytes()
 
 
+# ---- the CPU precondition of tests/test_gpu_varpro_class_axes.py: the references alone on every one of its cases
+_AXES = {}
+
+
+def _axes_cases():
+    from varpro_class_axes_cases import cases
+
+    if not _AXES:
+        _AXES.update(cases())
+    return _AXES
+
+
+@pytest.mark.parametrize("family,count", [("layout-bi", 6), ("layout-mono", 2), ("layout-tri", 6), ("n_b-", 9), ("min-slab-", 2)])
+def test_the_references_hold_their_precondition_on_every_case_of_the_axes_file(family, count):
+    """eps_v <= the case's cap on EVERY voxel (asserted inside the references: 1e-6, or the 1e-3 of 16 b-values or fewer), for the
+    labelled posterior under the GPU file's rows and for the EM's l0; no case clips but the two-compartment S0 / reduced layouts at
+    16 b-values, whose neighbouring rates leave a share of 1e-5 at most on a clipped amplitude."""
+    from varpro_marginal_cases import ref_kw
+    from varpro_prior_reference import likelihoods
+
+    assert len(_axes_cases()) == 7 * 2 + 9 + 2
+    mine = {k: v for k, v in _axes_cases().items() if k.startswith(family)}
+    assert len(mine) == count
+    for name, per_mode in mine.items():
+        for c in per_mode:
+            n_classes, n_vox, G = c.get("n_classes", 3), c["y"].shape[0], c["atoms"].shape[1]
+            assert n_vox == 65
+            lab = np.arange(n_vox) % n_classes
+            rows = np.log(np.random.default_rng(5).uniform(0.01, 1.0, (n_classes, G))) + 2.5  # the GPU file's _rows
+            args = (c["model"], c["b"], c["y"], c["atoms"], c["lo"], c["hi"])
+            ref = posterior(*args, lab, n_classes, log_prior=rows, **ref_kw(c))
+            l0, eps0, fin = likelihoods(*args, **ref_kw(c))
+            assert ref["finite"].all() and fin.all() and ref["eps"].max() <= c["max_eps"] and eps0.max() <= c["max_eps"], name
+            assert c["max_eps"] == (1e-3 if len(c["b"]) <= 16 else 1e-6), name
+            assert ref["clipped_mass"].max() <= (1e-5 if len(c["b"]) <= 16 else 0.0), name
+
+
 # ---- the CPU precondition of the GPU file's worth test
 @pytest.mark.parametrize("noise_sd,single,per_label", [(0.05, 0.10254, 0.08495), (0.0, 0.16883, 0.13024)])
 def test_the_reference_shows_the_gain_the_gpu_test_asks_the_library_for(noise_sd, single, per_label):
