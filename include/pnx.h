@@ -862,6 +862,74 @@ PNX_API int pnx_curvefit_varpro_prior_em_classes_f64(const pnx_curvefit_opts *op
                                      double *loglik, double *loglik_class, int *n_iter_done, int64_t *n_eff, int mem, int device,
                                      void *stream);
 /*
+ * Neighbourhood (MRF) prior for pnx_curvefit_varpro_posterior_f64 by coloured mean-field sweeps: the prior of
+ * pnx_curvefit_grid_posterior_mrf_f64 with theta restricted to the NON-LINEAR free rows (the rates, a free T1).  A fraction or S0
+ * row has no grid value -- its value belongs to the voxel-atom pair -- so its precision must be 0 (PNX_ERR_INVALID otherwise), the
+ * rule of the projected S0 row of the grid solver and of n_bins of pnx_curvefit_varpro_marginals_f64.  With lambda = precision:
+ *   l_g(v) = [pnx_curvefit_varpro_posterior_f64's l_g(v), term for term] + sum_{k non-linear} thetac_kg q_vk - 1/2 n_v r_g
+ *   thetac_kg = nl_atoms[row_k, g] - centre_k   centre_k: the posterior's own centre, min + (max - min) / 2 over the admissible atoms
+ *   q_vk = lambda_k sum_{u in N(v), present} (mean[k, u] - centre_k)      pnx_curvefit_grid_neighbour_field_f64 with centre = 0 and
+ *                                                                         precision = 0 on the linear rows: q is 0 there
+ *   n_v = the number of present neighbours;  r_g = sum_k lambda_k thetac_kg^2   (host, fp64, k ascending over the non-linear rows)
+ * A neighbour is present when its slot holds an index >= 0 and mean[0, u] is finite.  The Occam term of marginal_amplitudes and the
+ * exclusions lw = -inf stay as they are; a pair at lw = -inf is skipped before any arithmetic.
+ *
+ * pnx_curvefit_varpro_posterior_field_f64: one colour update.  Every argument of pnx_curvefit_varpro_posterior_f64 up to
+ * marginal_amplitudes, its weighting, refusals and outputs, for the voxels [first, first + count) under the l_g above, written IN
+ * PLACE into the full-length output arrays (n_free, n_vox) / (n_vox); the other voxels' entries are not touched.
+ *   n_vox in [0, 2^31 - 1];
+ *   field_q (n_free, n_vox), field_n (n_vox) int32: device, as the gather wrote them (only the range, and of field_q only the
+ *     non-linear rows, are read);
+ *   precision (n_free,) host: finite, >= 0, and 0 on a fraction / S0 row;
+ *   delta_max: device scalar or NULL; receives max over { k: non-linear, precision_k > 0 and range_k > 0; v in the range, finite } of
+ *     |mean_new[k, v] - mean_old[k, v]| / range_k,  range_k = max_g theta_kg - min_g theta_kg over the admissible atoms.  Each lane
+ *     reads its old mean before it overwrites it; the maximum is reduced per block by shuffles and then over the blocks by a small
+ *     kernel: no floating-point atomics.  0 for an empty range.
+ * With field_q = 0 and field_n = 0 the added terms are exactly +0.0 and the call returns the bytes of
+ * pnx_curvefit_varpro_posterior_f64 for those voxels, clipped_mass included; with every precision 0 the field is not read and the
+ * same holds.
+ * log_evidence is L_v - log sum_g exp(log_prior_g) with the field inside L_v: a LOCAL NORMALISER of the voxel's update given its
+ * neighbours, not a model evidence -- do not sum it over voxels or compare it between models.
+ * The field product runs on the fp64 matrix cores, one k-step (at most K + 1 <= 4 non-linear rows) into an accumulator of its own.
+ * PNX_MEM_DEVICE only (PNX_ERR_INVALID otherwise); the call only enqueues.
+ */
+PNX_API int pnx_curvefit_varpro_posterior_field_f64(const pnx_curvefit_opts *opts, int64_t n_vox, const double *b, const double *y,
+                                     int n_atoms, const double *nl_atoms, const double *fixed, const double *lo, const double *hi,
+                                     const double *log_prior, double noise_sd, int marginal_amplitudes, int64_t first, int64_t count,
+                                     const double *field_q, const int32_t *field_n, const double *precision, double *mean, double *sd,
+                                     int32_t *map_atom, double *map_p, double *log_evidence, double *ess, double *clipped_mass,
+                                     double *delta_max, int mem, int device, void *stream);
+/*
+ * pnx_curvefit_varpro_posterior_mrf_f64: the driver.  The arguments and outputs of pnx_curvefit_varpro_posterior_f64, and
+ *   n_nb in [1, 8]; neighbours (n_vox, n_nb) int32, -1 where a slot is empty, host|device as `mem`; the graph must be symmetric
+ *     (not checked);
+ *   n_colours in [1, 8]; colour_start (n_colours + 1,) int64 host, ascending from 0 to n_vox: the voxels of colour c are the
+ *     contiguous range [colour_start[c], colour_start[c+1]) -- the caller sorts the voxels by colour; a colour may be empty;
+ *   precision (n_free,) host; n_sweeps in [0, 100]; tol finite, >= 0;
+ *   delta (n_sweeps,) host or NULL; n_sweeps_done host or NULL.
+ * Sweep 0 is the plain posterior on all voxels (the bytes of pnx_curvefit_varpro_posterior_f64).  Sweep s = 1 .. n_sweeps runs, for
+ * each colour in order, pnx_curvefit_grid_neighbour_field_f64's gather and then the field posterior on that colour's range: colour
+ * after colour is coordinate ascent on the variational free energy, which never decreases.  delta[s-1] is the maximum of delta_max
+ * over the sweep's colour updates; the call stops after sweep s when delta[s-1] <= tol (tol = 0 runs all sweeps, without a host
+ * round trip per sweep); entries of delta past n_sweeps_done are NaN.  log_evidence is the local normaliser described above.
+ * A small kernel verifies the table before sweep 0, and nothing is dereferenced before it is bound-checked: an index outside
+ * [-1, n_vox), or a neighbour of a voxel inside the voxel's own colour range, returns PNX_ERR_INVALID and names the first offending
+ * voxel.  Refused before any device work: everything the posterior refuses; n_nb, n_colours, n_sweeps or tol out of range;
+ * colour_start not ascending from 0 to n_vox; a negative or non-finite precision; a positive precision on a fraction / S0 row.
+ * Every sum of a voxel depends on the order of the atoms and of its slots only: two calls return the same bytes, PNX_MEM_HOST or
+ * PNX_MEM_DEVICE, and the call returns the bytes of the same sequence composed from the gather and the field call.
+ *   PNX_MEM_HOST: y and neighbours are uploaded once (pnx_upload's path) and the outputs come back from one stream-ordered
+ *   buffer, as pnx_curvefit_grid_posterior_mrf_f64 does -- no chunk ring; PNX_ERR_NOMEM names the size.  For both `mem` values the
+ *   call SYNCHRONISES `stream` before it returns.
+ */
+PNX_API int pnx_curvefit_varpro_posterior_mrf_f64(const pnx_curvefit_opts *opts, int64_t n_vox, const double *b, const double *y,
+                                     int n_atoms, const double *nl_atoms, const double *fixed, const double *lo, const double *hi,
+                                     const double *log_prior, double noise_sd, int marginal_amplitudes, int n_nb,
+                                     const int32_t *neighbours, int n_colours, const int64_t *colour_start, const double *precision,
+                                     int n_sweeps, double tol, double *mean, double *sd, int32_t *map_atom, double *map_p,
+                                     double *log_evidence, double *ess, double *clipped_mass, double *delta, int *n_sweeps_done,
+                                     int mem, int device, void *stream);
+/*
  * Log-linear mono-exponential fit, ln S = ln S0 - b D by (weighted) linear least squares per voxel: the ADC
  * map, step 1 of a segmented IVIM fit, a cheap source of S0 / D start values.  A closed form over one pass of the data: a voxel
  * costs its signal row in and its results out.  Per voxel, in fp64, in the order written:

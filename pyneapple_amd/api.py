@@ -1025,6 +1025,118 @@ def varpro_posterior_device(opts, n_vox, b, y, nl_atoms, fixed, lo, hi, log_prio
                                                    int(device), stream))
 
 
+def varpro_mrf_slab_atoms(n_b, k):
+    """Atoms per LDS slab of the variable-projection field posterior (varpro_mrf_slab of csrc/pnx_varpro_mrf_args.hpp): the
+    posterior's rule with one more value per atom (r_g) and the 8 doubles of the delta reduction."""
+    kpad, k, width = (int(n_b) + 3) & ~3, int(k), 16
+    for w in range(16, 257, 16):
+        if k * kpad * (w if w & 16 else w + 16) + (k * (k + 1) + k + 3) * w + 8 <= 8192:
+            width = w
+    return width
+
+
+def varpro_mrf_centre(nl_atoms, nonlinear, log_prior=None):
+    """The centres the variable-projection posterior accumulates its moments about (varpro_posterior_check_args), per free
+    parameter: min + (max - min) / 2 of the row of nl_atoms over the admissible atoms where `nonlinear` (n_free,) bool is set (a
+    rate, T1; the rows of nl_atoms in order), 0 for a fraction / S0 row.  What `grid_neighbour_field` takes as `centre` in front
+    of `varpro_posterior_field`."""
+    nl_atoms = np.asarray(nl_atoms, np.float64)
+    nonlinear = np.asarray(nonlinear, bool)
+    if int(nonlinear.sum()) != nl_atoms.shape[0]:
+        raise ValueError(f"nonlinear marks {int(nonlinear.sum())} rows, nl_atoms has {nl_atoms.shape[0]}")
+    adm = np.ones(nl_atoms.shape[1], bool) if log_prior is None else np.asarray(log_prior, np.float64) > -np.inf
+    mn, mx = nl_atoms[:, adm].min(axis=1), nl_atoms[:, adm].max(axis=1)
+    centre = np.zeros(nonlinear.size)
+    centre[nonlinear] = mn + 0.5 * (mx - mn)
+    return centre
+
+
+def varpro_posterior_field(model, b, y, nl_atoms, lo, hi, field_q, field_n, precision, out, *, first=0, count=None, log_prior=None,
+                           noise_sd=0.0, marginal_amplitudes=True, fixed_idx=(), fixed_vals=None, sigma=None, t1_mode=0, tr=0., tm=0.,
+                           delta_max=None, device=0, stream=None):
+    """One colour update of the neighbourhood prior over a variable-projection dictionary (pnx_curvefit_varpro_posterior_field_f64;
+    method: include/pnx.h): the posterior of the voxels [first, first + count) with the field inside l_g, written in place into the
+    full-length tensors of `out`.  Device only, asynchronous (the caller synchronises): y (n_vox, n_b), field_q (n_free, n_vox),
+    field_n (n_vox,) int32 and out["mean"] (required, and read: delta compares against it), out["sd"], out["map_p"] (n_free,
+    n_vox), out["map_atom"] (n_vox,) int32, out["log_evidence"], out["ess"], out["clipped_mass"] (n_vox,) are torch tensors on the
+    device; delta_max: a one-element float64 device tensor or None.  The other arguments are `varpro_posterior`'s host arrays and
+    precision (n_free,), 0 on every fraction / S0 row.  Returns `out`."""
+    for name, t in (("y", y), ("field_q", field_q), ("field_n", field_n), ("out['mean']", (out or {}).get("mean"))):
+        if not _is_torch(t):
+            raise ValueError(f"varpro_posterior_field works in place on device tensors: {name} is not a torch tensor")
+    n_vox, n_b = y.shape
+    b = np.ascontiguousarray(b, np.float64)
+    if b.shape != (n_b,):
+        raise ValueError(f"b has shape {b.shape}, expected ({n_b},)")
+    o, nl_atoms, lo, hi, _, fv = _varpro_args(model, n_b, nl_atoms, lo, hi, lo, fixed_idx, fixed_vals, sigma, t1_mode, tr, tm)
+    lp = _posterior_log_prior(log_prior, nl_atoms.shape[1])
+    pr = _mrf_precision(precision, o.n_free)
+    count = n_vox - int(first) if count is None else int(count)
+    check(load().pnx_curvefit_varpro_posterior_field_f64(C.byref(o), int(n_vox), ptr(b), ptr(y), int(nl_atoms.shape[1]), ptr(nl_atoms), ptr(fv),
+                                                         ptr(lo), ptr(hi), ptr(lp), float(noise_sd), int(bool(marginal_amplitudes)), int(first),
+                                                         count, ptr(field_q), ptr(field_n), ptr(pr), ptr(out["mean"]), ptr(out.get("sd")),
+                                                         ptr(out.get("map_atom")), ptr(out.get("map_p")), ptr(out.get("log_evidence")),
+                                                         ptr(out.get("ess")), ptr(out.get("clipped_mass")), ptr(delta_max), MEM_DEVICE,
+                                                         int(device), stream))
+    return out
+
+
+def varpro_posterior_mrf(model, b, y, nl_atoms, lo, hi, neighbours, colour_start, precision, *, n_sweeps=4, tol=0.0, log_prior=None,
+                         noise_sd=0.0, marginal_amplitudes=True, fixed_idx=(), fixed_vals=None, sigma=None, t1_mode=0, tr=0., tm=0., device=0,
+                         out=None, stream=None):
+    """The variable-projection posterior under a neighbourhood (MRF) prior on its rates (and a free T1) by coloured mean-field
+    sweeps (pnx_curvefit_varpro_posterior_mrf_f64; method: include/pnx.h).  The arguments of `varpro_posterior`, and neighbours,
+    colour_start, n_sweeps and tol as `grid_posterior_mrf` takes them; precision (n_free,) >= 0, 0 on every fraction / S0 row.
+    y and neighbours are numpy arrays (staged once) or torch tensors on the device (read in place; `out` may hold preallocated
+    result tensors); the call synchronises either way.  Returns the dict of `varpro_posterior` -- log_evidence is the local
+    normaliser of the last update, not a model evidence -- with "delta" (n_sweeps,) the largest relative move of a mean per sweep,
+    NaN past "n_sweeps", the sweeps done."""
+    dev = _is_torch(y)
+    if dev != _is_torch(neighbours):
+        raise ValueError("y and neighbours must both be numpy arrays or both torch tensors")
+    if not dev:
+        _lib.require_device()
+        y = np.ascontiguousarray(np.atleast_2d(y), np.float64)
+        neighbours = np.ascontiguousarray(neighbours, np.int32)
+    n_vox, n_b = y.shape
+    b = np.ascontiguousarray(b, np.float64)
+    if b.shape != (n_b,):
+        raise ValueError(f"b has shape {b.shape}, expected ({n_b},)")
+    o, nl_atoms, lo, hi, _, fv = _varpro_args(model, n_b, nl_atoms, lo, hi, lo, fixed_idx, fixed_vals, sigma, t1_mode, tr, tm)
+    lp = _posterior_log_prior(log_prior, nl_atoms.shape[1])
+    n = o.n_free
+    if neighbours.ndim != 2 or neighbours.shape[0] != n_vox:
+        raise ValueError(f"neighbours must have shape ({n_vox}, n_nb), got {tuple(neighbours.shape)}")
+    pr = _mrf_precision(precision, n)
+    cs = np.ascontiguousarray(colour_start, np.int64)
+    if cs.ndim != 1 or cs.size < 2:
+        raise ValueError("colour_start must hold n_colours + 1 offsets")
+    n_sweeps = int(n_sweeps)
+    if dev:
+        import torch
+
+        mk = lambda key, shape, dt: (out or {}).get(key) if (out or {}).get(key) is not None else torch.empty(shape, dtype=dt, device=y.device)
+        res = {key: mk(key, (n, n_vox), torch.float64) for key in ("mean", "sd", "map_p")}
+        res["map_atom"] = mk("map_atom", (n_vox,), torch.int32)
+        for key in ("log_evidence", "ess", "clipped_mass"):
+            res[key] = mk(key, (n_vox,), torch.float64)
+    else:
+        res = {key: _out(out, key, (n, n_vox), np.float64) for key in ("mean", "sd", "map_p")}
+        res["map_atom"] = _out(out, "map_atom", (n_vox,), np.int32)
+        for key in ("log_evidence", "ess", "clipped_mass"):
+            res[key] = _out(out, key, (n_vox,), np.float64)
+    delta = np.full(min(max(n_sweeps, 0), GRID_MRF_MAX_SWEEPS), np.nan)  # outside 0..100 the library refuses before it writes
+    done = C.c_int(0)
+    check(load().pnx_curvefit_varpro_posterior_mrf_f64(C.byref(o), int(n_vox), ptr(b), ptr(y), int(nl_atoms.shape[1]), ptr(nl_atoms), ptr(fv),
+                                                       ptr(lo), ptr(hi), ptr(lp), float(noise_sd), int(bool(marginal_amplitudes)),
+                                                       int(neighbours.shape[1]), ptr(neighbours), int(cs.size - 1), ptr(cs), ptr(pr), n_sweeps,
+                                                       float(tol), ptr(res["mean"]), ptr(res["sd"]), ptr(res["map_atom"]), ptr(res["map_p"]),
+                                                       ptr(res["log_evidence"]), ptr(res["ess"]), ptr(res["clipped_mass"]), ptr(delta),
+                                                       C.byref(done), MEM_DEVICE if dev else MEM_HOST, int(device), stream))
+    res["delta"], res["n_sweeps"] = delta, int(done.value)
+    return res
+
+
 def varpro_prior_slab_atoms(n_b, k):
     """Atoms per LDS slab of the two EM passes over the variable-projection dictionary (varpro_prior_slab of
     csrc/pnx_varpro_prior_args.hpp): the variable projection's rule with 5 more values per atom -- the log-weight and the four

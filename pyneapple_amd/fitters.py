@@ -390,7 +390,7 @@ class HipPixelWiseFitter(HipFitterBase):
             if segmentation is None:
                 raise ValueError(f"{type(self.solver).__name__} asks for labels (a per-label prior): pass a segmentation")
             fit_kwargs = dict(fit_kwargs, labels=segmentation[mask])
-        # a solver with a neighbourhood (MRF) prior (HipBayesGridSolver: spatial_prior) takes the neighbour table and colours of the mask
+        # a solver with a neighbourhood (MRF) prior (HipBayesGridSolver, HipBayesVarProSolver: spatial_prior) takes the neighbour table and colours of the mask
         if getattr(self.solver, "needs_neighbours", False) and "neighbours" not in fit_kwargs:
             from . import api
 

@@ -1097,14 +1097,23 @@ class HipBayesGridSolver(RefBaseSolver):
         if neighbours is None or colours is None:
             raise ValueError("HipBayesGridSolver: neighbours (n_pixels, n_nb) and colours (n_pixels,) are required with spatial_prior "
                              "(api.grid_neighbours(mask, connectivity); HipPixelWiseFitter passes them)")
-        order, nb, start = self.colour_sort(neighbours, colours, n_pixels)
         precision = self.spatial_precision(log_prior)
         sp = self.spatial_prior
-        res = api.grid_posterior_mrf(self._kernel_model, xdata, np.ascontiguousarray(ydata[order]), self._atoms, lo, hi, nb, start, precision,
-                                     n_sweeps=sp["n_sweeps"], tol=sp["tol"], log_prior=log_prior, **common)
+        return self.in_colour_order(
+            ydata, neighbours, colours, precision, ("mean", "sd", "map_p", "map_atom", "log_evidence", "ess"),
+            lambda y, nb, start: api.grid_posterior_mrf(self._kernel_model, xdata, y, self._atoms, lo, hi, nb, start, precision,
+                                                        n_sweeps=sp["n_sweeps"], tol=sp["tol"], log_prior=log_prior, **common))
+
+    @classmethod
+    def in_colour_order(cls, ydata, neighbours, colours, precision, keys, run):
+        """`run(y, neighbours, colour_start)` on the voxels sorted by colour (colour_sort), its per-voxel results `keys` put back
+        into the caller's order, with "delta", "n_sweeps" and `precision` beside them: the sort and un-sort both Bayes solvers use."""
+        n_pixels = ydata.shape[0]
+        order, nb, start = cls.colour_sort(neighbours, colours, n_pixels)
+        res = run(np.ascontiguousarray(ydata[order]), nb, start)
         back = np.empty(n_pixels, np.int64)
         back[order] = np.arange(n_pixels)
-        out = {k: np.ascontiguousarray(v[..., back]) for k, v in res.items() if k in ("mean", "sd", "map_p", "map_atom", "log_evidence", "ess")}
+        out = {k: np.ascontiguousarray(v[..., back]) for k, v in res.items() if k in keys}
         out.update(delta=res["delta"], n_sweeps=res["n_sweeps"], precision=precision)
         return out
 
@@ -1405,8 +1414,19 @@ class HipBayesVarProSolver(RefBaseSolver):
             posterior of every voxel under its label's table; the diagnostics are then the grid solver's per-label set:
             "log_prior" (C, n_atoms), "prior_loglik" (n_iter + 1, C), "prior_loglik_total", "prior_n_eff" (C,), "prior_labels".
             Refused by name: marginals together with labels, max_voxels with per_label, a 2-D log_prior without per_label.
+        spatial_prior: None / False (default): every voxel is judged on its own.  HipBayesGridSolver's option, the same dict,
+            rules, messages and TOML table [Fitting.solver.spatial_prior]: a pairwise Gaussian neighbourhood (MRF) prior between
+            adjacent voxels on the RATES (and a free T1), by coloured mean-field sweeps (pnx_curvefit_varpro_posterior_mrf_f64,
+            DESIGN.md 4.1q).  A numeric strength applies to the non-linear names only; {name: s} with s > 0 on a fraction or S0
+            is a ValueError (its value is solved per voxel and atom: there is no grid value to pull towards).  The precision of a
+            rate is strength / (range of its row over the admitted atoms)^2, 0 for a one-value row.  `fit` then needs
+            `neighbours` and `colours` (HipPixelWiseFitter passes api.grid_neighbours(mask, connectivity)) and returns the
+            results in the caller's order.  With a single-table empirical_prior the table is learned first, without the field.
+            Refused by name: together with a per-label or 2-D prior, or with marginals.
     After fit: params_ = the posterior mean keyed by the model's names; diagnostics_ {"posterior_sd", "map" (dicts name ->
-    (n_pixels,)), "map_atom", "log_evidence", "ess", "clipped_mass", "n_pixels"}, with marginals also {"marginal" {name: (n_bins,
+    (n_pixels,)), "map_atom", "log_evidence", "ess", "clipped_mass", "n_pixels"}, with spatial_prior also {"spatial_sweeps",
+    "spatial_delta", "spatial_precision"} as HipBayesGridSolver reports them ("log_evidence" is then the local normaliser of the
+    last update), with marginals also {"marginal" {name: (n_bins,
     n_pixels)}, "marginal_values" {name: (n_bins,)}, "quantiles" {name: (n_q, n_pixels)}, "quantile_probs", "geo_mean" {name:
     (n_pixels,)}} (the rates and a free T1 only), with empirical_prior also {"log_prior" (n_atoms,) the learned table, "prior_loglik"
     the EM's log-likelihood trace, "prior_n_iter", "prior_n_voxels"}; pixel_results_ with success = the voxel's signal was finite."""
@@ -1415,14 +1435,20 @@ class HipBayesVarProSolver(RefBaseSolver):
     _marginals_options = classmethod(HipBayesGridSolver._marginals_options.__func__)  # one set of rules and messages
     _EMPIRICAL_PRIOR_DEFAULTS = HipBayesGridSolver._EMPIRICAL_PRIOR_DEFAULTS
     _empirical_prior_options = classmethod(HipBayesGridSolver._empirical_prior_options.__func__)  # likewise
+    _SPATIAL_PRIOR_DEFAULTS = HipBayesGridSolver._SPATIAL_PRIOR_DEFAULTS
+    _spatial_prior_options = classmethod(HipBayesGridSolver._spatial_prior_options.__func__)  # likewise
+    colour_sort = staticmethod(HipBayesGridSolver.colour_sort)  # one sort by colour, one way back, for both solvers
+    in_colour_order = classmethod(HipBayesGridSolver.in_colour_order.__func__)
 
     def __init__(self, model: Any, rates=None, max_iter: int = 250, tol: float = 1e-8, p0: dict[str, float] | None = None,
                  bounds: dict[str, tuple[float, float]] | None = None, ordered: bool = True, noise_sd: float | None = None, log_prior=None,
                  marginal_amplitudes: bool = True, sigma=None, device: int = 0, io_dtype: str = "float64", precision: str = "float64",
-                 marginals=None, empirical_prior=None, **ignored_reference_kwargs):
+                 marginals=None, empirical_prior=None, spatial_prior=None, **ignored_reference_kwargs):
         RefBaseSolver.__init__(self, model=model, max_iter=max_iter, tol=tol, verbose=bool(ignored_reference_kwargs.pop("verbose", False)))
         self._kernel_model = kernel_model_key(model)
         self._kernel_t1 = kernel_t1(model)
+        self.spatial_prior = self._spatial_prior_options(self._nonlinear_strength(spatial_prior, list(model.param_names)),
+                                                         list(model.param_names))
         per_label = False
         if isinstance(empirical_prior, dict) and "per_label" in empirical_prior:  # the grid solver's option, taken out here: the
             empirical_prior = dict(empirical_prior)                               # shared classmethod knows the four others
@@ -1481,11 +1507,53 @@ class HipBayesVarProSolver(RefBaseSolver):
             raise ValueError("empirical_prior max_voxels is not built with per_label: every label learns from all of its voxels")
         if self.empirical_prior and not per_label and self.log_prior is not None and self.log_prior.ndim == 2:
             raise ValueError("empirical_prior with a 2-D log_prior needs per_label: a single learned table has no single row to start from")
+        if self.spatial_prior and self.needs_labels:
+            raise ValueError("HipBayesVarProSolver: spatial_prior is not built with per-label priors (a 2-D log_prior or empirical_prior "
+                             "per_label): pnx_curvefit_varpro_posterior_mrf_f64 takes one prior table")
+        if self.spatial_prior and self.marginals:
+            raise ValueError("HipBayesVarProSolver: spatial_prior is not built with marginals: pnx_curvefit_varpro_marginals_f64 knows no field")
 
     @property
     def needs_labels(self) -> bool:
         """True when `fit` needs `labels`: a 2-D log_prior, or empirical_prior with per_label."""
         return bool((self.log_prior is not None and self.log_prior.ndim == 2) or (self.empirical_prior and self.empirical_prior.get("per_label")))
+
+    @property
+    def needs_neighbours(self) -> bool:
+        """True when `fit` needs `neighbours` and `colours`: spatial_prior is on."""
+        return bool(self.spatial_prior)
+
+    @staticmethod
+    def _nonlinear_strength(value, names):
+        """spatial_prior with its strength spelled out per parameter: a number applies to the non-linear names (the rates, T1)
+        only; a dict that gives a fraction or S0 a positive strength is refused -- its value is solved per voxel and atom, so there
+        is no grid value to pull towards.  Everything else is left to the shared option parser."""
+        if not isinstance(value, dict) or value.get("strength") is None:
+            return value
+        st = value["strength"]
+        linear = [n for n in names if n.startswith("f") or n == "S0"]
+        if isinstance(st, dict):
+            for n in linear:
+                v = st.get(n, 0.0)
+                if isinstance(v, (int, float, np.integer, np.floating)) and not isinstance(v, bool) and v > 0:
+                    raise ValueError(f"spatial_prior strength of {n} must be 0: a fraction or S0 is solved in closed form per voxel and atom "
+                                     f"and has no grid value for a neighbourhood prior to pull towards, got {v!r}")
+            return value
+        if isinstance(st, bool) or not isinstance(st, (int, float, np.integer, np.floating)):
+            return value  # the shared parser names the fault
+        return {**value, "strength": {n: (0.0 if n in linear else st) for n in names}}
+
+    def spatial_precision(self, log_prior=None):
+        """precision (n_free,) of the spatial prior under `log_prior` (None: uniform): strength / range^2 of the row of the rate
+        atoms over the admitted atoms, 0 for a one-value row and for every fraction / S0."""
+        names = list(self.model.param_names)
+        adm = np.ones(self._nl_atoms.shape[1], bool) if log_prior is None else np.asarray(log_prior, float) > -np.inf
+        rng = self._nl_atoms[:, adm].max(axis=1) - self._nl_atoms[:, adm].min(axis=1)
+        pr = np.zeros(len(names))
+        for j, n in enumerate(self._nl_names):
+            if rng[j] > 0.0:
+                pr[names.index(n)] = self.spatial_prior["strength"][n] / rng[j] ** 2
+        return pr
 
     label_rows = staticmethod(HipBayesGridSolver.label_rows)  # one mapping from label values to rows for both solvers
 
@@ -1520,7 +1588,8 @@ class HipBayesVarProSolver(RefBaseSolver):
         res = api.varpro_posterior_classes(self._kernel_model, xdata, ydata, self._nl_atoms, lo, hi, rows, n_classes, log_prior=table, **common)
         return res, learned
 
-    def fit(self, xdata: np.ndarray, ydata: np.ndarray, pixel_fixed_params=None, labels=None, **fit_kwargs) -> "HipBayesVarProSolver":
+    def fit(self, xdata: np.ndarray, ydata: np.ndarray, pixel_fixed_params=None, labels=None, neighbours=None, colours=None,
+            **fit_kwargs) -> "HipBayesVarProSolver":
         if pixel_fixed_params:
             raise ValueError("HipBayesVarProSolver is not built with per-pixel fixed parameters (pixel_fixed_params): the dictionary "
                              "would differ from voxel to voxel")
@@ -1555,7 +1624,19 @@ class HipBayesVarProSolver(RefBaseSolver):
                                           sigma=self.sigma, device=self.device, **self._kernel_t1)
             learned["n_voxels"] = sample.shape[0]
             log_prior = learned["log_prior"]
-        if not self.needs_labels:
+        if self.spatial_prior:
+            if neighbours is None or colours is None:
+                raise ValueError("HipBayesVarProSolver: neighbours (n_pixels, n_nb) and colours (n_pixels,) are required with spatial_prior "
+                                 "(api.grid_neighbours(mask, connectivity); HipPixelWiseFitter passes them)")
+            precision, sp = self.spatial_precision(log_prior), self.spatial_prior
+            res = self.in_colour_order(
+                ydata, neighbours, colours, precision, ("mean", "sd", "map_p", "map_atom", "log_evidence", "ess", "clipped_mass"),
+                lambda y, nb, start: api.varpro_posterior_mrf(self._kernel_model, xdata, y, self._nl_atoms, lo, hi, nb, start, precision,
+                                                              n_sweeps=sp["n_sweeps"], tol=sp["tol"], log_prior=log_prior,
+                                                              noise_sd=self.noise_sd, marginal_amplitudes=self.marginal_amplitudes,
+                                                              fixed_idx=fixed_idx, fixed_vals=fixed_vals, sigma=self.sigma, device=self.device,
+                                                              **self._kernel_t1))
+        elif not self.needs_labels:
             res = api.varpro_posterior(self._kernel_model, xdata, ydata, self._nl_atoms, lo, hi, log_prior=log_prior, noise_sd=self.noise_sd,
                                        marginal_amplitudes=self.marginal_amplitudes, fixed_idx=fixed_idx, fixed_vals=fixed_vals,
                                        sigma=self.sigma, device=self.device, **self._kernel_t1)
@@ -1573,6 +1654,9 @@ class HipBayesVarProSolver(RefBaseSolver):
             if "labels" in learned:
                 self.diagnostics_.update({"prior_loglik": learned["loglik_class"], "prior_loglik_total": learned["loglik"],
                                           "prior_n_eff": learned["n_eff"], "prior_labels": [int(v) for v in learned["labels"]]})
+        if self.spatial_prior:
+            self.diagnostics_.update({"spatial_sweeps": res["n_sweeps"], "spatial_delta": res["delta"],
+                                      "spatial_precision": {n: float(res["precision"][i]) for i, n in enumerate(names)}})
         if self.marginals:
             mg = api.varpro_marginals(self._kernel_model, xdata, ydata, self._nl_atoms, lo, hi, log_prior=log_prior, noise_sd=self.noise_sd,
                                       marginal_amplitudes=self.marginal_amplitudes, quantiles=self.marginals["quantiles"], fixed_idx=fixed_idx,
