@@ -930,6 +930,50 @@ PNX_API int pnx_curvefit_varpro_posterior_mrf_f64(const pnx_curvefit_opts *opts,
                                      double *log_evidence, double *ess, double *clipped_mass, double *delta, int *n_sweeps_done,
                                      int mem, int device, void *stream);
 /*
+ * The neighbourhood (MRF) prior above with a per-row choice of the coupled quantity.  Every free non-linear row k
+ * is coupled in f_k = nl_atoms[row_k] (coupling[k] = 0, the calls above) or in f_k = log nl_atoms[row_k] (coupling[k] = 1): on a
+ * geometric rate axis the prior then pulls the neighbours' E[log theta] together, not the means that the large atoms carry.
+ *   l_g(v) = [pnx_curvefit_varpro_posterior_f64's l_g(v), term for term] + sum_k fc_kg q_vk - 1/2 n_v r_g
+ *   fc_kg = f_kg - fcentre_k      fcentre_k = min + (max - min) / 2 of f_k over the admissible atoms
+ *   q_vk = lambda_k sum_{u in N(v), present} (field_mean[k, u] - fcentre_k)   pnx_curvefit_grid_neighbour_field_f64 fed field_mean
+ *                                                                             and fcentre (0 on the fraction / S0 rows)
+ *   r_g = sum_k lambda_k fc_kg^2  (host, fp64, k ascending);   field_mean[k, v] = E_W[f_k] under the weights W behind mean
+ * mean, sd, map_p, map_atom, log_evidence, ess and clipped_mass keep their meaning and layout: the moments stay over the linear
+ * theta.  Both moment sets come out of one fold, so they describe the same weights.
+ *
+ * pnx_curvefit_varpro_posterior_logfield_f64: one colour update.  The arguments of pnx_curvefit_varpro_posterior_field_f64, and
+ *   coupling (n_free,) int32 host: 0 or 1; must be 0 on a fraction / S0 row and where precision is 0; on a log row every
+ *     admissible atom must be > 0 -- each PNX_ERR_INVALID before any device work, by name;
+ *   field_mean (n_free, n_vox) device, not NULL: written in place for the range (NaN where mean is NaN); on a coupling-0 row
+ *     (every fraction / S0 row among them) it holds the bytes of mean;
+ *     mean and field_mean must not overlap (where the fold runs in two passes the second reads back the fraction / S0 rows of
+ *     mean that the first stored);
+ *   field_q: what the gather wrote from field_mean and fcentre;
+ *   delta_max: as above with |field_mean_new[k, v] - field_mean_old[k, v]| / range(f_k); the old field_mean is read before it
+ *     is overwritten.
+ * With every coupling 0 the call returns the bytes of pnx_curvefit_varpro_posterior_field_f64; with field_q = 0 and field_n = 0, or
+ * every precision 0, the bytes of pnx_curvefit_varpro_posterior_f64, clipped_mass included.
+ *
+ * pnx_curvefit_varpro_posterior_logmrf_f64: the driver.  The arguments of pnx_curvefit_varpro_posterior_mrf_f64, its sequence,
+ * checks, refusals, PNX_MEM_HOST path and synchronisation, and coupling as above; field_mean (n_free, n_vox) host|device as `mem`
+ * or NULL.  Sweep 0 runs the same fold without a field: the bytes of pnx_curvefit_varpro_posterior_f64 for every output above and
+ * field_mean from the same weights.  The call returns the bytes of the same sequence composed from the gather and the logfield
+ * call; with every coupling 0 the bytes of pnx_curvefit_varpro_posterior_mrf_f64.
+ */
+PNX_API int pnx_curvefit_varpro_posterior_logfield_f64(const pnx_curvefit_opts *opts, int64_t n_vox, const double *b, const double *y,
+                                     int n_atoms, const double *nl_atoms, const double *fixed, const double *lo, const double *hi,
+                                     const double *log_prior, double noise_sd, int marginal_amplitudes, int64_t first, int64_t count,
+                                     const double *field_q, const int32_t *field_n, const double *precision, const int32_t *coupling,
+                                     double *mean, double *sd, int32_t *map_atom, double *map_p, double *log_evidence, double *ess,
+                                     double *clipped_mass, double *field_mean, double *delta_max, int mem, int device, void *stream);
+PNX_API int pnx_curvefit_varpro_posterior_logmrf_f64(const pnx_curvefit_opts *opts, int64_t n_vox, const double *b, const double *y,
+                                     int n_atoms, const double *nl_atoms, const double *fixed, const double *lo, const double *hi,
+                                     const double *log_prior, double noise_sd, int marginal_amplitudes, int n_nb,
+                                     const int32_t *neighbours, int n_colours, const int64_t *colour_start, const double *precision,
+                                     const int32_t *coupling, int n_sweeps, double tol, double *mean, double *sd, int32_t *map_atom,
+                                     double *map_p, double *log_evidence, double *ess, double *clipped_mass, double *field_mean,
+                                     double *delta, int *n_sweeps_done, int mem, int device, void *stream);
+/*
  * Log-linear mono-exponential fit, ln S = ln S0 - b D by (weighted) linear least squares per voxel: the ADC
  * map, step 1 of a segmented IVIM fit, a cheap source of S0 / D start values.  A closed form over one pass of the data: a voxel
  * costs its signal row in and its results out.  Per voxel, in fp64, in the order written:

@@ -60,6 +60,10 @@ SOURCE_GROUPS = {
     "varpro_mrf": ["pnx_varpro_mrf.hip", "pnx_varpro_mrf.hpp", "pnx_varpro_mrf_args.hpp", "pnx_varpro_pair.hpp", "pnx_varpro_posterior.hpp",
                    "pnx_varpro_posterior_args.hpp", "pnx_varpro.hpp", "pnx_varpro_args.hpp", "pnx_grid_mrf.hpp", "pnx_grid_mrf_args.hpp",
                    "pnx_grid_posterior.hpp", "pnx_grid_posterior_args.hpp", "pnx_grid.hpp", "pnx_grid_args.hpp"],
+    "varpro_logmrf": ["pnx_varpro_logmrf.hip", "pnx_varpro_logmrf.hpp", "pnx_varpro_logmrf_args.hpp", "pnx_varpro_mrf_args.hpp",
+                      "pnx_varpro_pair.hpp", "pnx_varpro_posterior.hpp", "pnx_varpro_posterior_args.hpp", "pnx_varpro.hpp",
+                      "pnx_varpro_args.hpp", "pnx_grid_mrf.hpp", "pnx_grid_mrf_args.hpp", "pnx_grid_posterior.hpp",
+                      "pnx_grid_posterior_args.hpp", "pnx_grid.hpp", "pnx_grid_args.hpp"],
     "loglin": ["pnx_loglin.hip", "pnx_loglin.hpp", "pnx_loglin_args.hpp", "pnx_tile.hpp"],
     "peel": ["pnx_peel.hip", "pnx_peel.hpp", "pnx_peel_args.hpp", "pnx_tile.hpp"],
     # the host boundary (streamed path, chunk ring, deferred NNLS hand-over, peak tables): host-mode / PCIe-inclusive figures and
@@ -99,6 +103,7 @@ def _units():
              ("pnx_varpro_prior.o", "pnx_varpro_prior.hip", []),
              ("pnx_varpro_class.o", "pnx_varpro_class.hip", []),
              ("pnx_varpro_mrf.o", "pnx_varpro_mrf.hip", []),
+             ("pnx_varpro_logmrf.o", "pnx_varpro_logmrf.hip", []),
              ("pnx_loglin.o", "pnx_loglin.hip", []), ("pnx_peel.o", "pnx_peel.hip", []),
              ("pnx_curvefit_f32.o", "pnx_curvefit_f32.hip", CURVEFIT_FLAGS)]
     for m in range(N_MODELS):
@@ -145,7 +150,7 @@ def _stale(unit, force: bool) -> bool:
         deps = [d for d in deps if os.path.basename(d) in ("pnx_grid_args.hpp", "pnx_grid_posterior_args.hpp") or "pnx_grid" not in os.path.basename(d)]
     elif src in ("pnx_varpro_marginal.hip", "pnx_varpro_prior.hip", "pnx_varpro_class.hip"):  # of the dictionary search's headers, the HIP-free argument halves only
         deps = [d for d in deps if os.path.basename(d).endswith("_args.hpp") or "pnx_grid" not in os.path.basename(d)]
-    elif src == "pnx_varpro_mrf.hip":  # the neighbourhood prior's headers and what they include: the dictionary search's and its posterior's
+    elif src in ("pnx_varpro_mrf.hip", "pnx_varpro_logmrf.hip"):  # the neighbourhood prior's headers and what they include: the dictionary search's and its posterior's
         deps = [d for d in deps if "pnx_grid" not in os.path.basename(d) or os.path.basename(d).split(".")[0] in (
             "pnx_grid_mrf", "pnx_grid_mrf_args", "pnx_grid_posterior", "pnx_grid_posterior_args", "pnx_grid", "pnx_grid_args")]
     elif src not in ("pnx_api.hip", "pnx_grid.hip", "pnx_grid_posterior.hip", "pnx_grid_prior.hip", "pnx_grid_marginal.hip", "pnx_grid_class.hip",
@@ -155,7 +160,7 @@ def _stale(unit, force: bool) -> bool:
         deps = [d for d in deps if os.path.basename(d) == "pnx_grid_args.hpp" or "pnx_grid" not in os.path.basename(d)]  # of those, the slab rule only
     elif src == "pnx_grid.hip":
         deps = [d for d in deps if "pnx_grid_posterior" not in os.path.basename(d)]  # the posterior's headers: its unit and the ABI's
-    if src not in ("pnx_api.hip", "pnx_grid_mrf.hip", "pnx_varpro_mrf.hip"):
+    if src not in ("pnx_api.hip", "pnx_grid_mrf.hip", "pnx_varpro_mrf.hip", "pnx_varpro_logmrf.hip"):
         deps = [d for d in deps if "pnx_grid_mrf" not in os.path.basename(d)]  # the neighbourhood prior's headers: its units and the ABI's
     if src not in ("pnx_api.hip", "pnx_grid_class.hip", "pnx_varpro_class.hip"):
         deps = [d for d in deps if "pnx_grid_class" not in os.path.basename(d)]  # the per-label prior's headers: its unit and the ABI's
@@ -169,7 +174,7 @@ def _stale(unit, force: bool) -> bool:
     if src == "pnx_varpro.hip":  # the posterior's headers and the pair function: the posterior's and the marginals' units, the ABI's
         deps = [d for d in deps if "pnx_varpro_posterior" not in os.path.basename(d) and "pnx_varpro_pair" not in os.path.basename(d)]
     elif src not in ("pnx_api.hip", "pnx_varpro_posterior.hip", "pnx_varpro_marginal.hip", "pnx_varpro_prior.hip", "pnx_varpro_class.hip",
-                     "pnx_varpro_mrf.hip"):
+                     "pnx_varpro_mrf.hip", "pnx_varpro_logmrf.hip"):
         deps = [d for d in deps if "pnx_varpro" not in os.path.basename(d)]  # the variable-projection fit's headers: likewise
     if src not in ("pnx_api.hip", "pnx_varpro_class.hip"):
         deps = [d for d in deps if "pnx_varpro_class" not in os.path.basename(d)]  # the varpro per-label prior's headers: likewise
@@ -177,8 +182,11 @@ def _stale(unit, force: bool) -> bool:
         deps = [d for d in deps if "pnx_varpro_prior" not in os.path.basename(d)]  # the varpro EM prior's headers: likewise
     if src not in ("pnx_api.hip", "pnx_varpro_marginal.hip"):
         deps = [d for d in deps if "pnx_varpro_marginal" not in os.path.basename(d)]  # the varpro marginals' headers: likewise
-    if src not in ("pnx_api.hip", "pnx_varpro_mrf.hip"):
-        deps = [d for d in deps if "pnx_varpro_mrf" not in os.path.basename(d)]  # the varpro neighbourhood prior's headers: likewise
+    if src not in ("pnx_api.hip", "pnx_varpro_mrf.hip"):  # the varpro neighbourhood prior's headers: likewise; the log coupling reads its args half
+        deps = [d for d in deps if "pnx_varpro_mrf" not in os.path.basename(d)
+                or (src == "pnx_varpro_logmrf.hip" and os.path.basename(d) == "pnx_varpro_mrf_args.hpp")]
+    if src not in ("pnx_api.hip", "pnx_varpro_logmrf.hip"):
+        deps = [d for d in deps if "pnx_varpro_logmrf" not in os.path.basename(d)]  # the log coupling's headers: likewise
     if src not in ("pnx_api.hip", "pnx_peel.hip"):
         deps = [d for d in deps if "pnx_peel" not in os.path.basename(d)]  # the peeling fit's headers: likewise
     return max(os.path.getmtime(d) for d in deps) > os.path.getmtime(o)

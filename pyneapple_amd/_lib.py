@@ -35,6 +35,7 @@ ABI_SYMBOLS = [
     "pnx_curvefit_varpro_posterior_classes_f64", "pnx_curvefit_varpro_prior_em_classes_f64",
     "pnx_curvefit_grid_neighbour_field_f64", "pnx_curvefit_grid_posterior_field_f64", "pnx_curvefit_grid_posterior_mrf_f64",
     "pnx_curvefit_varpro_posterior_field_f64", "pnx_curvefit_varpro_posterior_mrf_f64",
+    "pnx_curvefit_varpro_posterior_logfield_f64", "pnx_curvefit_varpro_posterior_logmrf_f64",
 ]
 
 
@@ -174,6 +175,15 @@ def load():
     lib.pnx_curvefit_varpro_posterior_mrf_f64.argtypes = [C.POINTER(CurvefitOpts), C.c_int64, dp, dp, C.c_int, dp, dp, dp, dp, dp, C.c_double,
                                                           C.c_int, C.c_int, vp, C.c_int, vp, dp, C.c_int, C.c_double, dp, dp, vp, dp, dp, dp, dp,
                                                           dp, C.POINTER(C.c_int), C.c_int, C.c_int, vp]
+    # the same two with coupling (int32, host) behind precision and field_mean behind clipped_mass
+    lib.pnx_curvefit_varpro_posterior_logfield_f64.restype = C.c_int
+    lib.pnx_curvefit_varpro_posterior_logfield_f64.argtypes = [C.POINTER(CurvefitOpts), C.c_int64, dp, dp, C.c_int, dp, dp, dp, dp, dp,
+                                                               C.c_double, C.c_int, C.c_int64, C.c_int64, dp, vp, dp, vp, dp, dp, vp, dp, dp,
+                                                               dp, dp, dp, dp, C.c_int, C.c_int, vp]
+    lib.pnx_curvefit_varpro_posterior_logmrf_f64.restype = C.c_int
+    lib.pnx_curvefit_varpro_posterior_logmrf_f64.argtypes = [C.POINTER(CurvefitOpts), C.c_int64, dp, dp, C.c_int, dp, dp, dp, dp, dp, C.c_double,
+                                                             C.c_int, C.c_int, vp, C.c_int, vp, dp, vp, C.c_int, C.c_double, dp, dp, vp, dp, dp,
+                                                             dp, dp, dp, dp, C.POINTER(C.c_int), C.c_int, C.c_int, vp]
     # the varpro posterior's inputs, n_iter, pseudo_count, rel_tol, log_prior_out, loglik, n_iter_done, n_eff
     lib.pnx_curvefit_varpro_prior_em_f64.restype = C.c_int
     lib.pnx_curvefit_varpro_prior_em_f64.argtypes = [C.POINTER(CurvefitOpts), C.c_int64, dp, dp, C.c_int, dp, dp, dp, dp, dp, C.c_double, C.c_int,

@@ -1137,6 +1137,129 @@ def varpro_posterior_mrf(model, b, y, nl_atoms, lo, hi, neighbours, colour_start
     return res
 
 
+def varpro_logmrf_slab_atoms(n_b, k):
+    """Atoms per LDS slab of the log-field posterior (varpro_logmrf_slab of csrc/pnx_varpro_logmrf_args.hpp): `varpro_mrf_slab_atoms`'s
+    rule with k + 1 more values per atom, the centred field rows beside the centred moment rows."""
+    kpad, k, width = (int(n_b) + 3) & ~3, int(k), 16
+    for w in range(16, 257, 16):
+        if k * kpad * (w if w & 16 else w + 16) + (k * (k + 1) + 2 * k + 4) * w + 8 <= 8192:
+            width = w
+    return width
+
+
+def _logmrf_coupling(coupling, n_free):
+    c = np.ascontiguousarray(coupling, np.int32).reshape(-1)
+    if c.shape != (n_free,):
+        raise ValueError(f"coupling has {c.size} entries for {n_free} free parameters (0: linear, 1: log)")
+    return c
+
+
+def varpro_logmrf_centre(nl_atoms, nonlinear, coupling, log_prior=None):
+    """(fcentre, frange), each (n_free,): min + (max - min) / 2 and max - min of f over the admissible atoms, f = the row of
+    nl_atoms where coupling is 0 and its logarithm where it is 1; 0 for a fraction / S0 row.  fcentre is what
+    `grid_neighbour_field` takes as `centre` in front of `varpro_posterior_logfield`; strength / frange^2 is the solver's precision."""
+    nl_atoms = np.asarray(nl_atoms, np.float64)
+    nonlinear = np.asarray(nonlinear, bool)
+    coupling = _logmrf_coupling(coupling, nonlinear.size)
+    if int(nonlinear.sum()) != nl_atoms.shape[0]:
+        raise ValueError(f"nonlinear marks {int(nonlinear.sum())} rows, nl_atoms has {nl_atoms.shape[0]}")
+    if (coupling[~nonlinear] != 0).any():
+        raise ValueError("coupling must be 0 on a fraction / S0 row")
+    adm = np.ones(nl_atoms.shape[1], bool) if log_prior is None else np.asarray(log_prior, np.float64) > -np.inf
+    centre, rng = np.zeros(nonlinear.size), np.zeros(nonlinear.size)
+    for j, k in enumerate(np.flatnonzero(nonlinear)):
+        f = nl_atoms[j, adm]
+        if coupling[k]:
+            if not (f > 0).all():
+                raise ValueError(f"coupling[{k}]=1 (log) needs positive values on row {j} of nl_atoms")
+            f = np.log(f)
+        centre[k], rng[k] = f.min() + 0.5 * (f.max() - f.min()), f.max() - f.min()
+    return centre, rng
+
+
+def varpro_posterior_logfield(model, b, y, nl_atoms, lo, hi, field_q, field_n, precision, coupling, out, *, first=0, count=None,
+                              log_prior=None, noise_sd=0.0, marginal_amplitudes=True, fixed_idx=(), fixed_vals=None, sigma=None, t1_mode=0,
+                              tr=0., tm=0., delta_max=None, device=0, stream=None):
+    """One colour update of the neighbourhood prior with a per-row linear (0) or log (1) coupling
+    (pnx_curvefit_varpro_posterior_logfield_f64; method: include/pnx.h).  `varpro_posterior_field`'s arguments, coupling (n_free,)
+    and one more required device tensor out["field_mean"] (n_free, n_vox): the mean of f under the weights behind out["mean"],
+    read (delta compares against it) and written in place.  Returns `out`."""
+    for name, t in (("y", y), ("field_q", field_q), ("field_n", field_n), ("out['mean']", (out or {}).get("mean")),
+                    ("out['field_mean']", (out or {}).get("field_mean"))):
+        if not _is_torch(t):
+            raise ValueError(f"varpro_posterior_logfield works in place on device tensors: {name} is not a torch tensor")
+    n_vox, n_b = y.shape
+    b = np.ascontiguousarray(b, np.float64)
+    if b.shape != (n_b,):
+        raise ValueError(f"b has shape {b.shape}, expected ({n_b},)")
+    o, nl_atoms, lo, hi, _, fv = _varpro_args(model, n_b, nl_atoms, lo, hi, lo, fixed_idx, fixed_vals, sigma, t1_mode, tr, tm)
+    lp = _posterior_log_prior(log_prior, nl_atoms.shape[1])
+    pr = _mrf_precision(precision, o.n_free)
+    cp = _logmrf_coupling(coupling, o.n_free)
+    count = n_vox - int(first) if count is None else int(count)
+    check(load().pnx_curvefit_varpro_posterior_logfield_f64(C.byref(o), int(n_vox), ptr(b), ptr(y), int(nl_atoms.shape[1]), ptr(nl_atoms),
+                                                            ptr(fv), ptr(lo), ptr(hi), ptr(lp), float(noise_sd), int(bool(marginal_amplitudes)),
+                                                            int(first), count, ptr(field_q), ptr(field_n), ptr(pr), ptr(cp), ptr(out["mean"]),
+                                                            ptr(out.get("sd")), ptr(out.get("map_atom")), ptr(out.get("map_p")),
+                                                            ptr(out.get("log_evidence")), ptr(out.get("ess")), ptr(out.get("clipped_mass")),
+                                                            ptr(out["field_mean"]), ptr(delta_max), MEM_DEVICE, int(device), stream))
+    return out
+
+
+def varpro_posterior_logmrf(model, b, y, nl_atoms, lo, hi, neighbours, colour_start, precision, coupling, *, n_sweeps=4, tol=0.0,
+                            log_prior=None, noise_sd=0.0, marginal_amplitudes=True, fixed_idx=(), fixed_vals=None, sigma=None, t1_mode=0,
+                            tr=0., tm=0., device=0, out=None, stream=None):
+    """`varpro_posterior_mrf` with a per-row linear (0) or log (1) coupling (pnx_curvefit_varpro_posterior_logmrf_f64; method:
+    include/pnx.h): coupling (n_free,), 0 on every fraction / S0 row and where precision is 0.  Returns `varpro_posterior_mrf`'s dict
+    with "field_mean" (n_free, n_vox): the mean of log theta on a log row, the bytes of "mean" on every other row."""
+    dev = _is_torch(y)
+    if dev != _is_torch(neighbours):
+        raise ValueError("y and neighbours must both be numpy arrays or both torch tensors")
+    if not dev:
+        _lib.require_device()
+        y = np.ascontiguousarray(np.atleast_2d(y), np.float64)
+        neighbours = np.ascontiguousarray(neighbours, np.int32)
+    n_vox, n_b = y.shape
+    b = np.ascontiguousarray(b, np.float64)
+    if b.shape != (n_b,):
+        raise ValueError(f"b has shape {b.shape}, expected ({n_b},)")
+    o, nl_atoms, lo, hi, _, fv = _varpro_args(model, n_b, nl_atoms, lo, hi, lo, fixed_idx, fixed_vals, sigma, t1_mode, tr, tm)
+    lp = _posterior_log_prior(log_prior, nl_atoms.shape[1])
+    n = o.n_free
+    if neighbours.ndim != 2 or neighbours.shape[0] != n_vox:
+        raise ValueError(f"neighbours must have shape ({n_vox}, n_nb), got {tuple(neighbours.shape)}")
+    pr = _mrf_precision(precision, n)
+    cp = _logmrf_coupling(coupling, n)
+    cs = np.ascontiguousarray(colour_start, np.int64)
+    if cs.ndim != 1 or cs.size < 2:
+        raise ValueError("colour_start must hold n_colours + 1 offsets")
+    n_sweeps = int(n_sweeps)
+    if dev:
+        import torch
+
+        mk = lambda key, shape, dt: (out or {}).get(key) if (out or {}).get(key) is not None else torch.empty(shape, dtype=dt, device=y.device)
+        res = {key: mk(key, (n, n_vox), torch.float64) for key in ("mean", "sd", "map_p", "field_mean")}
+        res["map_atom"] = mk("map_atom", (n_vox,), torch.int32)
+        for key in ("log_evidence", "ess", "clipped_mass"):
+            res[key] = mk(key, (n_vox,), torch.float64)
+    else:
+        res = {key: _out(out, key, (n, n_vox), np.float64) for key in ("mean", "sd", "map_p", "field_mean")}
+        res["map_atom"] = _out(out, "map_atom", (n_vox,), np.int32)
+        for key in ("log_evidence", "ess", "clipped_mass"):
+            res[key] = _out(out, key, (n_vox,), np.float64)
+    delta = np.full(min(max(n_sweeps, 0), GRID_MRF_MAX_SWEEPS), np.nan)  # outside 0..100 the library refuses before it writes
+    done = C.c_int(0)
+    check(load().pnx_curvefit_varpro_posterior_logmrf_f64(C.byref(o), int(n_vox), ptr(b), ptr(y), int(nl_atoms.shape[1]), ptr(nl_atoms), ptr(fv),
+                                                          ptr(lo), ptr(hi), ptr(lp), float(noise_sd), int(bool(marginal_amplitudes)),
+                                                          int(neighbours.shape[1]), ptr(neighbours), int(cs.size - 1), ptr(cs), ptr(pr), ptr(cp),
+                                                          n_sweeps, float(tol), ptr(res["mean"]), ptr(res["sd"]), ptr(res["map_atom"]),
+                                                          ptr(res["map_p"]), ptr(res["log_evidence"]), ptr(res["ess"]), ptr(res["clipped_mass"]),
+                                                          ptr(res["field_mean"]), ptr(delta), C.byref(done), MEM_DEVICE if dev else MEM_HOST,
+                                                          int(device), stream))
+    res["delta"], res["n_sweeps"] = delta, int(done.value)
+    return res
+
+
 def varpro_prior_slab_atoms(n_b, k):
     """Atoms per LDS slab of the two EM passes over the variable-projection dictionary (varpro_prior_slab of
     csrc/pnx_varpro_prior_args.hpp): the variable projection's rule with 5 more values per atom -- the log-weight and the four

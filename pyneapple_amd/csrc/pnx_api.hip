@@ -34,6 +34,7 @@
 #include "pnx_simplex.hpp"
 #include "pnx_varpro.hpp"
 #include "pnx_varpro_class.hpp"
+#include "pnx_varpro_logmrf.hpp"
 #include "pnx_varpro_mrf.hpp"
 #include "pnx_varpro_marginal.hpp"
 #include "pnx_varpro_posterior.hpp"
@@ -2282,6 +2283,186 @@ int pnx_curvefit_varpro_posterior_mrf_f64(const pnx_curvefit_opts *o, int64_t n_
     if (mem == PNX_MEM_HOST) {
         const char *ob = (const char *)out_buf.p;
         PNX_HIP(hipMemcpyAsync(mean, ob, pb, hipMemcpyDeviceToHost, st));
+        if (sd) PNX_HIP(hipMemcpyAsync(sd, ob + off_sd, pb, hipMemcpyDeviceToHost, st));
+        if (map_p) PNX_HIP(hipMemcpyAsync(map_p, ob + off_mapp, pb, hipMemcpyDeviceToHost, st));
+        if (log_evidence) PNX_HIP(hipMemcpyAsync(log_evidence, ob + off_logev, nv * 8, hipMemcpyDeviceToHost, st));
+        if (ess) PNX_HIP(hipMemcpyAsync(ess, ob + off_ess, nv * 8, hipMemcpyDeviceToHost, st));
+        if (clipped_mass) PNX_HIP(hipMemcpyAsync(clipped_mass, ob + off_cm, nv * 8, hipMemcpyDeviceToHost, st));
+        if (map_atom) PNX_HIP(hipMemcpyAsync(map_atom, ob + off_atom, nv * 4, hipMemcpyDeviceToHost, st));
+    }
+    PNX_HIP(hipStreamSynchronize(st));
+    grid_mrf_report(n_sweeps, done, trace.data(), delta, n_sweeps_done);
+    return PNX_OK;
+}
+
+// ---- the same prior with a per-row linear or log coupling (kernel: pnx_varpro_logmrf.hip, argument checks: pnx_varpro_logmrf_args.hpp)
+int pnx_curvefit_varpro_posterior_logfield_f64(const pnx_curvefit_opts *o, int64_t n_vox, const double *b, const double *y, int n_atoms,
+                                               const double *nl_atoms, const double *fixed, const double *lo, const double *hi,
+                                               const double *log_prior, double noise_sd, int marginal_amplitudes, int64_t first, int64_t count,
+                                               const double *field_q, const int32_t *field_n, const double *precision,
+                                               const int32_t *coupling, double *mean, double *sd, int32_t *map_atom, double *map_p,
+                                               double *log_evidence, double *ess, double *clipped_mass, double *field_mean,
+                                               double *delta_max, int mem, int device, void *stream) {
+    if (!o) return set_error(PNX_ERR_INVALID, "opts is NULL");
+    pnx_curvefit_opts c = *o;  // as grid start: jac_mode and the tolerances are not looked at
+    c.jac_mode = PNX_JAC_ANALYTIC;
+    c.ftol = c.xtol = c.gtol = 0.0;
+    int rc = check_curvefit_opts(&c);
+    if (rc) return rc;
+    VarproLayout L;
+    VarproPosteriorHost H;
+    VarproMrfHost M;
+    VarproLogMrfHost G;
+    if ((rc = varpro_logmrf_posterior_field_check_args(&c, n_vox, b, y, n_atoms, nl_atoms, fixed, lo, hi, log_prior, noise_sd,
+                                                       marginal_amplitudes, first, count, field_q, field_n, precision, coupling, mean,
+                                                       field_mean, mem, &L, &H, &M, &G)))
+        return rc;
+    if (n_vox == 0) return PNX_OK;
+    DeviceInfo *dev;
+    if ((rc = use_device(device, &dev))) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    AsyncBuf dict_buf, post_buf, mrf_buf;  // built once per call, stream-ordered, freed behind the work that reads them
+    VarproDict D;
+    VarproPosterior P;
+    VarproLogMrf F;
+    if ((rc = dict_buf.alloc(varpro_dict_bytes(c.n_free, L.n_nl, L.k, n_atoms, c.n_b), st))) return rc;
+    if ((rc = post_buf.alloc(varpro_posterior_bytes(L.n_nl, n_atoms), st))) return rc;
+    if ((rc = mrf_buf.alloc(varpro_logmrf_bytes(L.n_nl, n_atoms, dev->cus), st))) return rc;
+    if ((rc = varpro_dict_build(&c, L, b, n_atoms, nl_atoms, fixed, lo, dict_buf.p, &D, st))) return rc;  // no fallback: lo is not read back
+    if ((rc = varpro_posterior_prepare(D, H, log_prior, noise_sd, marginal_amplitudes, post_buf.p, &P, st))) return rc;
+    if ((rc = varpro_logmrf_prepare(D, G, nl_atoms, precision, coupling, dev->cus, mrf_buf.p, &F, st))) return rc;
+    return varpro_logmrf_posterior_device(D, P, F, true, n_vox, first, count, y, field_q, field_n, mean, sd, map_atom, map_p, log_evidence, ess,
+                                          clipped_mass, field_mean, delta_max, false, dev->cus, st);
+}
+
+int pnx_curvefit_varpro_posterior_logmrf_f64(const pnx_curvefit_opts *o, int64_t n_vox, const double *b, const double *y, int n_atoms,
+                                             const double *nl_atoms, const double *fixed, const double *lo, const double *hi,
+                                             const double *log_prior, double noise_sd, int marginal_amplitudes, int n_nb,
+                                             const int32_t *neighbours, int n_colours, const int64_t *colour_start, const double *precision,
+                                             const int32_t *coupling, int n_sweeps, double tol, double *mean, double *sd, int32_t *map_atom,
+                                             double *map_p, double *log_evidence, double *ess, double *clipped_mass, double *field_mean,
+                                             double *delta, int *n_sweeps_done, int mem, int device, void *stream) {
+    if (!o) return set_error(PNX_ERR_INVALID, "opts is NULL");
+    pnx_curvefit_opts c = *o;  // as grid start: jac_mode and the tolerances are not looked at
+    c.jac_mode = PNX_JAC_ANALYTIC;
+    c.ftol = c.xtol = c.gtol = 0.0;
+    int rc = check_curvefit_opts(&c);
+    if (rc) return rc;
+    VarproLayout L;
+    VarproPosteriorHost H;
+    VarproMrfHost M;
+    VarproLogMrfHost G;
+    if ((rc = varpro_logmrf_check_args(&c, n_vox, b, y, n_atoms, nl_atoms, fixed, lo, hi, log_prior, noise_sd, marginal_amplitudes, n_nb,
+                                       neighbours, n_colours, colour_start, precision, coupling, n_sweeps, tol, mean, mem, &L, &H, &M, &G)))
+        return rc;
+    std::vector<double> trace((size_t)n_sweeps + 1, 0.0);
+    if (n_vox == 0) {
+        grid_mrf_report(n_sweeps, 0, trace.data(), delta, n_sweeps_done);
+        return PNX_OK;
+    }
+    DeviceInfo *dev;
+    if ((rc = use_device(device, &dev))) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    const int nf = c.n_free;
+    const size_t nv = (size_t)n_vox, pb = (size_t)nf * nv * sizeof(double);
+    AsyncBuf dict_buf, post_buf, mrf_buf, q_buf, n_buf, delta_buf, y_buf, nb_buf, out_buf, fm_buf;  // stream-ordered, freed behind the work that reads them
+    VarproDict D;
+    VarproPosterior P;
+    VarproLogMrf F;
+    if ((rc = dict_buf.alloc(varpro_dict_bytes(nf, L.n_nl, L.k, n_atoms, c.n_b), st))) return rc;
+    if ((rc = post_buf.alloc(varpro_posterior_bytes(L.n_nl, n_atoms), st))) return rc;
+    if ((rc = mrf_buf.alloc(varpro_logmrf_bytes(L.n_nl, n_atoms, dev->cus), st))) return rc;
+    if ((rc = q_buf.alloc(pb, st)) || (rc = n_buf.alloc(nv * sizeof(int32_t), st)) || (rc = delta_buf.alloc(((size_t)n_sweeps + 1) * 8, st)))
+        return rc;
+    double *mean_d = mean, *sd_d = sd, *mapp_d = map_p, *logev_d = log_evidence, *ess_d = ess, *cm_d = clipped_mass, *fm_d = field_mean;
+    int32_t *atom_d = map_atom;
+    size_t off_sd = 0, off_mapp = 0, off_logev = 0, off_ess = 0, off_cm = 0, off_atom = 0, off_fm = 0, out_bytes = 0;
+    if (mem == PNX_MEM_HOST) {  // every sweep reads the same signals and table: one upload, kept for the call; the outputs in one buffer
+        const size_t yb = nv * c.n_b * sizeof(double), nbb = nv * n_nb * sizeof(int32_t);
+        out_bytes = pb;
+        off_fm = out_bytes, out_bytes += pb;  // the sweeps need the means of f whether the caller asks for them or not
+        if (sd) off_sd = out_bytes, out_bytes += pb;
+        if (map_p) off_mapp = out_bytes, out_bytes += pb;
+        if (log_evidence) off_logev = out_bytes, out_bytes += nv * 8;
+        if (ess) off_ess = out_bytes, out_bytes += nv * 8;
+        if (clipped_mass) off_cm = out_bytes, out_bytes += nv * 8;
+        if (map_atom) off_atom = out_bytes, out_bytes += nv * 4;
+        if (y_buf.alloc(yb, st) != PNX_OK || nb_buf.alloc(nbb, st) != PNX_OK || out_buf.alloc(out_bytes, st) != PNX_OK)
+            return set_error(PNX_ERR_NOMEM, "varpro posterior logmrf: no device memory for the %zu bytes of y, neighbours and the outputs (%lld "
+                                            "voxels x %d), which stay resident for all sweeps", yb + nbb + out_bytes, (long long)n_vox, c.n_b);
+        if ((rc = pnx_upload(y_buf.p, y, (int64_t)yb, device, st, 0))) return rc;
+        if ((rc = pnx_upload(nb_buf.p, neighbours, (int64_t)nbb, device, st, 0))) return rc;
+        y = (const double *)y_buf.p;
+        neighbours = (const int32_t *)nb_buf.p;
+        char *ob = (char *)out_buf.p;
+        mean_d = (double *)ob;
+        fm_d = (double *)(ob + off_fm);
+        sd_d = sd ? (double *)(ob + off_sd) : nullptr;
+        mapp_d = map_p ? (double *)(ob + off_mapp) : nullptr;
+        logev_d = log_evidence ? (double *)(ob + off_logev) : nullptr;
+        ess_d = ess ? (double *)(ob + off_ess) : nullptr;
+        cm_d = clipped_mass ? (double *)(ob + off_cm) : nullptr;
+        atom_d = map_atom ? (int32_t *)(ob + off_atom) : nullptr;
+    } else if (!fm_d) {
+        if ((rc = fm_buf.alloc(pb, st))) return rc;
+        fm_d = (double *)fm_buf.p;
+    }
+    if ((rc = varpro_dict_build(&c, L, b, n_atoms, nl_atoms, fixed, lo, dict_buf.p, &D, st))) return rc;  // no fallback: lo is not read back
+    if ((rc = varpro_posterior_prepare(D, H, log_prior, noise_sd, marginal_amplitudes, post_buf.p, &P, st))) return rc;
+    if ((rc = varpro_logmrf_prepare(D, G, nl_atoms, precision, coupling, dev->cus, mrf_buf.p, &F, st))) return rc;
+    // the colouring: no index out of range, no edge inside a colour -- argument errors, found before any sweep
+    int32_t flags[2] = {INT32_MAX, INT32_MAX};
+    if ((rc = grid_mrf_colour_check_device(n_vox, n_nb, neighbours, n_colours, colour_start, F.flags, st))) return rc;
+    PNX_HIP(hipMemcpyAsync(flags, F.flags, sizeof(flags), hipMemcpyDeviceToHost, st));
+    PNX_HIP(hipStreamSynchronize(st));
+    if (flags[0] != INT32_MAX)
+        return set_error(PNX_ERR_INVALID, "varpro posterior logmrf: neighbours of voxel %d hold an index outside [-1, %lld)", flags[0], (long long)n_vox);
+    if (flags[1] != INT32_MAX)
+        return set_error(PNX_ERR_INVALID, "varpro posterior logmrf: voxel %d has a neighbour inside its own colour range (an edge inside a colour: "
+                                          "the update would not be coordinate ascent)", flags[1]);
+    double *delta_d = (double *)delta_buf.p;
+    PNX_HIP(hipMemsetAsync(delta_d, 0, ((size_t)n_sweeps + 1) * 8, st));
+    // sweep 0: the plain posterior -- the same fold without a field, so that field_mean belongs to the weights behind mean
+    if ((rc = varpro_logmrf_posterior_device(D, P, F, false, n_vox, 0, n_vox, y, nullptr, nullptr, mean_d, sd_d, atom_d, mapp_d, logev_d, ess_d, cm_d,
+                                             fm_d, nullptr, false, dev->cus, st)))
+        return rc;
+    GridMrfFieldArgs ga;  // the grid prior's gather over the means of f: fcentre and precision are 0 on the linear rows, so q is 0 there
+    memset(&ga, 0, sizeof(ga));
+    ga.nb = neighbours;
+    ga.mean = fm_d;
+    ga.q = (double *)q_buf.p;
+    ga.n = (int32_t *)n_buf.p;
+    ga.flag = nullptr;  // checked above
+    ga.n_vox = n_vox;
+    ga.n_free = nf;
+    ga.n_nb = n_nb;
+    for (int k = 0; k < nf; ++k) {
+        ga.centre[k] = G.fcentre[k];
+        ga.precision[k] = precision[k];
+    }
+    int done = 0;
+    for (int s = 1; s <= n_sweeps; ++s) {
+        for (int col = 0; col < n_colours; ++col) {
+            ga.first = colour_start[col];
+            ga.count = colour_start[col + 1] - colour_start[col];
+            if (ga.count == 0) continue;
+            if ((rc = grid_mrf_field_device(ga, st))) return rc;
+            if ((rc = varpro_logmrf_posterior_device(D, P, F, true, n_vox, ga.first, ga.count, y, ga.q, ga.n, mean_d, sd_d, atom_d, mapp_d, logev_d,
+                                                     ess_d, cm_d, fm_d, delta_d + (s - 1), true, dev->cus, st)))
+                return rc;
+        }
+        done = s;
+        if (tol > 0.0) {  // the stopping rule needs this sweep's delta on the host; tol = 0 runs all sweeps without a round trip
+            PNX_HIP(hipMemcpyAsync(&trace[s - 1], delta_d + (s - 1), 8, hipMemcpyDeviceToHost, st));
+            PNX_HIP(hipStreamSynchronize(st));
+            if (trace[s - 1] <= tol) break;
+        }
+    }
+    if (n_sweeps > 0) PNX_HIP(hipMemcpyAsync(trace.data(), delta_d, (size_t)n_sweeps * 8, hipMemcpyDeviceToHost, st));
+    if (mem == PNX_MEM_HOST) {
+        const char *ob = (const char *)out_buf.p;
+        PNX_HIP(hipMemcpyAsync(mean, ob, pb, hipMemcpyDeviceToHost, st));
+        if (field_mean) PNX_HIP(hipMemcpyAsync(field_mean, ob + off_fm, pb, hipMemcpyDeviceToHost, st));
         if (sd) PNX_HIP(hipMemcpyAsync(sd, ob + off_sd, pb, hipMemcpyDeviceToHost, st));
         if (map_p) PNX_HIP(hipMemcpyAsync(map_p, ob + off_mapp, pb, hipMemcpyDeviceToHost, st));
         if (log_evidence) PNX_HIP(hipMemcpyAsync(log_evidence, ob + off_logev, nv * 8, hipMemcpyDeviceToHost, st));

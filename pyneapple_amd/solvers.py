@@ -1423,6 +1423,15 @@ class HipBayesVarProSolver(RefBaseSolver):
             `neighbours` and `colours` (HipPixelWiseFitter passes api.grid_neighbours(mask, connectivity)) and returns the
             results in the caller's order.  With a single-table empirical_prior the table is learned first, without the field.
             Refused by name: together with a per-label or 2-D prior, or with marginals.
+            This solver's own key "coupling" (TOML: coupling = "log" in the same table): "linear" (default: the path above, byte for
+            byte), "log", or {name: "linear" | "log"} over the non-linear names.  A log-coupled rate is pulled towards its
+            neighbours' E[log rate] (pnx_curvefit_varpro_posterior_logmrf_f64), its precision is strength /
+            (range of log rate)^2; params_ and posterior_sd stay the moments of the linear rate.  On a geometric rate axis this
+            is the coupling to use.  A fraction / S0 name, an unknown value, or a non-positive admitted rate on a log row is a
+            ValueError, and so is, from `fit`, three compartments with S0 and a free T1 above 32 b-values (no kernel form);
+            diagnostics_ gains "spatial_coupling" {name: str} and, for the log rows that carry a precision, "geo_mean" {name:
+            exp E[log rate] per pixel}.  "geo_mean" has two sources that never meet (spatial_prior with marginals is refused):
+            here E[log rate] under the field's weights, out of the fold; with `marginals` the same quantity from the marginal.
     After fit: params_ = the posterior mean keyed by the model's names; diagnostics_ {"posterior_sd", "map" (dicts name ->
     (n_pixels,)), "map_atom", "log_evidence", "ess", "clipped_mass", "n_pixels"}, with spatial_prior also {"spatial_sweeps",
     "spatial_delta", "spatial_precision"} as HipBayesGridSolver reports them ("log_evidence" is then the local normaliser of the
@@ -1447,6 +1456,7 @@ class HipBayesVarProSolver(RefBaseSolver):
         RefBaseSolver.__init__(self, model=model, max_iter=max_iter, tol=tol, verbose=bool(ignored_reference_kwargs.pop("verbose", False)))
         self._kernel_model = kernel_model_key(model)
         self._kernel_t1 = kernel_t1(model)
+        spatial_prior, self.spatial_coupling = self._coupling_option(spatial_prior, list(model.param_names))
         self.spatial_prior = self._spatial_prior_options(self._nonlinear_strength(spatial_prior, list(model.param_names)),
                                                          list(model.param_names))
         per_label = False
@@ -1512,6 +1522,12 @@ class HipBayesVarProSolver(RefBaseSolver):
                              "per_label): pnx_curvefit_varpro_posterior_mrf_f64 takes one prior table")
         if self.spatial_prior and self.marginals:
             raise ValueError("HipBayesVarProSolver: spatial_prior is not built with marginals: pnx_curvefit_varpro_marginals_f64 knows no field")
+        if self.spatial_prior and self._log_coupled():
+            adm = np.ones(self._nl_atoms.shape[1], bool) if self.log_prior is None else self.log_prior > -np.inf
+            for j, n in enumerate(self._nl_names):
+                if self.spatial_coupling[n] == "log" and not (self._nl_atoms[j, adm] > 0).all():
+                    raise ValueError(f"spatial_prior coupling of {n} is 'log', which needs positive values: its admitted atoms reach "
+                                     f"{float(self._nl_atoms[j, adm].min())!r}")
 
     @property
     def needs_labels(self) -> bool:
@@ -1522,6 +1538,36 @@ class HipBayesVarProSolver(RefBaseSolver):
     def needs_neighbours(self) -> bool:
         """True when `fit` needs `neighbours` and `colours`: spatial_prior is on."""
         return bool(self.spatial_prior)
+
+    @staticmethod
+    def _coupling_option(value, names):
+        """(spatial_prior without its "coupling" key -- this solver's only; the shared parser knows the four others --, {name:
+        "linear" | "log"} for every parameter).  "linear" (the default) and "log" apply to the non-linear names (the rates, T1); a
+        dict gives them by name.  A fraction or S0 is never coupled: naming one is refused."""
+        linear = [n for n in names if n.startswith("f") or n == "S0"]
+        coupling = {n: "linear" for n in names}
+        if not isinstance(value, dict) or "coupling" not in value:
+            return value, coupling
+        value = dict(value)
+        c = value.pop("coupling")
+        if isinstance(c, str):
+            c = {n: c for n in names if n not in linear}
+        if not isinstance(c, dict):
+            raise ValueError(f"spatial_prior coupling must be 'linear', 'log' or {{parameter name: 'linear' | 'log'}}, got {c!r}")
+        bad = sorted(set(c) - set(names))
+        if bad:
+            raise ValueError(f"spatial_prior coupling names unknown parameters {bad}; the model has {names}")
+        for n, v in c.items():
+            if n in linear:
+                raise ValueError(f"spatial_prior coupling of {n} cannot be set: a fraction or S0 is solved in closed form per voxel and atom "
+                                 "and is not coupled")
+            if not isinstance(v, str) or v not in ("linear", "log"):
+                raise ValueError(f"spatial_prior coupling of {n} must be 'linear' or 'log', got {v!r}")
+            coupling[n] = v
+        return value, coupling
+
+    def _log_coupled(self):
+        return any(v == "log" for v in self.spatial_coupling.values())
 
     @staticmethod
     def _nonlinear_strength(value, names):
@@ -1549,6 +1595,10 @@ class HipBayesVarProSolver(RefBaseSolver):
         names = list(self.model.param_names)
         adm = np.ones(self._nl_atoms.shape[1], bool) if log_prior is None else np.asarray(log_prior, float) > -np.inf
         rng = self._nl_atoms[:, adm].max(axis=1) - self._nl_atoms[:, adm].min(axis=1)
+        if self._log_coupled():  # a log-coupled row: the range of log theta
+            cp = [int(self.spatial_coupling[n] == "log") for n in names]
+            frange = api.varpro_logmrf_centre(self._nl_atoms, [n in self._nl_names for n in names], cp, log_prior)[1]
+            rng = np.array([frange[names.index(n)] for n in self._nl_names])
         pr = np.zeros(len(names))
         for j, n in enumerate(self._nl_names):
             if rng[j] > 0.0:
@@ -1609,7 +1659,10 @@ class HipBayesVarProSolver(RefBaseSolver):
         fixed_vals = np.array([float(fixed[all_names[i]]) for i in fixed_idx]) if fixed_idx else None
         lo = np.array([self.bounds[n][0] for n in names], float)
         hi = np.array([self.bounds[n][1] for n in names], float)
-        log_prior, learned = self.log_prior, None
+        if self.spatial_prior and self._log_coupled() and self._kernel_model == "tri_s0" and self._nl_atoms.shape[0] == 4 and xdata.size > 32:
+            raise ValueError(f"spatial_prior coupling 'log' is not built for three compartments with S0 and a free T1 above 32 b-values "
+                             f"(got {xdata.size}): its fold does not fit the register file; coupling 'linear' takes this layout")
+        log_prior, learned, coupled = self.log_prior, None, None
         if self.needs_labels:
             res, learned = self._fit_labelled(xdata, ydata, labels, lo, hi,
                                               dict(noise_sd=self.noise_sd, marginal_amplitudes=self.marginal_amplitudes, fixed_idx=fixed_idx,
@@ -1629,13 +1682,18 @@ class HipBayesVarProSolver(RefBaseSolver):
                 raise ValueError("HipBayesVarProSolver: neighbours (n_pixels, n_nb) and colours (n_pixels,) are required with spatial_prior "
                                  "(api.grid_neighbours(mask, connectivity); HipPixelWiseFitter passes them)")
             precision, sp = self.spatial_precision(log_prior), self.spatial_prior
+            # the flags the device sees: a row without a precision (strength 0, a one-value row) is not coupled at all
+            coupled = np.array([int(self.spatial_coupling[n] == "log" and precision[i] > 0) for i, n in enumerate(names)], np.int32)
+            call = api.varpro_posterior_mrf if not self._log_coupled() else (
+                lambda *a, **kw: api.varpro_posterior_logmrf(*a, coupled, **kw))  # all linear: the linear entry point, as before
             res = self.in_colour_order(
-                ydata, neighbours, colours, precision, ("mean", "sd", "map_p", "map_atom", "log_evidence", "ess", "clipped_mass"),
-                lambda y, nb, start: api.varpro_posterior_mrf(self._kernel_model, xdata, y, self._nl_atoms, lo, hi, nb, start, precision,
-                                                              n_sweeps=sp["n_sweeps"], tol=sp["tol"], log_prior=log_prior,
-                                                              noise_sd=self.noise_sd, marginal_amplitudes=self.marginal_amplitudes,
-                                                              fixed_idx=fixed_idx, fixed_vals=fixed_vals, sigma=self.sigma, device=self.device,
-                                                              **self._kernel_t1))
+                ydata, neighbours, colours, precision,
+                ("mean", "sd", "map_p", "map_atom", "log_evidence", "ess", "clipped_mass", "field_mean"),
+                lambda y, nb, start: call(self._kernel_model, xdata, y, self._nl_atoms, lo, hi, nb, start, precision,
+                                          n_sweeps=sp["n_sweeps"], tol=sp["tol"], log_prior=log_prior,
+                                          noise_sd=self.noise_sd, marginal_amplitudes=self.marginal_amplitudes,
+                                          fixed_idx=fixed_idx, fixed_vals=fixed_vals, sigma=self.sigma, device=self.device,
+                                          **self._kernel_t1))
         elif not self.needs_labels:
             res = api.varpro_posterior(self._kernel_model, xdata, ydata, self._nl_atoms, lo, hi, log_prior=log_prior, noise_sd=self.noise_sd,
                                        marginal_amplitudes=self.marginal_amplitudes, fixed_idx=fixed_idx, fixed_vals=fixed_vals,
@@ -1656,7 +1714,10 @@ class HipBayesVarProSolver(RefBaseSolver):
                                           "prior_n_eff": learned["n_eff"], "prior_labels": [int(v) for v in learned["labels"]]})
         if self.spatial_prior:
             self.diagnostics_.update({"spatial_sweeps": res["n_sweeps"], "spatial_delta": res["delta"],
-                                      "spatial_precision": {n: float(res["precision"][i]) for i, n in enumerate(names)}})
+                                      "spatial_precision": {n: float(res["precision"][i]) for i, n in enumerate(names)},
+                                      "spatial_coupling": dict(self.spatial_coupling)})
+            if coupled is not None and "field_mean" in res:  # exp E[log theta] of the rows the device coupled in the logarithm; NaN where mean is
+                self.diagnostics_["geo_mean"] = {n: np.exp(res["field_mean"][i]) for i, n in enumerate(names) if coupled[i]}
         if self.marginals:
             mg = api.varpro_marginals(self._kernel_model, xdata, ydata, self._nl_atoms, lo, hi, log_prior=log_prior, noise_sd=self.noise_sd,
                                       marginal_amplitudes=self.marginal_amplitudes, quantiles=self.marginals["quantiles"], fixed_idx=fixed_idx,
