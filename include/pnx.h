@@ -609,6 +609,70 @@ PNX_API int pnx_curvefit_grid_posterior_mrf_f64(const pnx_curvefit_opts *opts, i
                                    double *mean, double *sd, int32_t *map_atom, double *map_p, double *log_evidence, double *ess,
                                    double *delta, int *n_sweeps_done, int mem, int device, void *stream);
 /*
+ * An edge-preserving neighbourhood prior for pnx_curvefit_grid_posterior_f64: the Gaussian pair potential above
+ * replaced by a multivariate Student-t with dof = nu > 0 degrees of freedom, written as a Gaussian scale mixture with one latent
+ * precision tau_uv per undirected edge,
+ *   p(theta, tau) ~ prod_v pi(theta_v) prod_{edges} Gamma(tau_uv; nu/2, nu/2) tau_uv^{K/2} exp(-1/2 tau_uv sum_k lambda_k (theta_vk - theta_uk)^2),
+ * K the number of rows with lambda_k > 0.  Mean field with q = prod_v q_v prod_edges q(tau_uv) keeps the voxel update above with
+ * every neighbour weighted by w_uv = E[tau_uv] and the count n_v replaced by the weight sum W_v:
+ *   s_uv = sum_k lambda_k (sd[k, v]^2 + sd[k, u]^2 + (mean[k, v] - mean[k, u])^2)     rows with lambda_k = 0 skipped
+ *   w_uv = (nu + K) / (nu + s_uv)
+ *   q_vk = lambda_k sum_{u in N(v), present} w_uv (mean[k, u] - centre_k);   W_v = sum_{u present} w_uv
+ *   l_g(v) = [pnx_curvefit_grid_posterior_f64's l_g(v)] + sum_k thetac_kg q_vk - 1/2 W_v r_g
+ * nu -> infinity is the Gaussian prior (w = 1, W_v = n_v).  The weights are computed on the fly from the current moments in the
+ * gather of every colour update and never stored, which is exact coordinate ascent on the free energy of DESIGN.md 4.1s.
+ *
+ * pnx_curvefit_grid_neighbour_wfield_f64: the weighted gather.  The arguments of pnx_curvefit_grid_neighbour_field_f64, and
+ *   sd (n_free, n_vox): host|device as `mem`; dof: finite, > 0 (PNX_ERR_INVALID otherwise);
+ *   field_w (n_vox) double, field_n (n_vox) int32 (the present count): out, written for the range only, as field_q;
+ *   edge_weight (n_vox, n_nb) double or NULL: w_uv per slot, 0 in a slot that is not present; written for the range only.
+ * The order of operations per voxel v, in fp64 (fma: one rounding):
+ *   a voxel whose own mean[0, v] is non-finite gets q = 0, W = 0, n = 0 and every edge_weight 0;
+ *   per present slot, in slot order:  s = 0;  for k ascending with lambda_k > 0:
+ *       t = fma(sd[k,u], sd[k,u], sd[k,v] * sd[k,v]);  d = mean[k,v] - mean[k,u];  s = fma(lambda_k, fma(d, d, t), s);
+ *     w = (nu + K) / (nu + s)   (nu + K rounded once on the host);  W += w;  acc_k = fma(w, mean[k,u] - centre_k, acc_k) for every k;
+ *   q_vk = lambda_k * acc_k.
+ * Every index is checked before it is dereferenced and reported through `flag` as the Gaussian gather does; no floating-point
+ * atomics.  Beside the Gaussian gather's reads (the table, n_free means per present neighbour) it reads the sd of the neighbour's
+ * rows with lambda_k > 0 and the voxel's own mean and sd of those rows: at most (2 n_nb + 2) / n_nb of the Gaussian gather's
+ * moment bytes, twice plus the voxel's own row.
+ */
+PNX_API int pnx_curvefit_grid_neighbour_wfield_f64(int64_t n_vox, int64_t first, int64_t count, int n_free, int n_nb,
+                                   const int32_t *neighbours, const double *mean, const double *sd, const double *centre,
+                                   const double *precision, double dof, double *field_q, double *field_w, int32_t *field_n,
+                                   double *edge_weight, int32_t *flag, int mem, int device, void *stream);
+/*
+ * pnx_curvefit_grid_posterior_wfield_f64: one colour update with a real weight.  pnx_curvefit_grid_posterior_field_f64 with
+ * field_w (n_vox) double, device, in field_n's place: l = l0 + fma(-1/2 W_v, r_g, fld), W_v / 2 held in doubles.  With
+ * field_w = (double) field_n it returns the bytes of pnx_curvefit_grid_posterior_field_f64; with field_q = 0 and field_w = 0, or
+ * every precision 0 (the field is then not read), those of pnx_curvefit_grid_posterior_f64.  Everything else -- refusals, delta_max,
+ * the local normaliser, PNX_MEM_DEVICE only -- is that call's.
+ */
+PNX_API int pnx_curvefit_grid_posterior_wfield_f64(const pnx_curvefit_opts *opts, int64_t n_vox, const double *b, const double *y,
+                                   int n_atoms, const double *atoms, const double *fixed, const double *lo, const double *hi,
+                                   int project_amplitude, const double *log_prior, double noise_sd, int64_t first, int64_t count,
+                                   const double *field_q, const double *field_w, const double *precision, double *mean, double *sd,
+                                   int32_t *map_atom, double *map_p, double *log_evidence, double *ess, double *delta_max, int mem,
+                                   int device, void *stream);
+/*
+ * pnx_curvefit_grid_posterior_tmrf_f64: the driver.  pnx_curvefit_grid_posterior_mrf_f64 with dof behind precision, sd REQUIRED
+ * (the weights need the variances), and two optional outputs in front of delta:
+ *   field_w (n_vox) double, field_n (n_vox) int32, host|device as `mem`, or NULL: W_v and the present count of every voxel at its
+ *     last update; 0 for a voxel that no sweep updated (n_sweeps = 0, an empty colour).
+ * Sweep 0 is the plain posterior; sweep s runs, for each colour in order, the weighted gather and then the weighted field
+ * posterior on that colour's range.  delta, tol, the colour check, the staging of PNX_MEM_HOST and the synchronisation are the
+ * Gaussian driver's, and the call returns the bytes of the same sequence composed from the calls above.  Refused with
+ * PNX_ERR_INVALID before any device work: a non-finite or non-positive dof, a NULL sd, and everything the Gaussian driver refuses.
+ * With every precision 0 (K = 0) the result is the plain posterior's bytes.
+ */
+PNX_API int pnx_curvefit_grid_posterior_tmrf_f64(const pnx_curvefit_opts *opts, int64_t n_vox, const double *b, const double *y,
+                                   int n_atoms, const double *atoms, const double *fixed, const double *lo, const double *hi,
+                                   int project_amplitude, const double *log_prior, double noise_sd, int n_nb, const int32_t *neighbours,
+                                   int n_colours, const int64_t *colour_start, const double *precision, double dof, int n_sweeps,
+                                   double tol, double *mean, double *sd, int32_t *map_atom, double *map_p, double *log_evidence,
+                                   double *ess, double *field_w, int32_t *field_n, double *delta, int *n_sweeps_done, int mem,
+                                   int device, void *stream);
+/*
  * Marginal posterior of every free parameter over the dictionary, and credible-interval quantiles from it.  The
  * arguments up to noise_sd, the weighting, the dictionary, a_g(v), c_g(v), tol_v, l_g and every refusal are
  * pnx_curvefit_grid_posterior_f64's.  The atoms sit on a grid: along free parameter k every atom holds one of n_bins[k] values.

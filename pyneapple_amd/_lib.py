@@ -36,6 +36,7 @@ ABI_SYMBOLS = [
     "pnx_curvefit_grid_neighbour_field_f64", "pnx_curvefit_grid_posterior_field_f64", "pnx_curvefit_grid_posterior_mrf_f64",
     "pnx_curvefit_varpro_posterior_field_f64", "pnx_curvefit_varpro_posterior_mrf_f64",
     "pnx_curvefit_varpro_posterior_logfield_f64", "pnx_curvefit_varpro_posterior_logmrf_f64",
+    "pnx_curvefit_grid_neighbour_wfield_f64", "pnx_curvefit_grid_posterior_wfield_f64", "pnx_curvefit_grid_posterior_tmrf_f64",
 ]
 
 
@@ -154,6 +155,17 @@ def load():
     lib.pnx_curvefit_grid_posterior_mrf_f64.argtypes = [C.POINTER(CurvefitOpts), C.c_int64, dp, dp, C.c_int, dp, dp, dp, dp, C.c_int, dp,
                                                         C.c_double, C.c_int, vp, C.c_int, vp, dp, C.c_int, C.c_double, dp, dp, vp, dp, dp, dp,
                                                         dp, C.POINTER(C.c_int), C.c_int, C.c_int, vp]
+    # the edge-preserving (Student-t) prior: the gather with sd behind mean, dof behind precision, field_w and edge_weight; the field
+    # posterior with field_w (double) in field_n's place; the driver with dof behind precision and field_w, field_n in front of delta
+    lib.pnx_curvefit_grid_neighbour_wfield_f64.restype = C.c_int
+    lib.pnx_curvefit_grid_neighbour_wfield_f64.argtypes = [C.c_int64, C.c_int64, C.c_int64, C.c_int, C.c_int, vp, dp, dp, dp, dp, C.c_double,
+                                                           dp, dp, vp, dp, vp, C.c_int, C.c_int, vp]
+    lib.pnx_curvefit_grid_posterior_wfield_f64.restype = C.c_int
+    lib.pnx_curvefit_grid_posterior_wfield_f64.argtypes = list(lib.pnx_curvefit_grid_posterior_field_f64.argtypes)
+    lib.pnx_curvefit_grid_posterior_tmrf_f64.restype = C.c_int
+    lib.pnx_curvefit_grid_posterior_tmrf_f64.argtypes = [C.POINTER(CurvefitOpts), C.c_int64, dp, dp, C.c_int, dp, dp, dp, dp, C.c_int, dp,
+                                                         C.c_double, C.c_int, vp, C.c_int, vp, dp, C.c_double, C.c_int, C.c_double, dp, dp, vp,
+                                                         dp, dp, dp, dp, vp, dp, C.POINTER(C.c_int), C.c_int, C.c_int, vp]
     # the posterior's inputs, n_bins, bin_of, bin_value, n_q, probs, marginal, quantile, log_evidence
     lib.pnx_curvefit_grid_marginals_f64.restype = C.c_int
     lib.pnx_curvefit_grid_marginals_f64.argtypes = [C.POINTER(CurvefitOpts), C.c_int64, dp, dp, C.c_int, dp, dp, dp, dp, C.c_int, dp, C.c_double,

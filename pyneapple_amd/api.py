@@ -760,6 +760,120 @@ def grid_posterior_mrf(model, b, y, atoms, lo, hi, neighbours, colour_start, pre
     return res
 
 
+def grid_neighbour_wfield(neighbours, mean, sd, centre, precision, dof, *, first=0, count=None, out=None, flag=None, edge_weight=False,
+                          device=0, stream=None):
+    """The weighted field of the edge-preserving (Student-t) neighbourhood prior for the voxels [first, first + count)
+    (pnx_curvefit_grid_neighbour_wfield_f64; method and order of operations: include/pnx.h): per present neighbour u the weight
+    w = (dof + K) / (dof + s_uv), s_uv = sum over the rows with a precision of precision[k] (sd[k, v]^2 + sd[k, u]^2 + (mean[k, v] -
+    mean[k, u])^2); field_q[k, v] = precision[k] * sum w (mean[k, u] - centre[k]), field_w[v] = sum w, field_n[v] the present count.
+    The arguments of `grid_neighbour_field` with sd (n_free, n_vox) like mean and dof > 0.  `out`: dict with "field_q", "field_w"
+    (n_vox,) float64, "field_n" (n_vox,) int32 and optionally "edge_weight" (n_vox, n_nb) float64 -- required for tensors;
+    edge_weight=True allocates the last for arrays.  Returns that dict."""
+    dev = _is_torch(mean)
+    if dev != _is_torch(neighbours) or dev != _is_torch(sd):
+        raise ValueError("neighbours, mean and sd must all be numpy arrays or all torch tensors")
+    n_free, n_vox = mean.shape
+    if tuple(sd.shape) != (n_free, n_vox):
+        raise ValueError(f"sd must have the shape of mean ({n_free}, {n_vox}), got {tuple(sd.shape)}")
+    if tuple(neighbours.shape[:1]) != (n_vox,) or neighbours.ndim != 2:
+        raise ValueError(f"neighbours must have shape ({n_vox}, n_nb), got {tuple(neighbours.shape)}")
+    n_nb = int(neighbours.shape[1])
+    centre, pr = _mrf_precision(centre, n_free), _mrf_precision(precision, n_free)
+    count = n_vox - int(first) if count is None else int(count)
+    if dev:
+        if out is None or any(k not in out for k in ("field_q", "field_w", "field_n")):
+            raise ValueError("device tensors need out={'field_q': ..., 'field_w': ..., 'field_n': ...}")
+        res = {k: out[k] for k in ("field_q", "field_w", "field_n")}
+        if out.get("edge_weight") is not None:
+            res["edge_weight"] = out["edge_weight"]
+    else:
+        _lib.require_device()
+        neighbours = np.ascontiguousarray(neighbours, np.int32)
+        mean, sd = np.ascontiguousarray(mean, np.float64), np.ascontiguousarray(sd, np.float64)
+        res = dict(field_q=_out(out, "field_q", (n_free, n_vox), np.float64), field_w=_out(out, "field_w", (n_vox,), np.float64),
+                   field_n=_out(out, "field_n", (n_vox,), np.int32))
+        if edge_weight or (out is not None and out.get("edge_weight") is not None):
+            res["edge_weight"] = _out(out, "edge_weight", (n_vox, n_nb), np.float64)
+    check(load().pnx_curvefit_grid_neighbour_wfield_f64(n_vox, int(first), count, n_free, n_nb, ptr(neighbours), ptr(mean), ptr(sd), ptr(centre),
+                                                        ptr(pr), float(dof), ptr(res["field_q"]), ptr(res["field_w"]), ptr(res["field_n"]),
+                                                        ptr(res.get("edge_weight")), ptr(flag), MEM_DEVICE if dev else MEM_HOST, int(device),
+                                                        stream))
+    return res
+
+
+def grid_posterior_wfield(model, b, y, atoms, lo, hi, field_q, field_w, precision, out, *, first=0, count=None, log_prior=None,
+                          noise_sd=0.0, fixed_idx=(), fixed_vals=None, sigma=None, project_amplitude=False, t1_mode=0, tr=0., tm=0.,
+                          delta_max=None, device=0, stream=None):
+    """One colour update under a real weight sum (pnx_curvefit_grid_posterior_wfield_f64): `grid_posterior_field` with field_w
+    (n_vox,) float64 on the device in field_n's place, l = l0 + field - 1/2 W_v r_g.  With field_w = field_n as doubles it returns
+    the bytes of `grid_posterior_field`.  Returns `out`."""
+    for name, t in (("y", y), ("field_q", field_q), ("field_w", field_w), ("out['mean']", (out or {}).get("mean"))):
+        if not _is_torch(t):
+            raise ValueError(f"grid_posterior_wfield works in place on device tensors: {name} is not a torch tensor")
+    n_vox, n_b = y.shape
+    o, b, atoms, fv, lo, hi, lp = _mrf_host_inputs("grid_posterior_wfield", model, b, n_b, atoms, lo, hi, fixed_idx, fixed_vals, sigma, t1_mode,
+                                                   tr, tm, log_prior)
+    pr = _mrf_precision(precision, o.n_free)
+    count = n_vox - int(first) if count is None else int(count)
+    check(load().pnx_curvefit_grid_posterior_wfield_f64(C.byref(o), int(n_vox), ptr(b), ptr(y), int(atoms.shape[1]), ptr(atoms), ptr(fv), ptr(lo),
+                                                        ptr(hi), int(bool(project_amplitude)), ptr(lp), float(noise_sd), int(first), count,
+                                                        ptr(field_q), ptr(field_w), ptr(pr), ptr(out["mean"]), ptr(out.get("sd")),
+                                                        ptr(out.get("map_atom")), ptr(out.get("map_p")), ptr(out.get("log_evidence")),
+                                                        ptr(out.get("ess")), ptr(delta_max), MEM_DEVICE, int(device), stream))
+    return out
+
+
+def grid_posterior_tmrf(model, b, y, atoms, lo, hi, neighbours, colour_start, precision, dof, *, n_sweeps=4, tol=0.0, log_prior=None,
+                        noise_sd=0.0, fixed_idx=(), fixed_vals=None, sigma=None, project_amplitude=False, t1_mode=0, tr=0., tm=0., device=0,
+                        out=None, stream=None):
+    """The grid posterior under the edge-preserving (Student-t) neighbourhood prior (pnx_curvefit_grid_posterior_tmrf_f64; method:
+    include/pnx.h): `grid_posterior_mrf` with dof > 0, the degrees of freedom of the pair potential -- every
+    neighbour enters with the weight (dof + K) / (dof + s_uv), small across an edge of the image; dof -> infinity is the Gaussian
+    prior.  Returns the dict of `grid_posterior_mrf` with "field_w" (n_vox,) the weight sum and "field_n" (n_vox,) int32 the
+    present neighbours of every voxel at its last update (0 where no sweep updated it)."""
+    dev = _is_torch(y)
+    if dev != _is_torch(neighbours):
+        raise ValueError("y and neighbours must both be numpy arrays or both torch tensors")
+    if not dev:
+        _lib.require_device()
+        y = np.ascontiguousarray(np.atleast_2d(y), np.float64)
+        neighbours = np.ascontiguousarray(neighbours, np.int32)
+    n_vox, n_b = y.shape
+    o, b, atoms, fv, lo, hi, lp = _mrf_host_inputs("grid_posterior_tmrf", model, b, n_b, atoms, lo, hi, fixed_idx, fixed_vals, sigma, t1_mode, tr,
+                                                   tm, log_prior)
+    n = o.n_free
+    if neighbours.ndim != 2 or neighbours.shape[0] != n_vox:
+        raise ValueError(f"neighbours must have shape ({n_vox}, n_nb), got {tuple(neighbours.shape)}")
+    pr = _mrf_precision(precision, n)
+    cs = np.ascontiguousarray(colour_start, np.int64)
+    if cs.ndim != 1 or cs.size < 2:
+        raise ValueError("colour_start must hold n_colours + 1 offsets")
+    n_sweeps = int(n_sweeps)
+    if dev:
+        import torch
+
+        mk = lambda key, shape, dt: (out or {}).get(key) if (out or {}).get(key) is not None else torch.empty(shape, dtype=dt, device=y.device)
+        res = {key: mk(key, (n, n_vox), torch.float64) for key in ("mean", "sd", "map_p")}
+        res["map_atom"], res["field_n"] = mk("map_atom", (n_vox,), torch.int32), mk("field_n", (n_vox,), torch.int32)
+        for key in ("log_evidence", "ess", "field_w"):
+            res[key] = mk(key, (n_vox,), torch.float64)
+    else:
+        res = {key: _out(out, key, (n, n_vox), np.float64) for key in ("mean", "sd", "map_p")}
+        res["map_atom"], res["field_n"] = _out(out, "map_atom", (n_vox,), np.int32), _out(out, "field_n", (n_vox,), np.int32)
+        for key in ("log_evidence", "ess", "field_w"):
+            res[key] = _out(out, key, (n_vox,), np.float64)
+    delta = np.full(min(max(n_sweeps, 0), GRID_MRF_MAX_SWEEPS), np.nan)  # outside 0..100 the library refuses before it writes
+    done = C.c_int(0)
+    check(load().pnx_curvefit_grid_posterior_tmrf_f64(C.byref(o), int(n_vox), ptr(b), ptr(y), int(atoms.shape[1]), ptr(atoms), ptr(fv), ptr(lo),
+                                                      ptr(hi), int(bool(project_amplitude)), ptr(lp), float(noise_sd), int(neighbours.shape[1]),
+                                                      ptr(neighbours), int(cs.size - 1), ptr(cs), ptr(pr), float(dof), n_sweeps, float(tol),
+                                                      ptr(res["mean"]), ptr(res["sd"]), ptr(res["map_atom"]), ptr(res["map_p"]),
+                                                      ptr(res["log_evidence"]), ptr(res["ess"]), ptr(res["field_w"]), ptr(res["field_n"]),
+                                                      ptr(delta), C.byref(done), MEM_DEVICE if dev else MEM_HOST, int(device), stream))
+    res["delta"], res["n_sweeps"] = delta, int(done.value)
+    return res
+
+
 GRID_MARGINAL_MAX_BINS = 128  # kGridMarginalMaxBins of csrc/pnx_grid_marginal_args.hpp
 GRID_MARGINAL_MAX_PROBS = 8
 

@@ -24,6 +24,7 @@
 #include "pnx_grid_posterior.hpp"
 #include "pnx_grid_marginal.hpp"
 #include "pnx_grid_mrf.hpp"
+#include "pnx_grid_tmrf.hpp"
 #include "pnx_grid_prior.hpp"
 #include "pnx_host_pipeline.hpp"
 #include "pnx_launch.hpp"
@@ -1710,6 +1711,255 @@ int pnx_curvefit_grid_posterior_mrf_f64(const pnx_curvefit_opts *o, int64_t n_vo
         if (log_evidence) PNX_HIP(hipMemcpyAsync(log_evidence, ob + off_logev, nv * 8, hipMemcpyDeviceToHost, st));
         if (ess) PNX_HIP(hipMemcpyAsync(ess, ob + off_ess, nv * 8, hipMemcpyDeviceToHost, st));
         if (map_atom) PNX_HIP(hipMemcpyAsync(map_atom, ob + off_atom, nv * 4, hipMemcpyDeviceToHost, st));
+    }
+    PNX_HIP(hipStreamSynchronize(st));
+    grid_mrf_report(n_sweeps, done, trace.data(), delta, n_sweeps_done);
+    return PNX_OK;
+}
+
+// ---- edge-preserving (Student-t) neighbourhood prior (kernels: pnx_grid_tmrf.hip, argument checks: pnx_grid_tmrf_args.hpp)
+int pnx_curvefit_grid_neighbour_wfield_f64(int64_t n_vox, int64_t first, int64_t count, int n_free, int n_nb, const int32_t *neighbours,
+                                           const double *mean, const double *sd, const double *centre, const double *precision, double dof,
+                                           double *field_q, double *field_w, int32_t *field_n, double *edge_weight, int32_t *flag, int mem,
+                                           int device, void *stream) {
+    int rc = grid_tmrf_field_check_args(n_vox, first, count, n_free, n_nb, neighbours, mean, sd, centre, precision, dof, field_q, field_w,
+                                        field_n, mem);
+    if (rc) return rc;
+    if (n_vox == 0 || count == 0) return PNX_OK;
+    DeviceInfo *dev;
+    if ((rc = use_device(device, &dev))) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    GridTmrfFieldArgs a;
+    memset(&a, 0, sizeof(a));
+    a.n_vox = n_vox;
+    a.first = first;
+    a.count = count;
+    a.n_free = n_free;
+    a.n_nb = n_nb;
+    a.dof = dof;
+    a.dof_k = dof + grid_tmrf_rows(n_free, precision);
+    for (int k = 0; k < n_free; ++k) {
+        a.centre[k] = centre[k];
+        a.precision[k] = precision[k];
+    }
+    if (mem == PNX_MEM_DEVICE) {
+        a.nb = neighbours;
+        a.mean = mean;
+        a.sd = sd;
+        a.q = field_q;
+        a.w = field_w;
+        a.n = field_n;
+        a.edge = edge_weight;
+        a.flag = flag;
+        return grid_tmrf_field_device(a, st);
+    }
+    // host arrays: the table, the means and the sds go up whole, the range of every row comes back; the call owns the flag and reports it
+    AsyncBuf nb_buf, mean_buf, sd_buf, q_buf, w_buf, n_buf, e_buf, flag_buf;
+    const size_t nbb = (size_t)n_vox * n_nb * sizeof(int32_t), mb = (size_t)n_free * n_vox * sizeof(double);
+    const size_t eb = (size_t)n_vox * n_nb * sizeof(double);
+    if ((rc = nb_buf.alloc(nbb, st)) || (rc = mean_buf.alloc(mb, st)) || (rc = sd_buf.alloc(mb, st)) || (rc = q_buf.alloc(mb, st)) ||
+        (rc = w_buf.alloc((size_t)n_vox * sizeof(double), st)) || (rc = n_buf.alloc((size_t)n_vox * sizeof(int32_t), st)) ||
+        (rc = flag_buf.alloc(sizeof(int32_t), st)) || (edge_weight && (rc = e_buf.alloc(eb, st))))
+        return rc;
+    int32_t host_flag = INT32_MAX;
+    if ((rc = pnx_upload(nb_buf.p, neighbours, (int64_t)nbb, device, st, 0))) return rc;
+    if ((rc = pnx_upload(mean_buf.p, mean, (int64_t)mb, device, st, 0))) return rc;
+    if ((rc = pnx_upload(sd_buf.p, sd, (int64_t)mb, device, st, 0))) return rc;
+    PNX_HIP(hipMemcpyAsync(flag_buf.p, &host_flag, sizeof(int32_t), hipMemcpyHostToDevice, st));
+    a.nb = (const int32_t *)nb_buf.p;
+    a.mean = (const double *)mean_buf.p;
+    a.sd = (const double *)sd_buf.p;
+    a.q = (double *)q_buf.p;
+    a.w = (double *)w_buf.p;
+    a.n = (int32_t *)n_buf.p;
+    a.edge = edge_weight ? (double *)e_buf.p : nullptr;
+    a.flag = (int32_t *)flag_buf.p;
+    if ((rc = grid_tmrf_field_device(a, st))) return rc;
+    for (int k = 0; k < n_free; ++k)
+        PNX_HIP(hipMemcpyAsync(field_q + (size_t)k * n_vox + first, a.q + (size_t)k * n_vox + first, (size_t)count * sizeof(double),
+                               hipMemcpyDeviceToHost, st));
+    PNX_HIP(hipMemcpyAsync(field_w + first, a.w + first, (size_t)count * sizeof(double), hipMemcpyDeviceToHost, st));
+    PNX_HIP(hipMemcpyAsync(field_n + first, a.n + first, (size_t)count * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    if (edge_weight)
+        PNX_HIP(hipMemcpyAsync(edge_weight + (size_t)first * n_nb, a.edge + (size_t)first * n_nb, (size_t)count * n_nb * sizeof(double),
+                               hipMemcpyDeviceToHost, st));
+    PNX_HIP(hipMemcpyAsync(&host_flag, flag_buf.p, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    PNX_HIP(hipStreamSynchronize(st));
+    if (flag) *flag = host_flag;
+    if (host_flag != INT32_MAX)
+        return set_error(PNX_ERR_INVALID, "grid neighbour wfield: neighbours of voxel %d hold an index outside [-1, %lld)", host_flag, (long long)n_vox);
+    return PNX_OK;
+}
+
+int pnx_curvefit_grid_posterior_wfield_f64(const pnx_curvefit_opts *o, int64_t n_vox, const double *b, const double *y, int n_atoms,
+                                           const double *atoms, const double *fixed, const double *lo, const double *hi,
+                                           int project_amplitude, const double *log_prior, double noise_sd, int64_t first, int64_t count,
+                                           const double *field_q, const double *field_w, const double *precision, double *mean, double *sd,
+                                           int32_t *map_atom, double *map_p, double *log_evidence, double *ess, double *delta_max, int mem,
+                                           int device, void *stream) {
+    if (!o) return set_error(PNX_ERR_INVALID, "opts is NULL");
+    pnx_curvefit_opts c = *o;  // as grid start: jac_mode and the tolerances are not looked at
+    c.jac_mode = PNX_JAC_ANALYTIC;
+    c.ftol = c.xtol = c.gtol = 0.0;
+    int rc = check_curvefit_opts(&c);
+    if (rc) return rc;
+    GridPosteriorHost H;
+    GridMrfHost M;
+    if ((rc = grid_tmrf_posterior_field_check_args(&c, n_vox, b, y, n_atoms, atoms, fixed, lo, hi, project_amplitude, log_prior, noise_sd, first,
+                                                   count, field_q, field_w, precision, mean, mem, &H, &M)))
+        return rc;
+    if (n_vox == 0) return PNX_OK;
+    DeviceInfo *dev;
+    if ((rc = use_device(device, &dev))) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    AsyncBuf dict_buf, post_buf, mrf_buf;  // built once per call, stream-ordered, freed behind the work that reads them
+    GridDict D;
+    GridPosterior P;
+    GridMrf F;
+    if ((rc = dict_buf.alloc(grid_dict_bytes(c.n_free, n_atoms, c.n_b), st))) return rc;
+    if ((rc = post_buf.alloc(grid_posterior_bytes(c.n_free, n_atoms), st))) return rc;
+    if ((rc = mrf_buf.alloc(grid_mrf_bytes(n_atoms, dev->cus), st))) return rc;
+    if ((rc = grid_dict_build(&c, b, n_atoms, atoms, fixed, lo, hi, H.s0_row, dict_buf.p, &D, st))) return rc;
+    if ((rc = grid_posterior_prepare(D, H, log_prior, noise_sd, post_buf.p, &P, st))) return rc;
+    if ((rc = grid_mrf_prepare(D, H, M, atoms, precision, dev->cus, mrf_buf.p, &F, st))) return rc;
+    return grid_tmrf_posterior_device(D, P, F, n_vox, first, count, y, field_q, field_w, mean, sd, map_atom, map_p, log_evidence, ess, delta_max,
+                                      false, dev->cus, st);
+}
+
+int pnx_curvefit_grid_posterior_tmrf_f64(const pnx_curvefit_opts *o, int64_t n_vox, const double *b, const double *y, int n_atoms,
+                                         const double *atoms, const double *fixed, const double *lo, const double *hi, int project_amplitude,
+                                         const double *log_prior, double noise_sd, int n_nb, const int32_t *neighbours, int n_colours,
+                                         const int64_t *colour_start, const double *precision, double dof, int n_sweeps, double tol,
+                                         double *mean, double *sd, int32_t *map_atom, double *map_p, double *log_evidence, double *ess,
+                                         double *field_w, int32_t *field_n, double *delta, int *n_sweeps_done, int mem, int device,
+                                         void *stream) {
+    if (!o) return set_error(PNX_ERR_INVALID, "opts is NULL");
+    pnx_curvefit_opts c = *o;  // as grid start: jac_mode and the tolerances are not looked at
+    c.jac_mode = PNX_JAC_ANALYTIC;
+    c.ftol = c.xtol = c.gtol = 0.0;
+    int rc = check_curvefit_opts(&c);
+    if (rc) return rc;
+    GridPosteriorHost H;
+    GridMrfHost M;
+    if ((rc = grid_tmrf_check_args(&c, n_vox, b, y, n_atoms, atoms, fixed, lo, hi, project_amplitude, log_prior, noise_sd, n_nb, neighbours,
+                                   n_colours, colour_start, precision, dof, n_sweeps, tol, mean, sd, mem, &H, &M)))
+        return rc;
+    std::vector<double> trace((size_t)n_sweeps + 1, 0.0);
+    if (n_vox == 0) {
+        grid_mrf_report(n_sweeps, 0, trace.data(), delta, n_sweeps_done);
+        return PNX_OK;
+    }
+    DeviceInfo *dev;
+    if ((rc = use_device(device, &dev))) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    const int nf = c.n_free;
+    const size_t nv = (size_t)n_vox, pb = (size_t)nf * nv * sizeof(double);
+    AsyncBuf dict_buf, post_buf, mrf_buf, q_buf, w_buf, n_buf, delta_buf, y_buf, nb_buf, out_buf;  // stream-ordered, freed behind the work that reads them
+    GridDict D;
+    GridPosterior P;
+    GridMrf F;
+    if ((rc = dict_buf.alloc(grid_dict_bytes(nf, n_atoms, c.n_b), st))) return rc;
+    if ((rc = post_buf.alloc(grid_posterior_bytes(nf, n_atoms), st))) return rc;
+    if ((rc = mrf_buf.alloc(grid_mrf_bytes(n_atoms, dev->cus), st))) return rc;
+    if ((rc = q_buf.alloc(pb, st)) || (rc = delta_buf.alloc(((size_t)n_sweeps + 1) * 8, st))) return rc;
+    const bool stage = mem == PNX_MEM_HOST;
+    if ((stage || !field_w) && (rc = w_buf.alloc(nv * sizeof(double), st))) return rc;
+    if ((stage || !field_n) && (rc = n_buf.alloc(nv * sizeof(int32_t), st))) return rc;
+    double *w_d = (stage || !field_w) ? (double *)w_buf.p : field_w;  // device callers' arrays are written in place
+    int32_t *n_d = (stage || !field_n) ? (int32_t *)n_buf.p : field_n;
+    double *mean_d = mean, *sd_d = sd, *mapp_d = map_p, *logev_d = log_evidence, *ess_d = ess;
+    int32_t *atom_d = map_atom;
+    size_t off_sd = 0, off_mapp = 0, off_logev = 0, off_ess = 0, off_atom = 0, out_bytes = 0;
+    if (stage) {  // every sweep reads the same signals and table: one upload, kept for the call; the outputs in one buffer
+        const size_t yb = nv * c.n_b * sizeof(double), nbb = nv * n_nb * sizeof(int32_t);
+        out_bytes = pb;
+        off_sd = out_bytes, out_bytes += pb;
+        if (map_p) off_mapp = out_bytes, out_bytes += pb;
+        if (log_evidence) off_logev = out_bytes, out_bytes += nv * 8;
+        if (ess) off_ess = out_bytes, out_bytes += nv * 8;
+        if (map_atom) off_atom = out_bytes, out_bytes += nv * 4;
+        if (y_buf.alloc(yb, st) != PNX_OK || nb_buf.alloc(nbb, st) != PNX_OK || out_buf.alloc(out_bytes, st) != PNX_OK)
+            return set_error(PNX_ERR_NOMEM, "grid posterior tmrf: no device memory for the %zu bytes of y, neighbours and the outputs (%lld voxels x "
+                                            "%d), which stay resident for all sweeps", yb + nbb + out_bytes, (long long)n_vox, c.n_b);
+        if ((rc = pnx_upload(y_buf.p, y, (int64_t)yb, device, st, 0))) return rc;
+        if ((rc = pnx_upload(nb_buf.p, neighbours, (int64_t)nbb, device, st, 0))) return rc;
+        y = (const double *)y_buf.p;
+        neighbours = (const int32_t *)nb_buf.p;
+        char *ob = (char *)out_buf.p;
+        mean_d = (double *)ob;
+        sd_d = (double *)(ob + off_sd);
+        mapp_d = map_p ? (double *)(ob + off_mapp) : nullptr;
+        logev_d = log_evidence ? (double *)(ob + off_logev) : nullptr;
+        ess_d = ess ? (double *)(ob + off_ess) : nullptr;
+        atom_d = map_atom ? (int32_t *)(ob + off_atom) : nullptr;
+    }
+    if ((rc = grid_dict_build(&c, b, n_atoms, atoms, fixed, lo, hi, H.s0_row, dict_buf.p, &D, st))) return rc;
+    if ((rc = grid_posterior_prepare(D, H, log_prior, noise_sd, post_buf.p, &P, st))) return rc;
+    if ((rc = grid_mrf_prepare(D, H, M, atoms, precision, dev->cus, mrf_buf.p, &F, st))) return rc;
+    // the colouring: no index out of range, no edge inside a colour -- argument errors, found before any sweep
+    int32_t flags[2] = {INT32_MAX, INT32_MAX};
+    if ((rc = grid_mrf_colour_check_device(n_vox, n_nb, neighbours, n_colours, colour_start, F.flags, st))) return rc;
+    PNX_HIP(hipMemcpyAsync(flags, F.flags, sizeof(flags), hipMemcpyDeviceToHost, st));
+    PNX_HIP(hipStreamSynchronize(st));
+    if (flags[0] != INT32_MAX)
+        return set_error(PNX_ERR_INVALID, "grid posterior tmrf: neighbours of voxel %d hold an index outside [-1, %lld)", flags[0], (long long)n_vox);
+    if (flags[1] != INT32_MAX)
+        return set_error(PNX_ERR_INVALID, "grid posterior tmrf: voxel %d has a neighbour inside its own colour range (an edge inside a colour: the "
+                                          "update would not be coordinate ascent)", flags[1]);
+    double *delta_d = (double *)delta_buf.p;
+    PNX_HIP(hipMemsetAsync(delta_d, 0, ((size_t)n_sweeps + 1) * 8, st));
+    PNX_HIP(hipMemsetAsync(w_d, 0, nv * sizeof(double), st));  // a voxel no sweep updates reports W = 0, n = 0
+    PNX_HIP(hipMemsetAsync(n_d, 0, nv * sizeof(int32_t), st));
+    // sweep 0: the plain posterior
+    if ((rc = grid_posterior_device(D, P, n_vox, y, mean_d, sd_d, atom_d, mapp_d, logev_d, ess_d, dev->cus, st))) return rc;
+    GridTmrfFieldArgs ga;
+    memset(&ga, 0, sizeof(ga));
+    ga.nb = neighbours;
+    ga.mean = mean_d;
+    ga.sd = sd_d;
+    ga.q = (double *)q_buf.p;
+    ga.w = w_d;
+    ga.n = n_d;
+    ga.edge = nullptr;
+    ga.flag = nullptr;  // checked above
+    ga.n_vox = n_vox;
+    ga.n_free = nf;
+    ga.n_nb = n_nb;
+    ga.dof = dof;
+    ga.dof_k = dof + grid_tmrf_rows(nf, precision);
+    for (int k = 0; k < nf; ++k) {
+        ga.centre[k] = H.centre[k];
+        ga.precision[k] = precision[k];
+    }
+    int done = 0;
+    for (int s = 1; s <= n_sweeps; ++s) {
+        for (int col = 0; col < n_colours; ++col) {
+            ga.first = colour_start[col];
+            ga.count = colour_start[col + 1] - colour_start[col];
+            if (ga.count == 0) continue;
+            if ((rc = grid_tmrf_field_device(ga, st))) return rc;
+            if ((rc = grid_tmrf_posterior_device(D, P, F, n_vox, ga.first, ga.count, y, ga.q, ga.w, mean_d, sd_d, atom_d, mapp_d, logev_d, ess_d,
+                                                 delta_d + (s - 1), true, dev->cus, st)))
+                return rc;
+        }
+        done = s;
+        if (tol > 0.0) {  // the stopping rule needs this sweep's delta on the host; tol = 0 runs all sweeps without a round trip
+            PNX_HIP(hipMemcpyAsync(&trace[s - 1], delta_d + (s - 1), 8, hipMemcpyDeviceToHost, st));
+            PNX_HIP(hipStreamSynchronize(st));
+            if (trace[s - 1] <= tol) break;
+        }
+    }
+    if (n_sweeps > 0) PNX_HIP(hipMemcpyAsync(trace.data(), delta_d, (size_t)n_sweeps * 8, hipMemcpyDeviceToHost, st));
+    if (stage) {
+        const char *ob = (const char *)out_buf.p;
+        PNX_HIP(hipMemcpyAsync(mean, ob, pb, hipMemcpyDeviceToHost, st));
+        PNX_HIP(hipMemcpyAsync(sd, ob + off_sd, pb, hipMemcpyDeviceToHost, st));
+        if (map_p) PNX_HIP(hipMemcpyAsync(map_p, ob + off_mapp, pb, hipMemcpyDeviceToHost, st));
+        if (log_evidence) PNX_HIP(hipMemcpyAsync(log_evidence, ob + off_logev, nv * 8, hipMemcpyDeviceToHost, st));
+        if (ess) PNX_HIP(hipMemcpyAsync(ess, ob + off_ess, nv * 8, hipMemcpyDeviceToHost, st));
+        if (map_atom) PNX_HIP(hipMemcpyAsync(map_atom, ob + off_atom, nv * 4, hipMemcpyDeviceToHost, st));
+        if (field_w) PNX_HIP(hipMemcpyAsync(field_w, w_d, nv * sizeof(double), hipMemcpyDeviceToHost, st));
+        if (field_n) PNX_HIP(hipMemcpyAsync(field_n, n_d, nv * sizeof(int32_t), hipMemcpyDeviceToHost, st));
     }
     PNX_HIP(hipStreamSynchronize(st));
     grid_mrf_report(n_sweeps, done, trace.data(), delta, n_sweeps_done);

@@ -48,4 +48,7 @@ int grid_mrf_posterior_device(const GridDict &D, const GridPosterior &P, const G
                               const double *y_d, const double *field_q_d, const int32_t *field_n_d, double *mean_d, double *sd_d,
                               int32_t *map_atom_d, double *map_p_d, double *log_evidence_d, double *ess_d, double *delta_d, bool accumulate,
                               int cus, hipStream_t stream);
+// *delta_d = max over block_d[0 .. blocks) (merged with the value it holds when `accumulate`): the tail of a field posterior, shared
+// with the weighted one (pnx_grid_tmrf.hip).
+int grid_mrf_delta_device(const double *block_d, int blocks, double *delta_d, bool accumulate, hipStream_t stream);
 }  // namespace pnx
