@@ -441,6 +441,39 @@ PNX_API int pnx_curvefit_grid_posterior_f64(const pnx_curvefit_opts *opts, int64
                                     int32_t *map_atom, double *map_p, double *log_evidence, double *ess, int mem, int device,
                                     void *stream);
 /*
+ * pnx_curvefit_grid_posterior_f64 under a Rician likelihood with a known noise sd, for magnitude data.  Its
+ * arguments without project_amplitude; its dictionary, cost c_g(v), fold and outputs, term for term.  The signals are magnitudes
+ * y_i >= 0 with y_i ~ Rice(s_gi, noise_sd).  With h(z) = log(exp(-z) I0(z)) (pnx_log_i0e_f64 below) and inv = 1 / noise_sd^2:
+ *   z_vgi  = |(y_vi * s_gi) * inv|                          two multiplications in this order
+ *   C_g(v) = sum_i h(z_vgi)                                 i = 0 .. n_b - 1 ascending, one chain of additions from 0
+ *   l_g(v) = fma(-c_g(v), inv, log_prior_g) + C_g(v)        the first term is the Gaussian call's l_g (known noise), the same bytes
+ * and everything behind l_g is that call's: L, W_g, mean, sd (Welford / Chan), map_atom, map_p, ess, excluded and padded atoms.
+ *   log_evidence = (L - log sum_g exp(log_prior_g)) + K_v,  K_v = sum_i log(y_vi * inv), summed over i = kq, kq + 4, ... ascending for
+ *     kq = 0 .. 3 into p_kq, then (p_kq + p_kq^1) + (p_kq^2 + p_kq^3) (the same value for every kq).
+ *   That is log sum_g pi_g prod_i Rice(y_vi | s_gi, noise_sd) with pi the normalised prior: the Rice log-density is
+ *   log(y / sd^2) - (y^2 + s^2) / (2 sd^2) + log I0(y s / sd^2) and log I0(z) = h(z) + z, so its sum over i is K_v - c_g / sd^2 + C_g.
+ *   It is comparable between models, as the Gaussian one is.
+ * The product y . s_g stays on the fp64 matrix cores; C_g(v) is not a matrix product and runs on the fp64 vector units between
+ * the product and the fold.  The model values are taken as non-negative: a negative s_gi enters h through |z| only.
+ * A voxel with a non-finite or a NEGATIVE signal entry gets NaN in every floating output and map_atom = -1; its neighbours are not
+ * affected.  A zero entry is allowed: h(0) = 0, log_evidence is -inf and every other output stays finite.
+ * PNX_ERR_INVALID before any device work: everything pnx_curvefit_grid_posterior_f64 refuses, and noise_sd <= 0 or non-finite (a
+ * marginalised noise scale has no closed form under this likelihood).  PNX_ERR_UNSUPPORTED, by name: opts->sigma (per-b-value
+ * weights: the Rice density has one sd).  The amplitude cannot be projected under this likelihood (the optimum has no closed form
+ * and the likelihood is not Gaussian in it): a free S0 must sit on the grid as a row of `atoms`.
+ * No floating-point atomics; the outputs are the same bytes from call to call and for PNX_MEM_HOST and PNX_MEM_DEVICE.
+ */
+PNX_API int pnx_curvefit_grid_posterior_rician_f64(const pnx_curvefit_opts *opts, int64_t n_vox, const double *b, const double *y,
+                                           int n_atoms, const double *atoms, const double *fixed, const double *lo, const double *hi,
+                                           const double *log_prior, double noise_sd, double *mean, double *sd, int32_t *map_atom,
+                                           double *map_p, double *log_evidence, double *ess, int mem, int device, void *stream);
+/*
+ * out[i] = h(z[i]) = log(exp(-z[i]) I0(z[i])), the log of the exponentially scaled modified Bessel function of order zero, one lane
+ * per element (csrc/pnx_bessel.hpp: four polynomial pieces, split at 2, 4 and 8, the last behind -log(2 pi z) / 2).  Finite for
+ * 0 <= z <= 1e300 with |error| <= 4.5 * 2^-52 max(|h|, 1); h(0) = 0; a negative or NaN input gives NaN.  z, out (n,) host|device.
+ */
+PNX_API int pnx_log_i0e_f64(int64_t n, const double *z, double *out, int mem, int device, void *stream);
+/*
  * The prior of pnx_curvefit_grid_posterior_f64 learned from the volume itself (empirical Bayes): the
  * non-parametric maximum-likelihood mixture over the dictionary, by EM.  The arguments up to noise_sd, the weighting, the refusals
  * and l_g are pnx_curvefit_grid_posterior_f64's.  With pi the current prior (log_prior_g = log pi_g inside l_g), one update is

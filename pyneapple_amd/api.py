@@ -353,6 +353,88 @@ def grid_posterior_device(opts, n_vox, b, y, atoms, fixed, lo, hi, project_ampli
                                                  ptr(map_atom), ptr(map_p), ptr(log_evidence), ptr(ess), MEM_DEVICE, int(device), stream))
 
 
+def grid_rician_slab_atoms(n_b, n_free):
+    """Atoms per LDS slab of the Rician posterior kernel (grid_rician_slab of csrc/pnx_grid_rician_args.hpp): the posterior's rule
+    with the signal rows of the block's waves (4 up to 32 b-values, 2 beyond; 16 rows of n_b padded to 4, plus 2, each) taken out of
+    the 64 KB first."""
+    kpad, width = (int(n_b) + 3) & ~3, 16
+    room = 8192 - (4 if kpad <= 32 else 2) * 16 * (kpad + 2)
+    for w in range(16, 257, 16):
+        if kpad * (w if w & 16 else w + 16) + (3 + int(n_free)) * w <= room:
+            width = w
+    return width
+
+
+def log_i0e(z, *, device=0, out=None, stream=None):
+    """h(z) = log(exp(-z) I0(z)), the log of the exponentially scaled modified Bessel function of order zero, on the device
+    (pnx_log_i0e_f64; csrc/pnx_bessel.hpp).  z: a float64 numpy array of any shape -- returns an array of that shape (`out`: optional
+    preallocated result) --, or an HBM-resident float64 torch tensor with `out` a tensor of the same size (asynchronous on `stream`;
+    returns `out`).  z >= 0 up to 1e300; a negative or NaN entry gives NaN."""
+    _lib.require_device()
+    if isinstance(z, np.ndarray) or not hasattr(z, "data_ptr"):
+        z = np.ascontiguousarray(z, np.float64)
+        res = _out({"h": out} if out is not None else None, "h", z.shape, np.float64)
+        check(load().pnx_log_i0e_f64(int(z.size), ptr(z), ptr(res), MEM_HOST, int(device), None))
+        return res
+    if out is None or out.numel() != z.numel():
+        raise ValueError("log_i0e on a device tensor takes `out`, a float64 device tensor of the same size")
+    check(load().pnx_log_i0e_f64(int(z.numel()), ptr(z), ptr(out), MEM_DEVICE, int(device), stream))
+    return out
+
+
+def grid_posterior_rician(model, b, y, atoms, lo, hi, *, noise_sd, log_prior=None, fixed_idx=(), fixed_vals=None, sigma=None, t1_mode=0,
+                          tr=0., tm=0., device=0, out=None):
+    """`grid_posterior` under a Rician likelihood with a known noise sd, for magnitude signals y >= 0 on host (numpy) arrays
+    (pnx_curvefit_grid_posterior_rician_f64; method: include/pnx.h).  The arguments of `grid_posterior` without project_amplitude
+    (a free S0 sits on the grid as a row of `atoms`); noise_sd: the noise sd of the real and imaginary channels, finite and > 0
+    (required: a marginalised noise scale is not built); sigma is refused by the library, by name.  Returns `grid_posterior`'s dict;
+    log_evidence is log sum_g pi_g prod_i Rice(y_i | s_gi, noise_sd).  A voxel with a negative or non-finite entry gets NaN and
+    map_atom = -1; a zero entry gives log_evidence = -inf and finite moments."""
+    _lib.require_device()
+    b = np.ascontiguousarray(b, np.float64)
+    y = np.ascontiguousarray(np.atleast_2d(y), np.float64)
+    n_vox, n_b = y.shape
+    if b.shape != (n_b,):
+        raise ValueError(f"b has shape {b.shape}, expected ({n_b},)")
+    atoms, lo, hi = (np.ascontiguousarray(a, np.float64) for a in (atoms, lo, hi))
+    fv = None
+    if len(fixed_idx):
+        fv = np.ascontiguousarray(fixed_vals, np.float64)
+        if fv.ndim != 1:
+            raise ValueError("grid_posterior_rician takes shared fixed values (n_fixed,): per-voxel fixed maps are not built")
+    o = make_opts(model, n_b, fixed_idx, jac="analytic", t1_mode=t1_mode, tr=tr, tm=tm, sigma=sigma)
+    n = o.n_free
+    if atoms.ndim != 2 or atoms.shape[0] != n or lo.shape != (n,) or hi.shape != (n,):
+        raise ValueError(f"atoms must have shape ({n}, n_atoms), lo / hi ({n},)")
+    if fv is not None and fv.shape != (o.n_fixed,):
+        raise ValueError("fixed_vals has the wrong shape")
+    lp = _posterior_log_prior(log_prior, atoms.shape[1])
+    res = {key: _out(out, key, (n, n_vox), np.float64) for key in ("mean", "sd", "map_p")}
+    res["map_atom"] = _out(out, "map_atom", (n_vox,), np.int32)
+    res["log_evidence"] = _out(out, "log_evidence", (n_vox,), np.float64)
+    res["ess"] = _out(out, "ess", (n_vox,), np.float64)
+    check(load().pnx_curvefit_grid_posterior_rician_f64(C.byref(o), n_vox, ptr(b), ptr(y), int(atoms.shape[1]), ptr(atoms), ptr(fv), ptr(lo),
+                                                        ptr(hi), ptr(lp), float(noise_sd), ptr(res["mean"]), ptr(res["sd"]),
+                                                        ptr(res["map_atom"]), ptr(res["map_p"]), ptr(res["log_evidence"]), ptr(res["ess"]),
+                                                        MEM_HOST, int(device), None))
+    return res
+
+
+def grid_posterior_rician_device(opts, n_vox, b, y, atoms, fixed, lo, hi, log_prior, noise_sd, mean, sd, map_atom, map_p, log_evidence, ess,
+                                 device, stream=None):
+    """Enqueue the Rician grid posterior on HBM-resident float64 torch tensors (asynchronous; caller synchronises): the tensors and
+    host arrays of `grid_posterior_device`, without project_amplitude.  `opts` from make_opts."""
+    b, atoms, lo, hi = (np.ascontiguousarray(a, np.float64) for a in (b, atoms, lo, hi))
+    if fixed is not None:
+        fixed = np.ascontiguousarray(fixed, np.float64)
+    if atoms.ndim != 2:
+        raise ValueError("atoms must have shape (n_free, n_atoms)")
+    lp = _posterior_log_prior(log_prior, atoms.shape[1])
+    check(load().pnx_curvefit_grid_posterior_rician_f64(C.byref(opts), int(n_vox), ptr(b), ptr(y), int(atoms.shape[1]), ptr(atoms), ptr(fixed),
+                                                        ptr(lo), ptr(hi), ptr(lp), float(noise_sd), ptr(mean), ptr(sd), ptr(map_atom),
+                                                        ptr(map_p), ptr(log_evidence), ptr(ess), MEM_DEVICE, int(device), stream))
+
+
 def grid_prior_slab_atoms(n_b):
     """Atoms per LDS slab of the two EM passes (grid_prior_slab of csrc/pnx_grid_prior_args.hpp): the posterior's slab at four
     parameter rows -- the four wave-private rows of the accumulate pass take the place of the parameter values."""

@@ -22,6 +22,7 @@
 #include "pnx_grid_args.hpp"
 #include "pnx_grid_class.hpp"
 #include "pnx_grid_posterior.hpp"
+#include "pnx_grid_rician.hpp"
 #include "pnx_grid_marginal.hpp"
 #include "pnx_grid_mrf.hpp"
 #include "pnx_grid_tmrf.hpp"
@@ -1300,6 +1301,63 @@ int pnx_curvefit_grid_posterior_f64(const pnx_curvefit_opts *o, int64_t n_vox, c
         return grid_posterior_device(D, P, (int64_t)n, S.d(GP_Y), S.d(GP_MEAN), S.d(GP_SD), (int32_t *)S.dev[GP_ATOM], S.d(GP_MAPP), S.d(GP_LOGEV),
                                      S.d(GP_ESS), dev->cus, s);
     });
+}
+
+// ---- posterior under a Rician likelihood (kernels: pnx_grid_rician.hip, argument checks: pnx_grid_rician_args.hpp) -------------
+int pnx_curvefit_grid_posterior_rician_f64(const pnx_curvefit_opts *o, int64_t n_vox, const double *b, const double *y, int n_atoms,
+                                           const double *atoms, const double *fixed, const double *lo, const double *hi,
+                                           const double *log_prior, double noise_sd, double *mean, double *sd, int32_t *map_atom,
+                                           double *map_p, double *log_evidence, double *ess, int mem, int device, void *stream) {
+    if (!o) return set_error(PNX_ERR_INVALID, "opts is NULL");
+    pnx_curvefit_opts c = *o;  // as grid start: jac_mode and the tolerances are not looked at
+    c.jac_mode = PNX_JAC_ANALYTIC;
+    c.ftol = c.xtol = c.gtol = 0.0;
+    int rc = check_curvefit_opts(&c);
+    if (rc) return rc;
+    GridPosteriorHost H;
+    if ((rc = grid_rician_check_args(&c, n_vox, b, y, n_atoms, atoms, fixed, lo, hi, log_prior, noise_sd, mean, mem, &H))) return rc;
+    if (n_vox == 0) return PNX_OK;
+    DeviceInfo *dev;
+    if ((rc = use_device(device, &dev))) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    AsyncBuf dict_buf, post_buf;  // built once per call, stream-ordered, freed behind the work that reads them
+    GridDict D;
+    GridPosterior P;
+    if ((rc = dict_buf.alloc(grid_dict_bytes(c.n_free, n_atoms, c.n_b), st))) return rc;
+    if ((rc = post_buf.alloc(grid_posterior_bytes(c.n_free, n_atoms), st))) return rc;
+    if ((rc = grid_dict_build(&c, b, n_atoms, atoms, fixed, lo, hi, -1, dict_buf.p, &D, st))) return rc;
+    if ((rc = grid_posterior_prepare(D, H, log_prior, noise_sd, post_buf.p, &P, st))) return rc;
+    if (mem == PNX_MEM_DEVICE) return grid_rician_posterior_device(D, P, n_vox, y, mean, sd, map_atom, map_p, log_evidence, ess, dev->cus, st);
+    PNX_HIP(hipStreamSynchronize(st));  // the ring's streams read the dictionary: complete before the first chunk starts
+    enum { GP_Y, GP_MEAN, GP_SD, GP_ATOM, GP_MAPP, GP_LOGEV, GP_ESS };
+    ArrayTable A;
+    A.add(y, sizeof(double), c.n_b, false);
+    A.add(mean, sizeof(double), c.n_free, true).pmajor = true;
+    A.add(sd, sizeof(double), c.n_free, true).pmajor = true;
+    A.add(map_atom, sizeof(int32_t), 1, true);
+    A.add(map_p, sizeof(double), c.n_free, true).pmajor = true;
+    A.add(log_evidence, sizeof(double), 1, true);
+    A.add(ess, sizeof(double), 1, true);
+    return ring_call(A, (size_t)n_vox, 3 << 18, device, st, [&](size_t n, const DevSet &S, hipStream_t s) {
+        return grid_rician_posterior_device(D, P, (int64_t)n, S.d(GP_Y), S.d(GP_MEAN), S.d(GP_SD), (int32_t *)S.dev[GP_ATOM], S.d(GP_MAPP),
+                                            S.d(GP_LOGEV), S.d(GP_ESS), dev->cus, s);
+    });
+}
+
+int pnx_log_i0e_f64(int64_t n, const double *z, double *out, int mem, int device, void *stream) {
+    int rc = log_i0e_check_args(n, z, out, mem);
+    if (rc) return rc;
+    if (n == 0) return PNX_OK;
+    DeviceInfo *dev;
+    if ((rc = use_device(device, &dev))) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    if (mem == PNX_MEM_DEVICE) return log_i0e_device(n, z, out, st);
+    enum { LI_Z, LI_OUT };
+    ArrayTable A;
+    A.add(z, sizeof(double), 1, false);
+    A.add(out, sizeof(double), 1, true);
+    return ring_call(A, (size_t)n, 3 << 18, device, st,
+                     [&](size_t m, const DevSet &S, hipStream_t s) { return log_i0e_device((int64_t)m, S.d(LI_Z), S.d(LI_OUT), s); });
 }
 
 // ---- the prior over the dictionary learned from the volume (kernels: pnx_grid_prior.hip, argument checks: pnx_grid_prior_args.hpp)

@@ -63,6 +63,16 @@ def make_numpy(model: str, n_vox: int, n_b: int, sigma: float = 0.01, seed: int 
     return b, np.ascontiguousarray(y), P
 
 
+def rician_magnitude(clean, noise_sd: float, seed: int = SEED) -> np.ndarray:
+    """Magnitude data from a noise-free volume: |m + noise_sd n1 + i noise_sd n2| with n1, n2 independent standard normal draws
+    of `clean`'s shape from a generator seeded with `seed` (n1 first, then n2) -- every entry follows Rice(m, noise_sd)."""
+    clean = np.asarray(clean, np.float64)
+    rng = np.random.default_rng(seed)
+    n1 = rng.standard_normal(clean.shape)
+    n2 = rng.standard_normal(clean.shape)
+    return np.ascontiguousarray(np.hypot(clean + noise_sd * n1, noise_sd * n2))
+
+
 ROW_CHUNK = 1 << 18  # rows per independently seeded block of a synthetic volume
 
 
