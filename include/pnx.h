@@ -474,6 +474,53 @@ PNX_API int pnx_curvefit_grid_posterior_rician_f64(const pnx_curvefit_opts *opts
  */
 PNX_API int pnx_log_i0e_f64(int64_t n, const double *z, double *out, int mem, int device, void *stream);
 /*
+ * A second, fine grid per voxel and the posterior fold on it: resolution where a voxel's posterior sits, for a
+ * caller that has a coarse posterior (pnx_curvefit_grid_posterior_f64) and forms a box around its mean.  No dictionary is shared:
+ * every voxel builds its own atoms from its centre and half-width.  opts, n_vox, b, y, fixed, lo, hi, project_amplitude as the
+ * posterior call takes them; noise_sd > 0: known noise, <= 0: marginalised (Jeffreys), non-finite: PNX_ERR_INVALID.
+ *   n_points (n_free,) int32 host, each in [1, 9]; their product, the most atoms a voxel can have, at most 4096; 1 on a projected S0 row;
+ *   centre, half_width (n_free, n_vox) host|device as `mem` (the rows of a projected S0 are not read).
+ * Per voxel v, in fp64, in this order:
+ *   axis of free row k (m = n_points[k], c = centre[k, v], h = half_width[k, v]):
+ *     a = max(lo_k, c - h), b = min(hi_k, c + h);  m == 1 or not (b > a): the single value min(max(c, lo_k), hi_k);
+ *     else step = (b - a) / (m - 1), x_j = fma(j, step, a) for j < m - 1 and x_{m-1} = b (no value leaves [lo_k, hi_k]).
+ *     A fixed parameter is an axis of its one value; a projected S0 is an axis of the value 1.
+ *   atoms: the Cartesian product of the axes in the model's parameter order, the first row slowest; index g counts them.
+ *   admitted atoms (the fraction-sum rule): the implied last fraction of a reduced layout may not be negative -- f1 <= 1 for
+ *     [f1, D1, D2 (, S0)], f1 + f2 <= 1 (one addition) for [f1, D1, f2, D2, D3 (, S0)], fixed fractions included; every atom of the
+ *     other layouts is admitted.  This is the feasible set of pnx_curvefit_simplex_f64.  The coarse grid builders admit whatever
+ *     lies inside lo / hi, so a box around a coarse mean can reach across the face f1 + f2 = 1 even where no coarse atom does; the
+ *     atoms beyond it are dropped here.  The prior is uniform over the admitted atoms.
+ *   s_gi = model(b_i; atom_g) with E = exp(-b_i x) taken from a per-voxel table of the rate axes (the fit's own exp and argument);
+ *   project_amplitude: dot = sum_i fma(y_i, s_gi, .), nrm = sum_i fma(s_gi, s_gi, .), i ascending, with S0 = 1;
+ *     a_g = min(max(dot / nrm, lo_S0), hi_S0), lo_S0 when nrm == 0;  d_i = fma(-a_g, s_gi, y_i);   otherwise d_i = y_i - s_gi;
+ *   c_g = 0.5 * sum_i fma(d_i, d_i, .), i ascending from 0: the DIRECT cost.  The expanded form 1/2 ||y||^2 - y . s + 1/2 ||s||^2 is not
+ *     used: its cancellation term is what a fine grid at high SNR would run into.
+ *   l_g = -c_g / noise_sd^2  (known noise);   l_g = -(nu / 2) log(max(c_g, tol_v))  (marginalised; nu = n_b, n_b - 1 with projection;
+ *     tol_v = max(4 n_b 2^-52 ||y_v||^2, 2^-1022), a floor against log 0 only: the direct cost has no cancellation to bound);
+ *   the fold is the posterior call's: each of 64 lanes takes the atoms g = lane, lane + 64, ... through a running log-sum-exp and
+ *     weighted Welford moments about the clipped centre, then a Chan merge over the lanes (xor 32, 16, ..., 1).
+ *   mean, sd, map_p (the values of the atom with the largest l, the lowest index among equals; a_g in a projected S0 row), ess as
+ *     the posterior call; log_norm = L - log(number of admitted atoms): the log of the MEAN weight over the voxel's own atoms -- a local
+ *     normaliser, NOT an evidence (the box differs from voxel to voxel and from level to level);
+ *   edge_mass[k] = sum of W_g over the atoms on the first or last value of row k, 0 for a one-value row: near 0 the box holds the
+ *     posterior, large values say the box truncates it.
+ * A voxel with a non-finite signal, a non-finite centre or half-width, or a negative half-width gets NaN in every output, and so
+ * does a voxel none of whose atoms is admitted; its neighbours are not affected.  An atom whose cost overflows has l = -inf and
+ * weight 0; when that holds for every admitted atom of a voxel (a finite but enormous signal under known noise) the weights are
+ * equal: log_norm = -inf, ess = the number of admitted atoms, mean and sd those of the uniform distribution over them, map_p the
+ *   first admitted atom.
+ *   mean, sd, map_p, edge_mass (n_free, n_vox); ess, log_norm (n_vox): out, host|device as `mem`; all but mean may be NULL.
+ * PNX_ERR_INVALID before any device work: n_points outside [1, 9] or spanning more than 4096 atoms, more than one point on a
+ * projected S0 row, bounds that are not finite with lo <= hi, a NULL pointer, projection without a free S0.  PNX_ERR_UNSUPPORTED, by
+ * name: opts->sigma, the T1 / STEAM factor (t1_mode: T1 would need a table of its own), per_voxel_p0_bounds, fixed_per_voxel, queue_order.
+ * No floating-point atomics; the outputs are the same bytes from call to call and for PNX_MEM_HOST and PNX_MEM_DEVICE.
+ */
+PNX_API int pnx_curvefit_grid_refine_f64(const pnx_curvefit_opts *opts, int64_t n_vox, const double *b, const double *y, const double *fixed,
+                                 const double *lo, const double *hi, int project_amplitude, double noise_sd, const int32_t *n_points,
+                                 const double *centre, const double *half_width, double *mean, double *sd, double *map_p, double *ess,
+                                 double *log_norm, double *edge_mass, int mem, int device, void *stream);
+/*
  * The prior of pnx_curvefit_grid_posterior_f64 learned from the volume itself (empirical Bayes): the
  * non-parametric maximum-likelihood mixture over the dictionary, by EM.  The arguments up to noise_sd, the weighting, the refusals
  * and l_g are pnx_curvefit_grid_posterior_f64's.  With pi the current prior (log_prior_g = log pi_g inside l_g), one update is

@@ -46,6 +46,7 @@ SOURCE_GROUPS = {
                   "pnx_grid_mrf_args.hpp", "pnx_grid_posterior.hpp", "pnx_grid_posterior_args.hpp", "pnx_grid.hpp", "pnx_grid_args.hpp"],
     "grid_rician": ["pnx_grid_rician.hip", "pnx_grid_rician.hpp", "pnx_grid_rician_args.hpp", "pnx_bessel.hpp", "pnx_grid_posterior.hpp",
                     "pnx_grid_posterior_args.hpp", "pnx_grid.hpp", "pnx_grid_args.hpp"],
+    "grid_refine": ["pnx_grid_refine.hip", "pnx_grid_refine.hpp", "pnx_grid_refine_args.hpp", "pnx_grid_args.hpp", "pnx_curvefit_kernel.hpp"],
     "grid_marginal": ["pnx_grid_marginal.hip", "pnx_grid_marginal.hpp", "pnx_grid_marginal_args.hpp", "pnx_grid_prior.hpp",
                       "pnx_grid_prior_args.hpp", "pnx_grid_posterior.hpp", "pnx_grid_posterior_args.hpp", "pnx_grid.hpp", "pnx_grid_args.hpp"],
     "varpro": ["pnx_varpro.hip", "pnx_varpro.hpp", "pnx_varpro_args.hpp", "pnx_grid_args.hpp", "pnx_predict.hpp"],
@@ -101,7 +102,7 @@ def _units():
              ("pnx_grid_posterior.o", "pnx_grid_posterior.hip", []), ("pnx_grid_prior.o", "pnx_grid_prior.hip", []),
              ("pnx_grid_marginal.o", "pnx_grid_marginal.hip", []), ("pnx_grid_class.o", "pnx_grid_class.hip", []),
              ("pnx_grid_mrf.o", "pnx_grid_mrf.hip", []), ("pnx_grid_tmrf.o", "pnx_grid_tmrf.hip", []),
-             ("pnx_grid_rician.o", "pnx_grid_rician.hip", []),
+             ("pnx_grid_rician.o", "pnx_grid_rician.hip", []), ("pnx_grid_refine.o", "pnx_grid_refine.hip", []),
              ("pnx_varpro.o", "pnx_varpro.hip", []),
              ("pnx_varpro_posterior.o", "pnx_varpro_posterior.hip", []),
              ("pnx_varpro_marginal.o", "pnx_varpro_marginal.hip", []),
@@ -159,7 +160,7 @@ def _stale(unit, force: bool) -> bool:
         deps = [d for d in deps if "pnx_grid" not in os.path.basename(d) or os.path.basename(d).split(".")[0] in (
             "pnx_grid_mrf", "pnx_grid_mrf_args", "pnx_grid_posterior", "pnx_grid_posterior_args", "pnx_grid", "pnx_grid_args")]
     elif src not in ("pnx_api.hip", "pnx_grid.hip", "pnx_grid_posterior.hip", "pnx_grid_prior.hip", "pnx_grid_marginal.hip", "pnx_grid_class.hip",
-                     "pnx_grid_mrf.hip", "pnx_grid_tmrf.hip", "pnx_grid_rician.hip", "pnx_varpro.hip"):
+                     "pnx_grid_mrf.hip", "pnx_grid_tmrf.hip", "pnx_grid_rician.hip", "pnx_grid_refine.hip", "pnx_varpro.hip"):
         deps = [d for d in deps if "pnx_grid" not in os.path.basename(d)]  # the dictionary search's headers: its units and the ABI's
     elif src == "pnx_varpro.hip":
         deps = [d for d in deps if os.path.basename(d) == "pnx_grid_args.hpp" or "pnx_grid" not in os.path.basename(d)]  # of those, the slab rule only
@@ -171,6 +172,8 @@ def _stale(unit, force: bool) -> bool:
         deps = [d for d in deps if "pnx_grid_tmrf" not in os.path.basename(d)]  # the Student-t prior's headers: its unit and the ABI's
     if src not in ("pnx_api.hip", "pnx_grid_rician.hip"):  # the Rician likelihood's headers and log I0e: its unit and the ABI's
         deps = [d for d in deps if "pnx_grid_rician" not in os.path.basename(d) and os.path.basename(d) != "pnx_bessel.hpp"]
+    if src not in ("pnx_api.hip", "pnx_grid_refine.hip"):
+        deps = [d for d in deps if "pnx_grid_refine" not in os.path.basename(d)]  # the fine grid's headers: its unit and the ABI's
     if src not in ("pnx_api.hip", "pnx_grid_class.hip", "pnx_varpro_class.hip"):
         deps = [d for d in deps if "pnx_grid_class" not in os.path.basename(d)]  # the per-label prior's headers: its unit and the ABI's
     if src not in ("pnx_api.hip", "pnx_grid_prior.hip", "pnx_grid_marginal.hip", "pnx_grid_class.hip", "pnx_varpro_marginal.hip",

@@ -37,7 +37,7 @@ ABI_SYMBOLS = [
     "pnx_curvefit_varpro_posterior_field_f64", "pnx_curvefit_varpro_posterior_mrf_f64",
     "pnx_curvefit_varpro_posterior_logfield_f64", "pnx_curvefit_varpro_posterior_logmrf_f64",
     "pnx_curvefit_grid_neighbour_wfield_f64", "pnx_curvefit_grid_posterior_wfield_f64", "pnx_curvefit_grid_posterior_tmrf_f64",
-    "pnx_curvefit_grid_posterior_rician_f64", "pnx_log_i0e_f64",
+    "pnx_curvefit_grid_posterior_rician_f64", "pnx_log_i0e_f64", "pnx_curvefit_grid_refine_f64",
 ]
 
 
@@ -139,6 +139,9 @@ def load():
     lib.pnx_curvefit_grid_posterior_rician_f64.restype = C.c_int
     lib.pnx_curvefit_grid_posterior_rician_f64.argtypes = [C.POINTER(CurvefitOpts), C.c_int64, dp, dp, C.c_int, dp, dp, dp, dp, dp, C.c_double,
                                                            dp, dp, vp, dp, dp, dp, C.c_int, C.c_int, vp]
+    lib.pnx_curvefit_grid_refine_f64.restype = C.c_int
+    lib.pnx_curvefit_grid_refine_f64.argtypes = [C.POINTER(CurvefitOpts), C.c_int64, dp, dp, dp, dp, dp, C.c_int, C.c_double, vp, dp, dp, dp, dp, dp,
+                                                 dp, dp, dp, C.c_int, C.c_int, vp]
     lib.pnx_log_i0e_f64.restype = C.c_int
     lib.pnx_log_i0e_f64.argtypes = [C.c_int64, dp, dp, C.c_int, C.c_int, vp]
     # the unlabelled calls' arguments with n_classes, labels in front of log_prior (n_classes, n_atoms); the EM's loglik_class behind loglik

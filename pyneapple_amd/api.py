@@ -435,6 +435,63 @@ def grid_posterior_rician_device(opts, n_vox, b, y, atoms, fixed, lo, hi, log_pr
                                                         ptr(map_p), ptr(log_evidence), ptr(ess), MEM_DEVICE, int(device), stream))
 
 
+GRID_REFINE_MAX_POINTS = 9  # kRefineMaxPoints of csrc/pnx_grid_refine_args.hpp
+
+
+def grid_refine(model, b, y, lo, hi, n_points, centre, half_width, *, noise_sd=0.0, fixed_idx=(), fixed_vals=None, sigma=None,
+                project_amplitude=False, t1_mode=0, tr=0., tm=0., device=0, out=None):
+    """Posterior of every voxel over a fine grid of its own on host (numpy) arrays (pnx_curvefit_grid_refine_f64; method:
+    include/pnx.h): along free parameter k the n_points[k] (1..9) values from max(lo, centre - half_width) to
+    min(hi, centre + half_width), a uniform prior over their Cartesian product (at most 4096 atoms), the direct cost.
+    centre, half_width: (n_free, n_vox).  noise_sd > 0 known, <= 0 marginalised.  sigma and the T1 / STEAM factor are refused by the
+    library, by name.  Returns dict(mean, sd, map_p, edge_mass (n_free, n_vox), ess, log_norm (n_vox,)); log_norm is a local
+    normaliser, not an evidence; a voxel with a non-finite signal, centre or half-width, a negative half-width or no admitted atom is
+    NaN everywhere.  `out`: optional dict of preallocated result arrays under the same keys."""
+    _lib.require_device()
+    b = np.ascontiguousarray(b, np.float64)
+    y = np.ascontiguousarray(np.atleast_2d(y), np.float64)
+    n_vox, n_b = y.shape
+    if b.shape != (n_b,):
+        raise ValueError(f"b has shape {b.shape}, expected ({n_b},)")
+    lo, hi, centre, half_width = (np.ascontiguousarray(a, np.float64) for a in (lo, hi, centre, half_width))
+    fv = None
+    if len(fixed_idx):
+        fv = np.ascontiguousarray(fixed_vals, np.float64)
+        if fv.ndim != 1:
+            raise ValueError("grid_refine takes shared fixed values (n_fixed,): per-voxel fixed maps are not built")
+    o = make_opts(model, n_b, fixed_idx, jac="analytic", t1_mode=t1_mode, tr=tr, tm=tm, sigma=sigma)
+    n = o.n_free
+    npts = np.ascontiguousarray(n_points, np.int32)
+    if lo.shape != (n,) or hi.shape != (n,) or npts.shape != (n,):
+        raise ValueError(f"lo / hi / n_points must have shape ({n},)")
+    if centre.shape != (n, n_vox) or half_width.shape != (n, n_vox):
+        raise ValueError(f"centre and half_width must have shape ({n}, {n_vox}), got {centre.shape} and {half_width.shape}")
+    if fv is not None and fv.shape != (o.n_fixed,):
+        raise ValueError("fixed_vals has the wrong shape")
+    res = {key: _out(out, key, (n, n_vox), np.float64) for key in ("mean", "sd", "map_p", "edge_mass")}
+    res["ess"] = _out(out, "ess", (n_vox,), np.float64)
+    res["log_norm"] = _out(out, "log_norm", (n_vox,), np.float64)
+    check(load().pnx_curvefit_grid_refine_f64(C.byref(o), n_vox, ptr(b), ptr(y), ptr(fv), ptr(lo), ptr(hi), int(bool(project_amplitude)),
+                                              float(noise_sd), ptr(npts), ptr(centre), ptr(half_width), ptr(res["mean"]), ptr(res["sd"]),
+                                              ptr(res["map_p"]), ptr(res["ess"]), ptr(res["log_norm"]), ptr(res["edge_mass"]), MEM_HOST,
+                                              int(device), None))
+    return res
+
+
+def grid_refine_device(opts, n_vox, b, y, fixed, lo, hi, project_amplitude, noise_sd, n_points, centre, half_width, mean, sd, map_p, ess,
+                       log_norm, edge_mass, device, stream=None):
+    """Enqueue the fine-grid posterior on HBM-resident float64 torch tensors (asynchronous; caller synchronises): y (n_vox, n_b),
+    centre / half_width / mean / sd / map_p / edge_mass (n_free, n_vox), ess / log_norm (n_vox,) on the device, all outputs but mean
+    may be None; b, shared fixed values, lo, hi and n_points are host arrays.  `opts` from make_opts."""
+    b, lo, hi = (np.ascontiguousarray(a, np.float64) for a in (b, lo, hi))
+    if fixed is not None:
+        fixed = np.ascontiguousarray(fixed, np.float64)
+    npts = np.ascontiguousarray(n_points, np.int32)
+    check(load().pnx_curvefit_grid_refine_f64(C.byref(opts), int(n_vox), ptr(b), ptr(y), ptr(fixed), ptr(lo), ptr(hi),
+                                              int(bool(project_amplitude)), float(noise_sd), ptr(npts), ptr(centre), ptr(half_width), ptr(mean),
+                                              ptr(sd), ptr(map_p), ptr(ess), ptr(log_norm), ptr(edge_mass), MEM_DEVICE, int(device), stream))
+
+
 def grid_prior_slab_atoms(n_b):
     """Atoms per LDS slab of the two EM passes (grid_prior_slab of csrc/pnx_grid_prior_args.hpp): the posterior's slab at four
     parameter rows -- the four wave-private rows of the accumulate pass take the place of the parameter values."""

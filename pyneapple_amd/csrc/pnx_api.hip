@@ -22,6 +22,7 @@
 #include "pnx_grid_args.hpp"
 #include "pnx_grid_class.hpp"
 #include "pnx_grid_posterior.hpp"
+#include "pnx_grid_refine.hpp"
 #include "pnx_grid_rician.hpp"
 #include "pnx_grid_marginal.hpp"
 #include "pnx_grid_mrf.hpp"
@@ -1358,6 +1359,44 @@ int pnx_log_i0e_f64(int64_t n, const double *z, double *out, int mem, int device
     A.add(out, sizeof(double), 1, true);
     return ring_call(A, (size_t)n, 3 << 18, device, st,
                      [&](size_t m, const DevSet &S, hipStream_t s) { return log_i0e_device((int64_t)m, S.d(LI_Z), S.d(LI_OUT), s); });
+}
+
+// ---- a fine grid per voxel (kernel: pnx_grid_refine.hip, argument checks: pnx_grid_refine_args.hpp) -------------------------------
+int pnx_curvefit_grid_refine_f64(const pnx_curvefit_opts *o, int64_t n_vox, const double *b, const double *y, const double *fixed,
+                                 const double *lo, const double *hi, int project_amplitude, double noise_sd, const int32_t *n_points,
+                                 const double *centre, const double *half_width, double *mean, double *sd, double *map_p, double *ess,
+                                 double *log_norm, double *edge_mass, int mem, int device, void *stream) {
+    if (!o) return set_error(PNX_ERR_INVALID, "opts is NULL");
+    pnx_curvefit_opts c = *o;  // as grid start: jac_mode and the tolerances are not looked at
+    c.jac_mode = PNX_JAC_ANALYTIC;
+    c.ftol = c.xtol = c.gtol = 0.0;
+    int rc = check_curvefit_opts(&c);
+    if (rc) return rc;
+    GridRefineHost H;
+    if ((rc = grid_refine_check_args(&c, n_vox, b, y, fixed, lo, hi, project_amplitude, noise_sd, n_points, centre, half_width, mean, mem, &H)))
+        return rc;
+    if (n_vox == 0) return PNX_OK;
+    DeviceInfo *dev;
+    if ((rc = use_device(device, &dev))) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    if (mem == PNX_MEM_DEVICE)
+        return grid_refine_device(&c, H, n_vox, b, y, fixed, lo, hi, noise_sd, n_points, centre, half_width, mean, sd, map_p, ess, log_norm,
+                                  edge_mass, dev->cus, st);
+    enum { GR_Y, GR_CENTRE, GR_HW, GR_MEAN, GR_SD, GR_MAPP, GR_ESS, GR_LOGN, GR_EDGE };
+    ArrayTable A;
+    A.add(y, sizeof(double), c.n_b, false);
+    A.add(centre, sizeof(double), c.n_free, false).pmajor = true;
+    A.add(half_width, sizeof(double), c.n_free, false).pmajor = true;
+    A.add(mean, sizeof(double), c.n_free, true).pmajor = true;
+    A.add(sd, sizeof(double), c.n_free, true).pmajor = true;
+    A.add(map_p, sizeof(double), c.n_free, true).pmajor = true;
+    A.add(ess, sizeof(double), 1, true);
+    A.add(log_norm, sizeof(double), 1, true);
+    A.add(edge_mass, sizeof(double), c.n_free, true).pmajor = true;
+    return ring_call(A, (size_t)n_vox, 3 << 18, device, st, [&](size_t n, const DevSet &S, hipStream_t s) {
+        return grid_refine_device(&c, H, (int64_t)n, b, S.d(GR_Y), fixed, lo, hi, noise_sd, n_points, S.d(GR_CENTRE), S.d(GR_HW), S.d(GR_MEAN),
+                                  S.d(GR_SD), S.d(GR_MAPP), S.d(GR_ESS), S.d(GR_LOGN), S.d(GR_EDGE), dev->cus, s);
+    });
 }
 
 // ---- the prior over the dictionary learned from the volume (kernels: pnx_grid_prior.hip, argument checks: pnx_grid_prior_args.hpp)

@@ -872,7 +872,8 @@ class HipPeelSolver(RefBaseSolver):
         return self
 
 
-_BAYES_MESSAGES = {-2: "array must not contain infs or NaNs"}
+_BAYES_MESSAGES = {-2: "array must not contain infs or NaNs",
+                   -4: "refine: no atom of the fine grid is admitted (the box lies beyond f1 + f2 = 1)"}
 
 
 class HipBayesGridSolver(RefBaseSolver):
@@ -951,6 +952,23 @@ class HipBayesGridSolver(RefBaseSolver):
             0, project=True, sigma, empirical_prior, spatial_prior, marginals, a 2-D log_prior.  Any other value is a ValueError.
             A voxel with a negative signal entry is reported as one with a non-finite signal.  About 27 times the cost of the
             Gaussian call at 32 b-values (README).
+        refine: None / False (default: everything above, byte for byte).  True, or a dict with any of {"points": 5, "levels": 1,
+            "span": 1.0, "n_sd": 2.0} (TOML: a table [Fitting.solver.refine]; an unknown key is a ValueError): after the coarse
+            posterior (level 0, unchanged) every voxel gets `levels` (1..3) fine grids of its own, each a box around the previous
+            level's mean with `points` (1..9; a number, or {name: int}) values per gridded axis, a uniform prior and the direct cost
+            (pnx_curvefit_grid_refine_f64): resolution where the voxel's posterior sits, which a 4-value axis
+            cannot give.  half_width_k = max(span * cell_k, n_sd * sd_k): cell_k is, at level 1, the width of the coarse grid cell
+            that holds the mean (the gap between the two neighbouring grid values, the end gap at the ends), afterwards the previous
+            level's point spacing; sd_k the previous level's posterior sd.  The box is cut at `bounds`; an axis with one coarse value
+            (and a projected S0) keeps one value; at most 4096 atoms per voxel.  Atoms of a reduced layout with f1 + f2 > 1 are
+            dropped.  params_, posterior_sd and map then are the LAST level's; diagnostics_ gains "refine_levels",
+            "refine_edge_mass" {name: (n_pixels,)} (the posterior share on the two ends of the last box: large values say the box
+            truncates the posterior) and "refine_ess", and keeps the coarse "ess", "map_atom" and "log_evidence" (still the model
+            evidence; a fine grid has none).  A voxel whose fine box holds no admitted atom (a coarse mean beyond f1 + f2 = 1) gets
+            NaN parameters and success False.  Every level is one host call: the signal is uploaded and the level's results come
+            back per level.  Helps at 1 % noise, where the coarse grid is the limit, and does little at 5 %
+            (README).  A ValueError "refine is not built with ...": noise_model="rician", spatial_prior, empirical_prior, marginals,
+            per-label priors, a non-uniform log_prior, sigma, the T1 / STEAM factor.
     Not built, hence a ValueError: per-pixel fixed parameters (the dictionary would differ from voxel to voxel), io_dtype or
     precision "float32" (the posterior reads and writes float64 arrays and exponentiates in fp64).
     Any other keyword (the reference's solver arguments: method, multi_threading, ...) is accepted and ignored.
@@ -970,14 +988,16 @@ class HipBayesGridSolver(RefBaseSolver):
     _EMPIRICAL_PRIOR_DEFAULTS = {"n_iter": 20, "pseudo_count": 0.0, "rel_tol": 1e-6, "max_voxels": None}
     _EMPIRICAL_PRIOR_PER_LABEL = {"per_label": False}  # reported among the options only when it is on
     _SPATIAL_PRIOR_DEFAULTS = {"strength": None, "n_sweeps": 4, "tol": 0.0, "connectivity": 6}
+    _REFINE_DEFAULTS = {"points": 5, "levels": 1, "span": 1.0, "n_sd": 2.0}
 
     def __init__(self, model: Any, grid=None, max_iter: int = 250, tol: float = 1e-8, p0: dict[str, float] | None = None,
                  bounds: dict[str, tuple[float, float]] | None = None, noise_sd: float | None = None, log_prior=None, project=None,
                  sigma=None, device: int = 0, io_dtype: str = "float64", precision: str = "float64", empirical_prior=None,
-                 marginals=None, spatial_prior=None, noise_model: str = "gaussian", **ignored_reference_kwargs):
+                 marginals=None, spatial_prior=None, noise_model: str = "gaussian", refine=None, **ignored_reference_kwargs):
         RefBaseSolver.__init__(self, model=model, max_iter=max_iter, tol=tol, verbose=bool(ignored_reference_kwargs.pop("verbose", False)))
         self._kernel_model = kernel_model_key(model)
         self._kernel_t1 = kernel_t1(model)
+        self.refine = self._refine_options(refine, list(model.param_names))
         if noise_model not in ("gaussian", "rician"):
             raise ValueError(f"noise_model must be 'gaussian' or 'rician', got {noise_model!r}")
         self.noise_model = noise_model
@@ -1053,6 +1073,99 @@ class HipBayesGridSolver(RefBaseSolver):
             for what, hit in refused:
                 if hit:
                     raise ValueError(f"HipBayesGridSolver: noise_model 'rician' is not built with {what}")
+        if self.refine:
+            refused = [("noise_model='rician': the fine grid has the Gaussian likelihood", self.noise_model == "rician"),
+                       ("spatial_prior: the fine grid knows no field", bool(self.spatial_prior)),
+                       ("empirical_prior: a learned table has no values between the coarse atoms", bool(self.empirical_prior)),
+                       ("marginals: pnx_curvefit_grid_marginals_f64 reports the coarse grid's", bool(self.marginals)),
+                       ("per-label priors (a 2-D log_prior): the fine grid's prior is uniform", self.needs_labels),
+                       ("a non-uniform log_prior: the fine grid's prior is uniform",
+                        self.log_prior is not None and bool(np.ptp(self.log_prior) > 0.0)),
+                       ("sigma (per-b-value weights)", self.sigma is not None),
+                       ("the T1 / STEAM factor (fit_t1): T1 would need a table of its own per voxel", bool(self._kernel_t1.get("t1_mode")))]
+            for what, hit in refused:
+                if hit:
+                    raise ValueError(f"HipBayesGridSolver: refine is not built with {what}")
+            self._refine_points = self.refine_points()
+
+    @classmethod
+    def _refine_options(cls, value, names):
+        """None when off, else {"points": {name: int} for every parameter, "levels", "span", "n_sd"}, checked."""
+        if value is None or value is False:
+            return None
+        if value is True:
+            value = {}
+        if not isinstance(value, dict):
+            raise ValueError(f"refine must be None, a bool or a dict of {sorted(cls._REFINE_DEFAULTS)}, got {value!r}")
+        unknown = sorted(set(value) - set(cls._REFINE_DEFAULTS))
+        if unknown:
+            raise ValueError(f"refine has unknown keys {unknown}; it takes {sorted(cls._REFINE_DEFAULTS)}")
+        opt = {**cls._REFINE_DEFAULTS, **value}
+        pts = opt["points"]
+        if isinstance(pts, dict):
+            bad = sorted(set(pts) - set(names))
+            if bad:
+                raise ValueError(f"refine points names unknown parameters {bad}; the model has {names}")
+            pts = {n: pts.get(n, cls._REFINE_DEFAULTS["points"]) for n in names}
+        else:
+            pts = {n: pts for n in names}
+        for n, v in pts.items():
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 1 <= v <= api.GRID_REFINE_MAX_POINTS:
+                raise ValueError(f"refine points of {n} must be an integer in [1, {api.GRID_REFINE_MAX_POINTS}], got {v!r}")
+        lv = opt["levels"]
+        if isinstance(lv, bool) or not isinstance(lv, (int, np.integer)) or not 1 <= lv <= 3:
+            raise ValueError(f"refine levels must be an integer in [1, 3], got {lv!r}")
+        for key in ("span", "n_sd"):
+            v = opt[key]
+            if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not (np.isfinite(v) and v >= 0.0):
+                raise ValueError(f"refine {key} must be finite and >= 0, got {v!r}")
+        if not (opt["span"] > 0.0 or opt["n_sd"] > 0.0):
+            raise ValueError("refine needs span > 0 or n_sd > 0: both 0 leave a box of one value")
+        return {"points": {n: int(v) for n, v in pts.items()}, "levels": int(lv), "span": float(opt["span"]), "n_sd": float(opt["n_sd"])}
+
+    def _coarse_axes(self):
+        """Per free parameter the sorted distinct coarse grid values (one value for a parameter the grid does not name)."""
+        return [np.unique(row) for row in self._atoms]
+
+    def refine_points(self):
+        """n_points (n_free,) int32 of the fine grid: refine["points"] on every axis with more than one coarse value, 1 on a one-value
+        axis and on a projected S0; more than 4096 atoms per voxel is a ValueError."""
+        names = list(self.model.param_names)
+        npts = np.array([self.refine["points"][n] if ax.size > 1 and not (self.project and n == "S0") else 1
+                         for n, ax in zip(names, self._coarse_axes())], np.int32)
+        total = int(np.prod(npts, dtype=np.int64))
+        if total > api.GRID_MAX_ATOMS:
+            raise ValueError(f"refine points span {total} atoms per voxel, more than the {api.GRID_MAX_ATOMS} a fine grid takes")
+        return npts
+
+    @staticmethod
+    def coarse_cell(values, mean):
+        """Width of the coarse grid cell that holds `mean` (n_pixels,): the gap between the two neighbouring grid values, the end gap
+        at the ends and beyond, 0 for a one-value axis.  A NaN mean gives NaN."""
+        mean = np.asarray(mean, float)
+        if values.size < 2:
+            return np.zeros_like(mean)
+        gaps = np.diff(values)
+        j = np.clip(np.searchsorted(values, np.nan_to_num(mean, nan=values[0]), side="right") - 1, 0, gaps.size - 1)
+        return np.where(np.isnan(mean), np.nan, gaps[j])
+
+    def _fit_refine(self, xdata, ydata, mean, sd, lo, hi, fixed_idx, fixed_vals):
+        """The fine levels behind the coarse posterior (mean, sd (n_free, n_pixels)): the last level's result dict of api.grid_refine."""
+        rf, npts = self.refine, self._refine_points
+        many = npts[:, None] > 1
+        cell = np.stack([self.coarse_cell(ax, mean[k]) for k, ax in enumerate(self._coarse_axes())])
+        res = None
+        for _ in range(rf["levels"]):
+            half = np.where(many, np.maximum(rf["span"] * cell, rf["n_sd"] * sd), 0.0)
+            if self.project:  # the projected S0 row is fitted per atom: its centre and half-width are not read
+                half[list(self.model.param_names).index("S0")] = 0.0
+            centre = np.ascontiguousarray(mean)
+            res = api.grid_refine(self._kernel_model, xdata, ydata, lo, hi, npts, centre, np.ascontiguousarray(half), noise_sd=self.noise_sd,
+                                  fixed_idx=fixed_idx, fixed_vals=fixed_vals, project_amplitude=self.project, device=self.device)
+            a, b = np.maximum(lo[:, None], centre - half), np.minimum(hi[:, None], centre + half)
+            cell = np.where(many, np.maximum(b - a, 0.0) / np.maximum(npts[:, None] - 1, 1), 0.0)
+            mean, sd = res["mean"], res["sd"]
+        return res
 
     @property
     def needs_labels(self) -> bool:
@@ -1317,12 +1430,22 @@ class HipBayesGridSolver(RefBaseSolver):
         elif not self.needs_labels:
             res = api.grid_posterior(self._kernel_model, xdata, ydata, self._atoms, lo, hi, log_prior=log_prior, **common)
         mean, atom = res["mean"], res["map_atom"]
-        self.pixel_results_ = PixelResultsView(mean.T, None, atom >= 0,
-                                               lambda i, a=atom: None if a[i] >= 0 else _BAYES_MESSAGES[-2])
+        fine = None
+        if self.refine:
+            fine = self._fit_refine(xdata, np.ascontiguousarray(ydata, np.float64), mean, res["sd"], lo, hi, fixed_idx, fixed_vals)
+            mean = fine["mean"]
+            res = {**res, "sd": fine["sd"], "map_p": fine["map_p"]}
+        # with refine a voxel can also lose every fine atom to the fraction-sum rule (a coarse mean beyond the face f1 + f2 = 1)
+        good = atom >= 0 if fine is None else (atom >= 0) & np.isfinite(mean).all(axis=0)
+        self.pixel_results_ = PixelResultsView(mean.T, None, good,
+                                               lambda i, a=atom, g=good: None if g[i] else _BAYES_MESSAGES[-2 if a[i] < 0 else -4])
         self.params_ = {name: [float(mean[i, 0])] if n_pixels == 1 else mean[i] for i, name in enumerate(names)}
         self.diagnostics_ = {"posterior_sd": {n: res["sd"][i] for i, n in enumerate(names)},
                              "map": {n: res["map_p"][i] for i, n in enumerate(names)}, "map_atom": atom,
                              "log_evidence": res["log_evidence"], "ess": res["ess"], "n_pixels": n_pixels}
+        if fine is not None:
+            self.diagnostics_.update({"refine_levels": self.refine["levels"], "refine_ess": fine["ess"],
+                                      "refine_edge_mass": {n: fine["edge_mass"][i] for i, n in enumerate(names)}})
         if self.noise_model != "gaussian":
             self.diagnostics_["noise_model"] = self.noise_model
         if learned is not None:
